@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/s of the EmLoco rollout hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps of the headline loop and prints its line (headline, `roofline` of the rigid-body
+kernel from the HIP events of those same steps, `summary`).  `--full` adds every other leg: env.step alone, the policy / configs[2] /
+PPO legs, the JTA train step (both precision classes, bool padding mask) with the JRDB evaluation, and the CPU baselines; the `--no_*`
+options switch single legs of a `--full` run off.  `--dump-outputs DIR` writes what the last timed step computed (rank 0's envs) as
+DIR/<name>.npy, float32 / float64: the same arguments give the same inputs, so two builds can be compared output for output.
 
 One "step" = one iteration of the rollout loop AMPValueAgent.play_steps drives (amp_continuous_value.py:45-145): reset the
 envs that finished, pre-physics -> 4 fused physics substeps -> fused post-physics, then the LocoVal bookkeeping (discounted
@@ -604,6 +610,45 @@ def locoval_policy_leg(env, E, dev, steps, warmup):
                     "the sequential order (tests/test_gpu_env.py); EMLOCO_DEFER_DISC=0 puts the discriminator back between env.step and the reset"}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, agent, task):
+    """--dump-outputs: what the timed loop's last step handed its caller -- observations, reward, reset / terminate flags, episode
+    progress, the simulator state -- and what that step's LocoVal bookkeeping / fit left (per-env return accumulators, the fitted
+    network as its flat parameter vector, the fit statistics).  Written after the timed region: the pending fits are flushed and the
+    deferred observation pass of the last step is launched (task.wait_obs), as for any caller that reads them.  Above DUMP_MAX_BYTES
+    in all, the per-env arrays keep a fixed seeded sample of envs (`env_index.npy`)."""
+    import torch
+    agent._sync_fit()
+    task.wait_obs()
+    torch.cuda.synchronize()
+    E = task.num_envs
+    per_env = {"obs": task.obs_buf, "reward": task.rew_buf, "reset": task.reset_buf, "terminate": task._terminate_buf,
+               "progress": task.progress_buf, "rigid_body_state": task._rigid_body_state.view(E, -1, 13),
+               "dof_state": task._dof_state.view(E, -1, 2), "root_state": task._humanoid_root_states,
+               "locoval_current_rewards": agent.acc.current_rewards, "locoval_current_lengths": agent.acc.current_lengths,
+               "locoval_current_combined_rewards": agent.acc.current_combined_rewards,
+               "locoval_discount_coefs": agent.acc.discount_coefs}
+    whole = {"locoval_params": agent._flat_params, "locoval_stats": agent._stats}
+
+    def host(t):
+        a = t.detach().cpu().numpy()
+        return a.astype(np.float64 if a.dtype in (np.float64, np.int64, np.int32) else np.float32)
+    arrays = {k: host(v) for k, v in per_env.items()}
+    fixed = {k: host(v) for k, v in whole.items()}
+    fixed_bytes = sum(a.nbytes for a in fixed.values())
+    env_bytes = sum(a.nbytes for a in arrays.values()) / E
+    if fixed_bytes + E * env_bytes > DUMP_MAX_BYTES:
+        keep = int((DUMP_MAX_BYTES - fixed_bytes) // (env_bytes + 8))          # + the env's row of env_index
+        idx = np.sort(np.random.default_rng(0).choice(E, size=keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["env_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in {**arrays, **fixed}.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a))
+
+
 def summary_of(out):
     """Compact digest of the line (numbers only, no notes), printed as its last key so that a reader of the TAIL of stdout sees every leg:
     headline, the rigid-body kernel, env_step_only, policy, configs[2] (frozen policy + discriminator reward + LocoVal fit), the PPO
@@ -638,11 +683,17 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--num_envs", type=int, default=4096, help="envs per GPU")
-    ap.add_argument("--no_cpu_baseline", action="store_true")
-    ap.add_argument("--no_policy", action="store_true", help="skip the frozen-policy leg (row A19, reported separately)")
-    ap.add_argument("--no_jta", action="store_true", help="skip the train_jta samples/s leg (run on rank 0 at N=1)")
-    ap.add_argument("--no_ppo", action="store_true", help="skip the PPO + AMP train_epoch leg (configs[1] end to end; rank 0 at N=1, under `policy`)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: env.step alone, policy / configs[2] / PPO, JTA train step + JRDB eval, CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
+    ap.add_argument("--no_cpu_baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no_policy", action="store_true", help="with --full: skip the frozen-policy leg (row A19, reported separately)")
+    ap.add_argument("--no_jta", action="store_true", help="with --full: skip the train_jta samples/s leg (run on rank 0 at N=1)")
+    ap.add_argument("--no_ppo", action="store_true", help="with --full: skip the PPO + AMP train_epoch leg (configs[1] end to end; rank 0 at N=1, under `policy`)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # bare `python bench.py --gpus N`: become the launcher -- one process per GPU, as the driver's
         # `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...` does
@@ -729,10 +780,12 @@ def main():
         all_reduce_(t, dist.ReduceOp.MAX)
         elapsed = float(t.item())
     fitted, vloss = agent.fitted_episodes, agent.vnet_loss
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, agent, task)
 
-    # env.step alone in the same (sequential) schedule, no LocoVal bookkeeping / fit: reported beside the headline at N = 1
+    # env.step alone in the same (sequential) schedule, no LocoVal bookkeeping / fit: reported beside the headline at N = 1 (--full)
     env_only = None
-    if world == 1:
+    if world == 1 and a.full:
         agent._sync_fit()
         agent.detach()                                   # the LocoVal return bookkeeping leaves the task's flags launch
         for k in range(a.warmup):
@@ -793,7 +846,7 @@ def main():
                                     "note": "reset_done + env.step in the same sequential schedule without the LocoVal bookkeeping / fit; kernel_ms = "
                                             "sim_step_kernel with nothing but the observation launch of the previous step beside it"}
             out["sequential"] = dict(out["env_step_only"])         # the name earlier rounds reported this leg under
-        if world == 1 and not a.no_policy:
+        if world == 1 and a.full and not a.no_policy:
             # a policy reads the reset envs' fresh observations, so the reset chain cannot hide beside the step: the sequential
             # schedule (observation launch of the live envs beside the reset chain, cost-ordered dispatch) is the faster one here
             # (measured: 3.95 M against 3.78 M env-steps/s)
@@ -803,10 +856,10 @@ def main():
             out["policy"]["with_discriminator_and_locoval_fit"] = locoval_policy_leg(env, E, dev, a.steps, a.warmup)
             if not a.no_ppo:
                 out["policy"]["ppo"] = ppo_leg(env, E, dev)
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
     # the JTA train-step and evaluation legs run on every rank (data parallel at N > 1); rank 0 reports
-    if not a.no_jta:
+    if a.full and not a.no_jta:
         del agent, env, task, pool
         torch.cuda.empty_cache()
         jta = jta_leg(dev, rank=rank, world=world)

@@ -411,7 +411,7 @@ def test_two_rank_evaluation_equals_single_rank():
 
 # ------------------------------------------------------------------------------------------------ launcher / RCCL smoke
 def test_bench_launcher_four_ranks_sharing_the_gpu_prints_one_json_line():
-    """`EMLOCO_BENCH_SHARE_GPU=1 python bench.py --gpus 4 --num_envs 256` -- the driver's multi-GPU contract on a one-GPU box: bench.py
+    """`EMLOCO_BENCH_SHARE_GPU=1 python bench.py --gpus 4 --num_envs 256 --full` -- the driver's multi-GPU contract on a one-GPU box: bench.py
     becomes the launcher (torch.distributed.run, 127.0.0.1), four ranks shard the envs, the timed loop is bracketed by barriers with
     MAX-over-ranks timing, the JTA / evaluation legs run data parallel, rank 0 prints ONE JSON line whose value counts all ranks'
     envs.  (gloo instead of RCCL: four processes on one device are refused by the collective library; no scaling number is
@@ -422,7 +422,7 @@ def test_bench_launcher_four_ranks_sharing_the_gpu_prints_one_json_line():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, EMLOCO_BENCH_SHARE_GPU="1", PYTHONPATH=root)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--num_envs", "256", "--steps", "20", "--warmup", "5",
-                        "--no_cpu_baseline"], cwd=root, env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--no_cpu_baseline"], cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -452,6 +452,36 @@ def test_bench_launcher_eight_ranks_sharing_the_gpu_runs_the_drivers_rank_count(
     assert d["config"]["num_envs_per_gpu"] == 128 and "x8" in d["config"]["parallelism"] and "TEST MODE" in d["config"]["parallelism"]
     assert abs(d["value"] - 8 * 128 * 12 / (d["ms_per_step"] * 12 / 1e3)) < 0.02 * d["value"]      # whole-job aggregate over the eight shards
     assert d["summary"]["headline_env_steps_per_s"] == d["value"] and list(d)[-1] == "summary"      # the digest closes the line
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """`bench.py --gpus 1 --steps 7 --warmup 3 --dump-outputs DIR` without --full: ONE JSON line with the headline keys, exactly
+    --steps timed steps, none of the --full legs; DIR holds the last timed step's arrays as float32 / float64 .npy files (every
+    env at this size, 64 MB at most) and the observations are the task's finished ones (finite, one row per env)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--num_envs", "256", "--steps", "7", "--warmup", "3",
+                        "--dump-outputs", str(out)], cwd=root, env=dict(os.environ, PYTHONPATH=root), capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 7 and d["warmup"] == 3 and d["ms_per_step"] > 0 and d["dtype"] == "f32" and d["higher_is_better"] is True
+    assert abs(d["value"] - 256 * 7 / (d["ms_per_step"] * 7 / 1e3)) < 0.02 * d["value"]
+    for k in ("env_step_only", "policy", "cpu_baseline", "jta"):
+        assert k not in d, k
+    assert list(d)[-1] == "summary" and d["roofline"]["launches_timed"] > 0
+    files = {p.name: np.load(p) for p in out.glob("*.npy")}
+    assert {"obs.npy", "reward.npy", "reset.npy", "rigid_body_state.npy", "locoval_params.npy"} <= set(files)
+    assert "env_index.npy" not in files and sum(a.nbytes for a in files.values()) <= 64 << 20
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert files["obs.npy"].shape == (256, 1422) and np.isfinite(files["obs.npy"]).all()
+    assert files["rigid_body_state.npy"].shape == (256, 24, 13) and files["locoval_params.npy"].shape == (6174,)
 
 
 def _rccl_worker(rank, world, port, q):

@@ -6,7 +6,7 @@ OUT=gpurun_out/r04/ab_event_scope.txt
 for rep in 1 2; do
 for v in system device; do
   echo "== EMLOCO_EVENT_SCOPE=$v" >> $OUT
-  EMLOCO_EVENT_SCOPE=$v timeout 300 python bench.py --no_jta --no_policy --no_ppo 2>/dev/null | python -c "
+  EMLOCO_EVENT_SCOPE=$v timeout 300 python bench.py --full --no_jta --no_policy --no_ppo 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readlines()[-1]); print(d['value'], d['ms_per_step'], d.get('env_step_only'))" >> $OUT
 done; done

@@ -5,7 +5,7 @@ OUT=gpurun_out/r04/ab_small_tile.txt
 : > $OUT
 run() {
   echo "== $*" >> $OUT
-  env "$@" timeout 300 python bench.py --steps 100 --warmup 20 --no_cpu_baseline --no_jta --no_ppo 2>/dev/null | python -c "
+  env "$@" timeout 300 python bench.py --full --steps 100 --warmup 20 --no_cpu_baseline --no_jta --no_ppo 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -3,7 +3,7 @@
 R=${1:-r04}
 F=gpurun_out/$R/final
 mkdir -p $F
-python bench.py > $F/bench_default.log 2>$F/bench_default.err
+python bench.py --full > $F/bench_default.log 2>$F/bench_default.err
 bash tools/collect_profiles.sh $R > $F/collect.log 2>&1
 bash tools/exp/prof_env2.sh $F/env_step_trace.txt > /dev/null 2>&1
 bash tools/exp/prof_env_disc.sh $F/env_step_trace_disc.txt > /dev/null 2>&1
