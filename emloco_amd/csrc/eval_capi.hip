@@ -1,0 +1,54 @@
+// eval_capi.hip -- C ABI of the LocoVal evaluation kernels (include/emloco_predictor.h: emloco_locoval_eval_*).
+#include <hip/hip_runtime.h>
+#include <cstdio>
+#include "eval_kernels.hip"
+
+namespace {
+int efail(int code, const char *what, hipError_t e = hipSuccess) {
+    if (e != hipSuccess) fprintf(stderr, "[emloco] %s: %s\n", what, hipGetErrorString(e));
+    else fprintf(stderr, "[emloco] %s\n", what);
+    return code;
+}
+}  // namespace
+
+#define EHIPCHK(expr)                                                  \
+    do {                                                               \
+        hipError_t e_ = (expr);                                        \
+        if (e_ != hipSuccess) return efail(-2, #expr, e_);             \
+    } while (0)
+
+static_assert(sizeof(EmlocoLocoValRecord) == 48, "EmlocoLocoValRecord is 48 bytes (the numpy dtype of learning/locoval_eval.py)");
+
+extern "C" {
+
+int emloco_locoval_eval_step(const EmlocoLocoValEval *s, const float *reward_raw, const float *disc, const int64_t *dones,
+                             const int64_t *terminate, const uint8_t *inverted, void *stream) {
+    if (!s || s->n_env < 1 || s->games_per_env < 1 || !reward_raw || !dones || !s->coef || !s->c_disc || !s->tp_disc || !s->cr ||
+        !s->c_loc || !s->c_pow || !s->tp_cr || !s->tp_loc || !s->tp_pow || !s->steps || !s->games || !s->done || !s->terminated ||
+        !s->inverted || !s->waypoint_traj || !s->init_pose || !s->init_vel || !s->traj13 || !s->pose || !s->vel || !s->row_mask)
+        return efail(-1, "emloco_locoval_eval_step: bad argument");
+    hipLaunchKernelGGL(emloco::locoval_eval_step_kernel, dim3((unsigned)((s->n_env + 3) / 4)), dim3(256), 0, (hipStream_t)stream, *s,
+                       reward_raw, disc, dones, terminate, inverted);
+    EHIPCHK(hipGetLastError());
+    return 0;
+}
+
+int emloco_locoval_eval_finish(const EmlocoLocoValEval *s, const float *value, EmlocoLocoValRecord *records, void *stream) {
+    if (!s || s->n_env < 1 || s->games_per_env < 1 || !value || !records || !s->n_full || !s->games || !s->done || !s->steps)
+        return efail(-1, "emloco_locoval_eval_finish: bad argument");
+    hipLaunchKernelGGL(emloco::locoval_eval_finish_kernel, dim3((unsigned)((s->n_env + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *s,
+                       value, records);
+    EHIPCHK(hipGetLastError());
+    return 0;
+}
+
+int emloco_locoval_eval_reduce(int n_env, int games_per_env, const EmlocoLocoValRecord *records, const int32_t *games, double *moments,
+                               void *stream) {
+    if (n_env < 1 || games_per_env < 1 || !records || !games || !moments) return efail(-1, "emloco_locoval_eval_reduce: bad argument");
+    hipLaunchKernelGGL(emloco::locoval_eval_reduce_kernel, dim3(1), dim3(emloco::kEvalReduceThreads), 0, (hipStream_t)stream, n_env,
+                       games_per_env, records, games, moments);
+    EHIPCHK(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"

@@ -1,0 +1,290 @@
+"""LocoVal evaluation: the `--test` player of the reference, batched on the device.
+
+Mirror of pacer/pacer/learning/amp_value_players.py:35-272 (AMPPlayerContinuousValue.run, the `plot_val_reward: True` branch of
+the shipped player config): the frozen policy plays deterministically; for every game the loop records the discounted return up
+to `step_to_pred` and its locomotion / power / style parts, what LocoVal predicted for the game's start, the squared error of
+that prediction against the normalised return, the return at the end and the game's length; at the end it prints the averages,
+the (population) standard deviations and the Pearson correlations of prediction against return.
+
+The reference plays one env at a time and reads the device every step.  Here every env of the batch plays its own games one after
+another with the semantics of the reference's single-env game, and the bookkeeping is three HIP launches per step
+(include/emloco_predictor.h: emloco_locoval_eval_step -> emloco_locoval_fwd_rows -> emloco_locoval_eval_finish).  Each env records
+exactly its first G = ceil(games_num / E_total) games -- stopping at the first `games_num` finished games would over-sample short
+games -- into a slot of its own (records[env][game]: fixed order, deterministic), keeps stepping once its quota is met, and records
+nothing more.  The host reads one device counter (envs whose quota is met) every `poll_every` steps and nothing else until the end,
+when one launch reduces the records to a moment vector (in double, fixed order); ranks all-reduce that vector once, and
+`report_from_moments` turns it into the reference's numbers and printed lines.
+"""
+import math
+
+import numpy as np
+import torch
+
+from .. import dist as D
+
+# EmlocoLocoValRecord (include/emloco_predictor.h), 48 bytes
+RECORD_DTYPE = np.dtype({"names": ["disc_to_pred", "value", "cr_to_pred", "loc_to_pred", "pow_to_pred", "norm", "sq_err", "cr_end",
+                                   "steps", "terminated", "inverted"],
+                         "formats": ["<f8"] + ["<f4"] * 7 + ["<i4"] * 3,
+                         "offsets": [0, 8, 12, 16, 20, 24, 28, 32, 36, 40, 44], "itemsize": 48})
+RECORD_WORDS = RECORD_DTYPE.itemsize // 4
+# the moment vector of emloco_locoval_eval_reduce (EMLOCO_EVAL_MOMENTS doubles)
+MOMENT_NAMES = ("games", "sum_v", "sum_v2",
+                "sum_total", "sum_total2", "sum_v_total", "sum_loc", "sum_loc2", "sum_v_loc",
+                "sum_pow", "sum_pow2", "sum_v_pow", "sum_disc", "sum_disc2", "sum_v_disc",
+                "sum_sq_err", "sum_cr_end", "sum_steps", "terminated", "inverted")
+PARTS = ("total", "loc", "pow", "disc")
+_Y_FIELD = {"total": "cr_to_pred", "loc": "loc_to_pred", "pow": "pow_to_pred", "disc": "disc_to_pred"}
+
+
+def moments_from_records(rec):
+    """The moment vector of a structured array of records (RECORD_DTYPE), in float64, summed in record order -- what
+    emloco_locoval_eval_reduce computes on the device (there in a fixed tree order)."""
+    m = np.zeros(len(MOMENT_NAMES), np.float64)
+    v = rec["value"].astype(np.float64)
+    m[0] = len(rec)
+    m[1], m[2] = float(np.add.reduce(v)), float(np.add.reduce(v * v))
+    for k, part in enumerate(PARTS):
+        y = rec[_Y_FIELD[part]].astype(np.float64)
+        m[3 + 3 * k], m[4 + 3 * k], m[5 + 3 * k] = float(np.add.reduce(y)), float(np.add.reduce(y * y)), float(np.add.reduce(v * y))
+    m[15] = float(np.add.reduce(rec["sq_err"].astype(np.float64)))
+    m[16] = float(np.add.reduce(rec["cr_end"].astype(np.float64)))
+    m[17] = float(np.add.reduce(rec["steps"].astype(np.float64)))
+    m[18] = float(np.count_nonzero(rec["terminated"]))
+    m[19] = float(np.count_nonzero(rec["inverted"]))
+    return m
+
+
+def _std(n, s, s2):
+    """numpy's population std from the sums (amp_value_players.py:260: np.std, ddof 0)."""
+    var = (s2 - s * s / n) / n
+    return math.sqrt(max(var, 0.0))
+
+
+def _corr(n, sv, sv2, sy, sy2, svy):
+    """np.corrcoef(v, y)[0, 1] from the sums (NaN where a variance is zero, as numpy returns it)."""
+    cov = n * svy - sv * sy
+    den = (n * sv2 - sv * sv) * (n * sy2 - sy * sy)
+    if not den > 0.0:
+        return float("nan")
+    return max(-1.0, min(1.0, cov / math.sqrt(den)))
+
+
+def report_from_moments(m):
+    """The reference's summary (amp_value_players.py:256,258,260,268-271, same formats) from a moment vector: a dict of the numbers
+    and `lines`, the lines the reference prints (the Correlation line carries the reference's embedded newline)."""
+    m = [float(x) for x in m]
+    n = m[0]
+    if n < 1:
+        return {"games": 0, "lines": ["no game finished"]}
+    r = {"games": int(round(n))}
+    r["av_reward"], r["av_steps"], r["av_value_loss"] = m[16] / n, m[17] / n, m[15] / n
+    r["av_value"] = m[1] / n
+    r["std_value"] = _std(n, m[1], m[2])
+    for k, part in enumerate(PARTS):
+        s, s2, svy = m[3 + 3 * k], m[4 + 3 * k], m[5 + 3 * k]
+        r["av_" + part] = s / n
+        r["std_" + part] = _std(n, s, s2)
+        r["corr_" + part] = _corr(n, m[1], m[2], s, s2, svy)
+    r["terminated"], r["inverted"] = int(round(m[18])), int(round(m[19]))
+    r["lines"] = [
+        f"av reward: {r['av_reward']:.3f}, av steps: {r['av_steps']:.3f}, av value loss: {r['av_value_loss']:.3f}",
+        f"av_loc: {r['av_loc']:.2f}, av_pow: {r['av_pow']:.2f}, av_disc: {r['av_disc']:.2f}, av_total: {r['av_total']:.2f}",
+        f"std_loc: {r['std_loc']:.2f}, std_pow: {r['std_pow']:.2f}, std_disc: {r['std_disc']:.2f}, std_total: {r['std_total']:.2f}",
+        f"Correlation: \n Total reward: {r['corr_total']:.3f}",
+        f"Loc reward: {r['corr_loc']:.3f}",
+        f"Pow reward: {r['corr_pow']:.3f}",
+        f"Disc reward: {r['corr_disc']:.3f}",
+    ]
+    return r
+
+
+class LocoValEvaluator:
+    """Plays `games_num` games (all ranks together) of a frozen policy and scores a LocoVal network on them.
+
+    vec_env: the RLGPUEnv / VecTaskPythonWrapper of the task (this rank's shard of the envs).
+    policy_bundle: an AMPPolicyBundle (the deterministic action of its FrozenPolicy, the style reward of its FrozenDisc), or a
+      callable obs -> actions (then `disc_reward`, a callable amp_obs -> (E,), or None for a style reward of 0).
+    valuenet: a ValuePoseNet on the task's device (the fused HIP forward evaluates it).
+    max_steps: the step cap of the reference's player (rl_games BasePlayer: 27 000); a run whose games never finish stops there and
+      the report states the shortfall."""
+
+    def __init__(self, vec_env, policy_bundle, valuenet, games_num, max_steps=27000, poll_every=16, gamma=0.99, disc_reward=None):
+        from ..predictor import ops
+        from .value_pose_net import ValuePoseNet
+        self.vec_env = vec_env
+        env = vec_env.env if hasattr(vec_env, "env") else vec_env
+        self.env, self.task = env, env.task
+        task = self.task
+        self.device = torch.device(task.device)
+        if self.device.type != "cuda" or not isinstance(valuenet, ValuePoseNet):
+            raise RuntimeError("LocoValEvaluator runs its bookkeeping and the LocoVal forward as HIP kernels: it needs a gfx950 device, "
+                               "libemloco_hip.so and the HIP ValuePoseNet (there is no CPU path in the product)")
+        for flag in ("fused_chain", "overlap_obs", "overlap_reset"):
+            if getattr(task, flag, False):        # the loop reads the inputs the task captured at reset right after env.step
+                raise RuntimeError(f"LocoValEvaluator: task.{flag} is set (a loop that left it on must detach() first)")
+        if hasattr(task, "attach_returns"):
+            task.attach_returns(None)             # no training bookkeeping rides in the task's flags launch here
+        if getattr(task, "amp_ring", False):
+            task.enable_amp_ring(False)
+        if int(games_num) < 1:
+            raise ValueError("games_num must be at least 1")
+        self.valuenet = valuenet
+        if hasattr(policy_bundle, "frozen"):
+            bundle = policy_bundle
+            self.policy = lambda obs: bundle.frozen.act(obs, deterministic=True, generator=bundle.generator)
+            self.disc_reward = disc_reward or bundle.disc_reward
+        else:
+            self.policy, self.disc_reward = policy_bundle, disc_reward
+        E = task.num_envs
+        self.num_envs = E
+        self.games_num = int(games_num)
+        e_total = torch.tensor([E], dtype=torch.float64, device=self.device)
+        D.all_reduce_(e_total)
+        self.envs_total = int(e_total.item())
+        self.games_per_env = G = -(-self.games_num // self.envs_total)
+        self.max_steps, self.poll_every, self.gamma = int(max_steps), max(1, int(poll_every)), float(gamma)
+        self.step_to_pred = int(task.step_to_pred)
+        dev = self.device
+        f = lambda *s: torch.zeros(*s, device=dev)
+        i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)
+        u8 = lambda *s: torch.zeros(*s, dtype=torch.uint8, device=dev)
+        self._b = b = dict(coef=torch.ones(E, dtype=torch.float64, device=dev), c_disc=torch.zeros(E, dtype=torch.float64, device=dev),
+                           tp_disc=torch.zeros(E, dtype=torch.float64, device=dev), cr=f(E), c_loc=f(E), c_pow=f(E), tp_cr=f(E),
+                           tp_loc=f(E), tp_pow=f(E), steps=i32(E), games=i32(E), done=u8(E), terminated=u8(E), inverted=u8(E),
+                           n_full=i32(1), traj13=f(E, 13, 3), pose=f(E, 24, 3), vel=f(E, 2), row_mask=f(E))
+        # the forward's persistent output (a game's prediction stays in its row until the game is recorded) and its scratch rows
+        self._value, self._x100, self._h1, self._h2, self._ang = f(E), f(E, 100), f(E, 49), f(E, 24), f(E)
+        self._records = torch.zeros(E * G * RECORD_WORDS, dtype=torch.int32, device=dev)
+        self._moments = torch.zeros(ops.EVAL_MOMENTS, dtype=torch.float64, device=dev)
+        self._inputs = ("waypoint_traj", "init_pose", "init_vel")
+        p = lambda t: t.data_ptr()
+        self._s = ops.LocoValEval(E, self.step_to_pred, G, 0, self.gamma, *[p(b[k]) for k in (
+            "coef", "c_disc", "tp_disc", "cr", "c_loc", "c_pow", "tp_cr", "tp_loc", "tp_pow", "steps", "games", "done", "terminated",
+            "inverted", "n_full")], *[p(self._input(k)) for k in self._inputs], p(b["traj13"]), p(b["pose"]), p(b["vel"]), p(b["row_mask"]))
+        self.steps_run = 0
+        self.started = False
+
+    def _input(self, name):
+        """The task's LocoVal inputs the kernel reads by address (15 x 3 waypoints, 24 x 3 joints, 2 velocity components per env)."""
+        t = getattr(self.task, name)
+        want = {"waypoint_traj": (self.num_envs, 15, 3), "init_pose": (self.num_envs, 24, 3), "init_vel": (self.num_envs, 2)}[name]
+        if tuple(t.shape) != want or t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device:
+            raise RuntimeError(f"LocoValEvaluator: task.{name} must be a contiguous float32 {want} tensor on {self.device}")
+        return t
+
+    def _check_inputs(self):
+        for k, ptr in zip(self._inputs, (self._s.waypoint_traj, self._s.init_pose, self._s.init_vel)):
+            if self._input(k).data_ptr() != ptr:
+                raise RuntimeError(f"LocoValEvaluator: the task re-allocated {k} after the evaluator took its address")
+
+    # ------------------------------------------------------------------ one step
+    def step_once(self):
+        """env_reset(done_indices) -> deterministic action -> env.step -> style reward -> the three launches (:116-204)."""
+        task = self.task
+        with torch.no_grad():
+            if not self.started:
+                self.env.reset(torch.arange(self.num_envs, device=self.device))
+                self.started = True
+            elif hasattr(self.env, "reset_done"):
+                self.env.reset_done()
+            else:
+                self.env.reset(task.reset_buf.nonzero(as_tuple=False).flatten())
+            actions = self.policy(task.obs_buf)
+            _obs, _rew, dones, infos = self.vec_env.step(actions)
+            disc = None if self.disc_reward is None else self.disc_reward(infos["amp_obs"]).contiguous().float()
+            self._launch(task.reward_raw, disc, dones, infos.get("terminate", getattr(task, "_terminate_buf", None)), task.inverted)
+        self.steps_run += 1
+
+    def _launch(self, reward_raw, disc, dones, terminate, inverted):
+        """The bookkeeping of one step on the current stream (also the entry point of the tests that script the streams)."""
+        import ctypes as C
+        from ..predictor import ops
+        from ..sim import current_stream_handle
+        lib = ops._lib()
+        st = current_stream_handle(self.device)
+        P = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        assert reward_raw.dtype == torch.float32 and reward_raw.shape == (self.num_envs, 2) and dones.dtype == torch.int64
+        assert terminate is None or terminate.dtype == torch.int64
+        if inverted is not None and inverted.dtype == torch.bool:
+            inverted = inverted.view(torch.uint8)
+        self._check_inputs()
+        ops._chk(lib.emloco_locoval_eval_step(C.byref(self._s), P(reward_raw.contiguous()), P(disc), P(dones.contiguous()),
+                                              P(None if terminate is None else terminate.contiguous()),
+                                              P(None if inverted is None else inverted.contiguous()), st), "emloco_locoval_eval_step")
+        self._forward(st)
+        ops._chk(lib.emloco_locoval_eval_finish(C.byref(self._s), P(self._value), P(self._records), st), "emloco_locoval_eval_finish")
+
+    def _forward(self, st):
+        """LocoVal on the rows whose game took its first step (:128-134), into the persistent `value` rows."""
+        import ctypes as C
+        from ..predictor import ops
+        P = lambda t: C.c_void_p(t.data_ptr())
+        b, n = self._b, self.valuenet._network
+        w = [n.fc1.weight, n.fc1.bias, n.fc2.weight, n.fc2.bias, n.fc3.weight, n.fc3.bias]
+        for t in w:
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.device == self.device
+        ops._chk(ops._lib().emloco_locoval_fwd_rows(self.num_envs, P(b["traj13"]), 3, P(b["pose"]), P(b["vel"]), *[P(t) for t in w],
+                                                    P(self._value), P(self._x100), P(self._h1), P(self._h2), P(self._ang), P(b["row_mask"]),
+                                                    st), "emloco_locoval_fwd_rows")
+
+    # ------------------------------------------------------------------ the run
+    def envs_full(self):
+        """Envs of this rank whose quota is met (a host read)."""
+        return int(self._b["n_full"].item())
+
+    def run(self, say=print):
+        """Step until every env of this rank has recorded its quota (polled every `poll_every` steps) or `max_steps` is reached; then one
+        reduction, one all-reduce of the moment vector (all ranks), the report.  Returns the report dict."""
+        while self.steps_run < self.max_steps:
+            self.step_once()
+            if self.steps_run % self.poll_every == 0 and self.envs_full() == self.num_envs:
+                break
+        return self.report(say=say)
+
+    def moments(self):
+        import ctypes as C
+        from ..predictor import ops
+        from ..sim import current_stream_handle
+        P = lambda t: C.c_void_p(t.data_ptr())
+        ops._chk(ops._lib().emloco_locoval_eval_reduce(self.num_envs, self.games_per_env, P(self._records), P(self._b["games"]),
+                                                       P(self._moments), current_stream_handle(self.device)), "emloco_locoval_eval_reduce")
+        m = self._moments.clone()
+        D.all_reduce_(m)                            # the one collective of the evaluation
+        return m.cpu().numpy()
+
+    def report(self, say=print):
+        m = self.moments()
+        rep = report_from_moments(m)
+        full = torch.tensor([float(self.envs_full()), float(self.steps_run)], dtype=torch.float64, device=self.device)
+        D.all_reduce_(full)
+        expected = self.envs_total * self.games_per_env
+        rep.update(games_requested=self.games_num, envs=self.envs_total, games_per_env=self.games_per_env, games_expected=expected,
+                   shortfall=expected - rep["games"], steps=self.steps_run, max_steps=self.max_steps, ranks=D.world_size(),
+                   moments=[float(x) for x in m])
+        head = [f"LocoVal evaluation: {rep['games']} games = {self.envs_total} envs x {self.games_per_env} (the first "
+                f"{self.games_per_env} games of every env), {self.steps_run} steps"]
+        if expected != self.games_num:
+            head.append(f"  games_num {self.games_num} is not a multiple of the {self.envs_total} envs: {expected} games are recorded")
+        if rep["shortfall"] > 0:
+            head.append(f"  step cap {self.max_steps} reached: {rep['shortfall']} of {expected} games did not finish")
+        if rep["games"] > 0:
+            head.append(f"  early terminations {rep['terminated']}, inverted paths {rep['inverted']}")
+        rep["lines"] = head + rep["lines"]
+        if say is not None:
+            for ln in rep["lines"]:
+                say(ln)
+        return rep
+
+    def records(self):
+        """This rank's recorded games as a numpy structured array (RECORD_DTYPE) with `env` and `game` columns, env-major."""
+        E, G = self.num_envs, self.games_per_env
+        raw = self._records.cpu().numpy().view(RECORD_DTYPE).reshape(E, G)
+        games = self._b["games"].cpu().numpy()
+        env, game = np.nonzero(np.arange(G)[None, :] < games[:, None])
+        rec = raw[env, game]
+        out = np.zeros(len(rec), dtype=[(k, RECORD_DTYPE.fields[k][0]) for k in RECORD_DTYPE.names] + [("env", "<i4"), ("game", "<i4")])
+        for k in RECORD_DTYPE.names:
+            out[k] = rec[k]
+        out["env"], out["game"] = env, game
+        return out

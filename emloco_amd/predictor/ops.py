@@ -25,6 +25,19 @@ class LocoValStep(C.Structure):
                 ("staged_reward", C.c_void_p), ("staged_done", C.c_void_p)]          # staged mode (both NULL: off)
 
 
+class LocoValEval(C.Structure):
+    """EmlocoLocoValEval (include/emloco_predictor.h): the per-env game state of the LocoVal evaluation (`run.py --test`)."""
+    _fields_ = [("n_env", C.c_int32), ("step_to_pred", C.c_int32), ("games_per_env", C.c_int32), ("_pad", C.c_int32),
+                ("gamma", C.c_double), ("coef", C.c_void_p), ("c_disc", C.c_void_p), ("tp_disc", C.c_void_p),
+                ("cr", C.c_void_p), ("c_loc", C.c_void_p), ("c_pow", C.c_void_p), ("tp_cr", C.c_void_p), ("tp_loc", C.c_void_p),
+                ("tp_pow", C.c_void_p), ("steps", C.c_void_p), ("games", C.c_void_p), ("done", C.c_void_p), ("terminated", C.c_void_p),
+                ("inverted", C.c_void_p), ("n_full", C.c_void_p), ("waypoint_traj", C.c_void_p), ("init_pose", C.c_void_p),
+                ("init_vel", C.c_void_p), ("traj13", C.c_void_p), ("pose", C.c_void_p), ("vel", C.c_void_p), ("row_mask", C.c_void_p)]
+
+
+EVAL_MOMENTS = 20          # EMLOCO_EVAL_MOMENTS
+
+
 def _lib():
     global _bound
     lib = L.require_device()
@@ -68,6 +81,9 @@ def _lib():
         lib.emloco_locoval_returns_finish.argtypes = [C.POINTER(LocoValStep), vp, vp]
         lib.emloco_locoval_fit_grad.argtypes = [ci, vp, vp, vp, vp, vp, vp, vp]
         lib.emloco_locoval_bwd_rows.argtypes = [ci, vp, ci] + [vp] * 17
+        lib.emloco_locoval_eval_step.argtypes = [C.POINTER(LocoValEval), vp, vp, vp, vp, vp, vp]
+        lib.emloco_locoval_eval_finish.argtypes = [C.POINTER(LocoValEval), vp, vp, vp]
+        lib.emloco_locoval_eval_reduce.argtypes = [ci, ci, vp, vp, vp, vp]
         lib.emloco_adamw_gated.argtypes = [ci] + [vp] * 7 + [cf] * 5 + [vp, vp]
         lib.emloco_adam_clip_flat.argtypes = [C.c_int64] + [vp] * 4 + [cf, C.c_double, C.c_double] + [cf] * 5 + [vp, vp]
         lib.emloco_adam_clip_flat_counted.argtypes = [C.c_int64] + [vp] * 4 + [cf, C.c_double, C.c_double] + [cf] * 3 + [vp, vp, vp]

@@ -6,6 +6,12 @@
 rl_games (the PPO runner the reference plugs into, pacer/requirements.txt:26) is not vendored; this entry
 runs the LocoVal rollout loop of `learning/locoval_rollout.py` (AMPValueAgent.play_steps bookkeeping) with a
 frozen random-init policy, and prints the reference's `fps_step` counter (common_agent.py:187).
+
+    python -m emloco_amd.run --test --num_envs 4096 --policy_checkpoint policy.pth --valuenet_path LocoVal.pth \
+        [--games_num N] [--eval_out report.json] [--eval_records games.npz]
+
+is the reference's `pacer/run.py --test --valuenet_path ...` (AMPPlayerContinuousValue.run): the frozen policy plays
+deterministically and LocoVal is scored against the discounted returns of the games (`learning/locoval_eval.py`).
 """
 import random
 import sys
@@ -72,10 +78,36 @@ class RLGPUEnv:
         return self.env.get_number_of_agents()
 
 
+def _pop_opt(argv, name, default=None):
+    """Remove `name VALUE` from argv (an option get_args does not know) and return VALUE."""
+    if name in argv:
+        i = argv.index(name)
+        if i + 1 >= len(argv):
+            raise SystemExit(f"run.py: {name} needs a value")
+        v = argv[i + 1]
+        del argv[i:i + 2]
+        return v
+    return default
+
+
 def main(argv=None):
+    argv = list(sys.argv[1:] if argv is None else argv)
+    # --test (the reference's player, amp_value_players.py): its own options, checked before anything touches a device
+    games_num = _pop_opt(argv, "--games_num")
+    eval_out = _pop_opt(argv, "--eval_out")
+    eval_records = _pop_opt(argv, "--eval_records")
+    max_steps = _pop_opt(argv, "--max_steps")
+    if "--test" in argv:
+        vp = _pop_opt(list(argv), "--valuenet_path", "")
+        if not vp:
+            raise SystemExit("run.py --test: --valuenet_path <LocoVal.pth> is required (the LocoVal network to evaluate; "
+                             "pacer/run.py --test takes it the same way)")
+        if "--policy_checkpoint" not in argv and "--policy_random_init" not in argv:
+            raise SystemExit("run.py --test: give the policy to play, --policy_checkpoint <policy.pth> or --policy_random_init")
+        if "--train_policy" in argv:
+            raise SystemExit("run.py: --test and --train_policy exclude each other")
     from . import configure_runtime
     configure_runtime()                                  # entry point: 16 hardware queues, ahead of the first GPU call (emloco_amd/__init__.py)
-    argv = list(sys.argv[1:] if argv is None else argv)
     steps = 100
     if "--steps" in argv:
         i = argv.index("--steps")
@@ -111,6 +143,9 @@ def main(argv=None):
     fill_flags(args)
     env = RLGPUEnv(create_rlgpu_env(args, cfg, cfg_train, rank=rank))
     say = print if rank == 0 else (lambda *a, **k: None)
+    if args.test:
+        _run_test(args, env, policy_ckpt, games_num, max_steps, eval_out, eval_records, rank, world, say)
+        return
     if train_policy:
         import yaml
         from .learning.amp_agent import AMPAgent
@@ -142,6 +177,47 @@ def main(argv=None):
     dt = time.time() - t0
     say(f"fps_step: {env.env.num_envs * world * n / dt:,.0f} env-steps/s ({n} steps of {env.env.num_envs} envs x {world} ranks), "
         f"LocoVal loss {agent.vnet_loss:.4f}, {agent.fitted_episodes} episodes fitted")
+    if world > 1:
+        torch.distributed.destroy_process_group()
+
+
+def _run_test(args, env, policy_ckpt, games_num, max_steps, eval_out, eval_records, rank, world, say):
+    """--test: LocoValEvaluator with the frozen policy (deterministic actions) and the LocoVal network of --valuenet_path."""
+    import json
+    import yaml
+    from .learning.amp_policy import DEFAULT_CFG, AMPPolicyBundle
+    from .learning.locoval_eval import LocoValEvaluator
+    from .learning.value_pose_net import ValuePoseNet
+    cfg_train = yaml.safe_load(open(DEFAULT_CFG))
+    config = cfg_train["params"]["config"]
+    player = config.get("player", {})
+    task = env.env.task
+    bundle = AMPPolicyBundle(task, cfg_train=cfg_train, checkpoint=policy_ckpt, deterministic=bool(player.get("deterministic", True)))
+    valuenet = ValuePoseNet(use_pose=True, use_vel=True).to(task.device)
+    valuenet.load_state_dict(torch.load(args.valuenet_path, map_location=task.device))     # amp_value_players.py:301
+    valuenet.eval()
+    ev = LocoValEvaluator(env, bundle, valuenet, int(games_num) if games_num else int(player.get("games_num", 200)),
+                          max_steps=int(max_steps) if max_steps else 27000, gamma=float(config.get("gamma", 0.99)))
+    t0 = time.time()
+    rep = ev.run(say=say)
+    torch.cuda.synchronize()
+    rep["seconds"] = time.time() - t0
+    say(f"{rep['steps']} steps of {ev.envs_total} envs in {rep['seconds']:.2f} s")
+    recs = ev.records()
+    if eval_records:
+        # per-game records of every rank (what the reference draws as scatter plots): gathered on rank 0
+        parts = [recs]
+        if world > 1:
+            gathered = [None] * world
+            torch.distributed.all_gather_object(gathered, recs)
+            parts = gathered
+        if rank == 0:
+            cols = {k: np.concatenate([p[k] for p in parts]) for k in recs.dtype.names}
+            cols["rank"] = np.concatenate([np.full(len(p), r, np.int32) for r, p in enumerate(parts)])
+            np.savez(eval_records, **cols)
+    if eval_out and rank == 0:
+        with open(eval_out, "w") as f:
+            json.dump({k: v for k, v in rep.items()}, f, indent=1, default=float)
     if world > 1:
         torch.distributed.destroy_process_group()
 

@@ -316,6 +316,63 @@ int emloco_adamw_gated(int n, float *params, const float *grads, float *exp_avg,
                        float *steps_out, const float *tail2, float lr, float beta1, float beta2, float eps, float weight_decay,
                        double *stats, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * LocoVal evaluation (`run.py --test --valuenet_path ...`): the per-game bookkeeping of AMPPlayerContinuousValue.run
+ * (pacer/pacer/learning/amp_value_players.py:35-272, the plot_val_reward branch) for every env of a batch at once, in
+ * three launches per step around emloco_locoval_fwd_rows plus one reduction at the end (csrc/eval_kernels.hip):
+ *   emloco_locoval_eval_step    per step after env.step: the discount coefficient (:144, double), the discounted locomotion /
+ *                               power / style parts and their sum (:150-152; style in double), the step_to_pred capture
+ *                               (:177-184), and at the game's first step the LocoVal inputs in origin-relative form
+ *                               (:128-134, the helper of emloco_locoval_returns) with a 0/1 row mask for the forward
+ *   emloco_locoval_eval_finish  after the forward: for the envs whose game ended this step, the game record (:187-204: the
+ *                               prediction, the return up to step_to_pred and its parts, (G + 10) / 110 (:55-56,195), the
+ *                               squared error (:196), the return at the end, the length) into records[env][game] while the
+ *                               env's quota of games_per_env is not met; then the per-game state is reset
+ *   emloco_locoval_eval_reduce  one launch at the end: the moment vector of the recorded games, in double, in a fixed order
+ * One env = one game at a time, as the reference's single-env player; every env records exactly its first games_per_env games
+ * (no over-sampling of short games).  No atomics touch the records: the result is deterministic. */
+typedef struct {
+    int32_t n_env, step_to_pred;
+    int32_t games_per_env;          /* quota G of recorded games per env */
+    int32_t _pad;
+    double gamma;
+    double *coef;                   /* [n_env] gamma^(n+1) of the current game (:144; a Python float in the reference) */
+    double *c_disc;                 /* [n_env] discounted style reward (double, :143-149) */
+    double *tp_disc;                /* [n_env] its capture at n == step_to_pred */
+    float *cr, *c_loc, *c_pow;      /* [n_env] discounted total / locomotion / power reward (fp32, :150-152) */
+    float *tp_cr, *tp_loc, *tp_pow; /* [n_env] their captures at n == step_to_pred */
+    int32_t *steps;                 /* [n_env] steps of the current game */
+    int32_t *games;                 /* [n_env] games recorded so far (stops at games_per_env) */
+    uint8_t *done, *terminated, *inverted;   /* [n_env] this step's flags, for emloco_locoval_eval_finish */
+    int32_t *n_full;                /* [1] envs whose quota is met (the one counter the host polls) */
+    const float *waypoint_traj;     /* [n_env][15][3]  task.waypoint_traj */
+    const float *init_pose;         /* [n_env][24][3]  task.init_pose */
+    const float *init_vel;          /* [n_env][2]      task.init_vel */
+    float *traj13;                  /* out [n_env][13][3] */
+    float *pose;                    /* out [n_env][24][3] */
+    float *vel;                     /* out [n_env][2] */
+    float *row_mask;                /* out [n_env]: 1 where this step is a game's first (the rows emloco_locoval_fwd_rows evaluates) */
+} EmlocoLocoValEval;
+/* one game (48 bytes); the reference's lists: vals (:206), rewards (:208, UNnormalised), rewards_loc/pow/disc (:181-183,190-192),
+ * value_loss (:196), cur_rewards / cur_steps (:203-204) */
+typedef struct {
+    double disc_to_pred;
+    float value, cr_to_pred, loc_to_pred, pow_to_pred, norm, sq_err, cr_end;
+    int32_t steps, terminated, inverted;
+} EmlocoLocoValRecord;
+/* moments[EMLOCO_EVAL_MOMENTS] (double): [0] games, [1] sum v, [2] sum v^2, then for y in (total, loc, pow, disc) at [3 + 3 k]:
+ * sum y, sum y^2, sum v y; [15] sum sq_err, [16] sum cr_end, [17] sum steps, [18] games terminated early, [19] games on an
+ * inverted path.  v = value, total = cr_to_pred. */
+#define EMLOCO_EVAL_MOMENTS 20
+/* reward_raw [n_env][2] (locomotion, power: task.reward_raw); disc [n_env] or NULL = 0; dones / terminate (or NULL) int64 [n_env];
+ * inverted [n_env] or NULL */
+int emloco_locoval_eval_step(const EmlocoLocoValEval *s, const float *reward_raw, const float *disc, const int64_t *dones,
+                             const int64_t *terminate, const uint8_t *inverted, void *stream);
+/* value [n_env]: what emloco_locoval_fwd_rows wrote for the masked rows (kept between steps); records [n_env][games_per_env] */
+int emloco_locoval_eval_finish(const EmlocoLocoValEval *s, const float *value, EmlocoLocoValRecord *records, void *stream);
+int emloco_locoval_eval_reduce(int n_env, int games_per_env, const EmlocoLocoValRecord *records, const int32_t *games,
+                               double *moments, void *stream);
+
 /* torch.nn.utils.clip_grad_norm_(params, max_norm) + torch.optim.Adam.step() (train_jta.py:317-318,411; train_jrdb.py likewise) on ONE
  * flat fp32 buffer of n parameters with their gradients, first and second moments laid out alike -- three launches (block sums of
  * squares, the clip coefficient from them in a fixed order, the update) where the foreach implementations issue ~25.  The gradient is

@@ -1,0 +1,311 @@
+"""CPU: the LocoVal evaluation (`run.py --test`, emloco_amd/learning/locoval_eval.py) against the reference's own player.
+
+Fixture tests/golden/locoval_player.npz comes from running AMPPlayerContinuousValue.run (pacer/pacer/learning/amp_value_players.py)
+on scripted streams (tests/golden/gen_golden_player.py).  Here:
+  * `Restatement`, a plain-torch statement of the per-game arithmetic (test infrastructure; the product runs it as HIP kernels),
+    reproduces the reference's per-game lists exactly;
+  * `report_from_moments` prints the reference's summary lines character for character;
+  * the kernels of emloco_amd/csrc/eval_kernels.hip, compiled for the CPU through tests/emu/hip/, give the restatement's records
+    bit for bit, for many envs whose game boundaries are shifted against each other;
+  * `run.py --test` without a LocoVal checkpoint stops with a clear message.
+"""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FIXTURE = os.path.join(ROOT, "tests", "golden", "locoval_player.npz")
+
+
+def fixture():
+    return dict(np.load(FIXTURE))
+
+
+class Restatement:
+    """amp_value_players.py:116-204 for E envs that each play games one after another (one env = the reference's single env).
+    Dtypes as the reference's: `coef` and the style part are Python floats (double), cr and the locomotion / power parts fp32 tensors
+    to which Python scalars are added (cast to fp32)."""
+
+    def __init__(self, E, step_to_pred, gamma, games_per_env, device="cpu"):
+        self.E, self.stp, self.gamma, self.G, self.dev = E, int(step_to_pred), float(gamma), int(games_per_env), device
+        z32 = lambda: torch.zeros(E, dtype=torch.float32, device=device)
+        z64 = lambda: torch.zeros(E, dtype=torch.float64, device=device)
+        self.coef = torch.ones(E, dtype=torch.float64, device=device)
+        self.c_disc, self.tp_disc = z64(), z64()
+        self.cr, self.c_loc, self.c_pow, self.tp_cr, self.tp_loc, self.tp_pow, self.value = (z32() for _ in range(7))
+        self.steps = torch.zeros(E, dtype=torch.int64, device=device)
+        self.records = [[] for _ in range(E)]
+
+    def step(self, r_loc, r_pow, disc, dones, terminate, inverted, value_fn):
+        n = self.steps
+        self.coef = self.coef * self.gamma                                      # :144
+        c32 = self.coef.float()
+        d = torch.zeros(self.E, dtype=torch.float64, device=self.dev) if disc is None else disc.double()
+        self.c_disc = self.c_disc + (d * 0.25) * self.coef                      # :149
+        self.c_loc = self.c_loc + (r_loc * 0.5) * c32                           # :150
+        self.c_pow = self.c_pow + (r_pow * 0.5) * c32                           # :151
+        self.cr = self.cr + ((r_loc + r_pow) * 0.5 + (d * 0.25).float()) * c32  # :152
+        cap = n == self.stp                                                     # :177-184
+        self.tp_cr = torch.where(cap, self.cr, self.tp_cr)
+        self.tp_loc = torch.where(cap, self.c_loc, self.tp_loc)
+        self.tp_pow = torch.where(cap, self.c_pow, self.tp_pow)
+        self.tp_disc = torch.where(cap, self.c_disc, self.tp_disc)
+        first = n == 0
+        if bool(first.any()):                                                   # :128-134
+            self.value = torch.where(first, value_fn(first).float(), self.value)
+        self.steps = n + 1
+        done = dones != 0
+        for e in torch.nonzero(done).flatten().tolist():
+            if len(self.records[e]) >= self.G:
+                continue
+            at_end = int(self.steps[e]) - 1 < self.stp                          # :187-193
+            tp_cr = self.cr[e] if at_end else self.tp_cr[e]
+            # :195.  A true fp32 division, as the reference's CPU run that made the fixture divides: torch on a GPU divides a tensor by
+            # a Python scalar as a multiplication by the scalar's fp32 reciprocal (1 ulp apart for some returns), hence a tensor divisor
+            norm = (tp_cr - (-10)) / torch.tensor(100 - (-10), dtype=torch.float32, device=tp_cr.device)
+            v = self.value[e]
+            sq = torch.nn.functional.mse_loss(v, norm)                          # :196
+            self.records[e].append(dict(
+                disc_to_pred=float(self.c_disc[e] if at_end else self.tp_disc[e]), value=float(v), cr_to_pred=float(tp_cr),
+                loc_to_pred=float(self.c_loc[e] if at_end else self.tp_loc[e]), pow_to_pred=float(self.c_pow[e] if at_end else self.tp_pow[e]),
+                norm=float(norm), sq_err=float(sq), cr_end=float(self.cr[e]), steps=int(self.steps[e]),
+                terminated=int(terminate[e] != 0) if terminate is not None else 0, inverted=int(bool(inverted[e])) if inverted is not None else 0))
+        keep = ~done
+        self.coef = torch.where(keep, self.coef, torch.ones_like(self.coef))
+        for k in ("c_disc", "cr", "c_loc", "c_pow"):
+            setattr(self, k, torch.where(keep, getattr(self, k), torch.zeros_like(getattr(self, k))))
+        self.steps = torch.where(keep, self.steps, torch.zeros_like(self.steps))
+
+    def record_array(self):
+        from emloco_amd.learning.locoval_eval import RECORD_DTYPE
+        rows = [(e, g, r) for e in range(self.E) for g, r in enumerate(self.records[e])]
+        out = np.zeros(len(rows), dtype=[(k, RECORD_DTYPE.fields[k][0]) for k in RECORD_DTYPE.names] + [("env", "<i4"), ("game", "<i4")])
+        for i, (e, g, r) in enumerate(rows):
+            for k, v in r.items():
+                out[k][i] = v
+            out["env"][i], out["game"][i] = e, g
+        return out
+
+
+def shifted_script(fx, E):
+    """Every env replays the fixture's games, env e starting at game e mod K (cyclic): the game boundaries of the envs are shifted
+    against each other.  Returns [T, E] streams and, per env, the fixture game of each of its K games."""
+    lengths = [int(x) for x in fx["lengths"]]
+    K, T = len(lengths), int(sum(lengths))
+    starts = np.concatenate([[0], np.cumsum(lengths)[:-1]])
+    cols = {k: np.zeros((T, E), fx[k].dtype) for k in ("r_loc", "r_pow", "disc", "dones", "terminate")}
+    gid = np.zeros((T, E), np.int64)
+    order = np.zeros((E, K), np.int64)
+    for e in range(E):
+        t = 0
+        for j in range(K):
+            g = (e + j) % K
+            order[e, j] = g
+            sl = slice(int(starts[g]), int(starts[g]) + lengths[g])
+            for k in cols:
+                cols[k][t:t + lengths[g], e] = fx[k][sl]
+            gid[t:t + lengths[g], e] = g
+            t += lengths[g]
+    cols["inverted"] = fx["inverted"][gid]
+    cols["gid"] = gid
+    return cols, order
+
+
+def _fixture_record(fx, g):
+    return dict(value=fx["values"][g], cr_to_pred=fx["rewards"][g], loc_to_pred=fx["rewards_loc"][g], pow_to_pred=fx["rewards_pow"][g],
+                disc_to_pred=fx["rewards_disc"][g], sq_err=fx["value_loss"][g], cr_end=fx["cur_rewards"][g], steps=fx["cur_steps"][g])
+
+
+def assert_records_equal_fixture(rec, fx, order):
+    """Every record equals the fixture's game bit for bit (floats compared as the reference's fp32 / double values)."""
+    for i in range(len(rec)):
+        g = int(order[rec["env"][i], rec["game"][i]])
+        want = _fixture_record(fx, g)
+        for k, v in want.items():
+            got = rec[k][i]
+            if k in ("disc_to_pred", "steps"):
+                assert float(got) == float(v), (k, i, g, got, v)
+            else:
+                assert np.float32(got).tobytes() == np.float32(v).tobytes() and np.float64(np.float32(v)) == np.float64(v), (k, i, g, got, v)
+        assert rec["inverted"][i] == int(fx["inverted"][g])
+        end = int(np.cumsum(fx["lengths"])[g]) - 1
+        assert rec["terminated"][i] == int(fx["terminate"][end])
+
+
+def run_restatement(fx, E):
+    s, order = shifted_script(fx, E)
+    K = len(fx["lengths"])
+    R = Restatement(E, int(fx["step_to_pred"]), float(fx["gamma"]), K)
+    t_ = lambda a: torch.from_numpy(np.ascontiguousarray(a))
+    for t in range(s["r_loc"].shape[0]):
+        gid = t_(s["gid"][t])
+        R.step(t_(s["r_loc"][t]), t_(s["r_pow"][t]), t_(s["disc"][t]), t_(s["dones"][t]), t_(s["terminate"][t]), t_(s["inverted"][t]),
+               lambda first: t_(fx["values"])[gid])
+    return R, s, order
+
+
+# ------------------------------------------------------------------------------------------------------------ restatement vs fixture
+def test_restatement_reproduces_the_reference_player():
+    fx = fixture()
+    R, _, order = run_restatement(fx, 1)
+    rec = R.record_array()
+    K = len(fx["lengths"])
+    assert len(rec) == K
+    assert_records_equal_fixture(rec, fx, order)
+    # the lists as the reference keeps them
+    assert np.array_equal(rec["value"].astype(np.float64), fx["vals"])
+    assert np.array_equal(rec["cr_to_pred"].astype(np.float64), fx["rewards"])
+    assert np.array_equal(rec["disc_to_pred"], fx["rewards_disc"])
+    assert np.array_equal(rec["sq_err"].astype(np.float64), fx["value_loss"])
+    assert np.array_equal(rec["steps"].astype(np.float64), fx["cur_steps"])
+
+
+def test_fixture_covers_the_game_lengths_the_issue_names():
+    fx = fixture()
+    L, stp = [int(x) for x in fx["lengths"]], int(fx["step_to_pred"])
+    assert any(n < stp for n in L) and stp in L and stp + 1 in L and any(n > stp + 1 for n in L) and 168 in L
+    assert any(L[i] == L[i + 1] == 1 for i in range(len(L) - 1))         # back-to-back one-step games
+
+
+# ------------------------------------------------------------------------------------------------------------ the printed summary
+def _reference_lines(fx):
+    keys = ("av reward:", "av_loc:", "std_loc:", "Correlation:", " Total reward:", "Loc reward:", "Pow reward:", "Disc reward:")
+    return [str(ln) for ln in fx["printed"] if str(ln).startswith(keys)]
+
+
+def test_report_from_moments_prints_the_reference_lines():
+    from emloco_amd.learning.locoval_eval import moments_from_records, report_from_moments
+    fx = fixture()
+    R, _, _ = run_restatement(fx, 1)
+    rec = R.record_array()
+    rep = report_from_moments(moments_from_records(rec))
+    assert "\n".join(rep["lines"]).split("\n") == _reference_lines(fx)
+    assert rep["games"] == len(fx["lengths"])
+    v = fx["vals"]
+    for part, y in (("total", fx["rewards"]), ("loc", fx["rewards_loc"]), ("pow", fx["rewards_pow"]), ("disc", fx["rewards_disc"])):
+        assert abs(rep["corr_" + part] - np.corrcoef(v, y)[0, 1]) < 1e-12, part
+        assert abs(rep["std_" + part] - np.std(y)) < 1e-12, part
+        assert abs(rep["av_" + part] - np.mean(y)) < 1e-12, part
+    assert abs(rep["av_value_loss"] - float(fx["total_value_loss"]) / len(v)) < 1e-12
+    assert abs(rep["av_reward"] - float(fx["sum_rewards"]) / len(v)) < 1e-12
+    assert rep["terminated"] == int(sum(fx["terminate"][np.cumsum(fx["lengths"]) - 1]))
+    assert rep["inverted"] == int(fx["inverted"].sum())
+
+
+def test_report_of_no_games_and_of_constant_values():
+    from emloco_amd.learning.locoval_eval import report_from_moments
+    assert report_from_moments(np.zeros(20))["games"] == 0
+    m = np.zeros(20)
+    m[0], m[1], m[2] = 4, 2.0, 1.0             # four games, every prediction 0.5: zero variance -> NaN correlation (numpy's answer)
+    m[3], m[4], m[5] = 10.0, 30.0, 5.0
+    rep = report_from_moments(m)
+    assert np.isnan(rep["corr_total"]) and rep["lines"][3].endswith("nan")
+
+
+# ------------------------------------------------------------------------------------------------------------ the kernels, emulated
+@pytest.fixture(scope="module")
+def emu(tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("emu_eval") / "libemu_eval.so")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-x", "c++", "-ffp-contract=off", "-DEMLOCO_EMU", "-Wno-psabi",
+                           "-I", os.path.join(ROOT, "tests", "emu"), "-o", so, os.path.join(ROOT, "tests", "emu_locoval_eval.cpp"),
+                           os.path.join(ROOT, "tests", "emu", "emu_runtime.cpp"), "-lpthread"], timeout=300)
+    lib = C.CDLL(so)
+    assert lib.emu_locoval_record_size() == 48
+    return lib
+
+
+def _ptr(a):
+    return C.c_void_p(a.ctypes.data) if a is not None else None
+
+
+def test_emulated_kernels_equal_the_restatement_bit_for_bit(emu):
+    from emloco_amd.predictor.ops import LocoValEval
+    from emloco_amd.learning.locoval_eval import RECORD_DTYPE, RECORD_WORDS, moments_from_records
+    fx = fixture()
+    E, K = 67, len(fx["lengths"])
+    R, s, order = run_restatement(fx, E)
+    want = R.record_array()
+    rng = np.random.default_rng(3)
+    wp = rng.standard_normal((E, 15, 3)).astype(np.float32)
+    ip = rng.standard_normal((E, 24, 3)).astype(np.float32)
+    iv = rng.standard_normal((E, 2)).astype(np.float32)
+    b = dict(coef=np.ones(E), c_disc=np.zeros(E), tp_disc=np.zeros(E), **{k: np.zeros(E, np.float32) for k in
+             ("cr", "c_loc", "c_pow", "tp_cr", "tp_loc", "tp_pow", "row_mask")}, steps=np.zeros(E, np.int32), games=np.zeros(E, np.int32),
+             done=np.zeros(E, np.uint8), terminated=np.zeros(E, np.uint8), inverted=np.zeros(E, np.uint8), n_full=np.zeros(1, np.int32),
+             traj13=np.zeros((E, 13, 3), np.float32), pose=np.zeros((E, 24, 3), np.float32), vel=np.zeros((E, 2), np.float32))
+    st = LocoValEval(E, int(fx["step_to_pred"]), K, 0, float(fx["gamma"]), *[b[k].ctypes.data for k in (
+        "coef", "c_disc", "tp_disc", "cr", "c_loc", "c_pow", "tp_cr", "tp_loc", "tp_pow", "steps", "games", "done", "terminated",
+        "inverted", "n_full")], wp.ctypes.data, ip.ctypes.data, iv.ctypes.data, b["traj13"].ctypes.data, b["pose"].ctypes.data,
+        b["vel"].ctypes.data, b["row_mask"].ctypes.data)
+    value = np.zeros(E, np.float32)
+    records = np.zeros(E * K * RECORD_WORDS, np.int32)
+    T = s["r_loc"].shape[0]
+    for t in range(T):
+        rr = np.ascontiguousarray(np.stack([s["r_loc"][t], s["r_pow"][t]], axis=1))
+        disc, dones, term = [np.ascontiguousarray(s[k][t]) for k in ("disc", "dones", "terminate")]
+        inv = np.ascontiguousarray(s["inverted"][t].astype(np.uint8))
+        assert emu.emu_locoval_eval_step(C.byref(st), _ptr(rr), _ptr(disc), _ptr(dones), _ptr(term), _ptr(inv)) == 0
+        first = b["row_mask"] != 0
+        if first.any():                                           # the LocoVal inputs of the game's first step, origin-relative
+            assert np.array_equal(b["traj13"][first], (wp[:, :13] - wp[:, :1])[first])
+            assert np.array_equal(b["pose"][first], (ip - ip[:, :1])[first])
+            assert np.array_equal(b["vel"][first], iv[first])
+        value[first] = fx["values"][s["gid"][t]][first]          # stands where emloco_locoval_fwd_rows writes the masked rows
+        assert emu.emu_locoval_eval_finish(C.byref(st), _ptr(value), _ptr(records)) == 0
+    assert np.array_equal(b["games"], np.full(E, K)) and int(b["n_full"][0]) == E
+    raw = records.view(RECORD_DTYPE).reshape(E, K)
+    got = raw[want["env"], want["game"]]
+    for k in RECORD_DTYPE.names:
+        assert got[k].tobytes() == want[k].tobytes(), k
+    assert_records_equal_fixture(want, fx, order)
+    mom = np.zeros(20)
+    assert emu.emu_locoval_eval_reduce(E, K, _ptr(records), _ptr(b["games"]), _ptr(mom)) == 0
+    ref = moments_from_records(want)
+    np.testing.assert_allclose(mom, ref, rtol=1e-12, atol=0)
+
+
+def test_quota_records_only_the_first_games_of_each_env(emu):
+    """G = 2: an env records its first two games and nothing after them (no over-sampling of short games)."""
+    from emloco_amd.predictor.ops import LocoValEval
+    from emloco_amd.learning.locoval_eval import RECORD_DTYPE, RECORD_WORDS
+    E, G, T = 3, 2, 12
+    dones = np.zeros((T, E), np.int64)
+    for e, ends in enumerate([[0, 1, 2, 3, 4], [5, 11], [11]]):      # env 0: five one-step games, env 1: two games, env 2: one
+        dones[ends, e] = 1
+    b = dict(coef=np.ones(E), c_disc=np.zeros(E), tp_disc=np.zeros(E), **{k: np.zeros(E, np.float32) for k in
+             ("cr", "c_loc", "c_pow", "tp_cr", "tp_loc", "tp_pow", "row_mask")}, steps=np.zeros(E, np.int32), games=np.zeros(E, np.int32),
+             done=np.zeros(E, np.uint8), terminated=np.zeros(E, np.uint8), inverted=np.zeros(E, np.uint8), n_full=np.zeros(1, np.int32))
+    io = [np.zeros(s, np.float32) for s in ((E, 15, 3), (E, 24, 3), (E, 2), (E, 13, 3), (E, 24, 3), (E, 2))]
+    st = LocoValEval(E, 144, G, 0, 0.99, *[b[k].ctypes.data for k in (
+        "coef", "c_disc", "tp_disc", "cr", "c_loc", "c_pow", "tp_cr", "tp_loc", "tp_pow", "steps", "games", "done", "terminated",
+        "inverted", "n_full")], *[a.ctypes.data for a in io], b["row_mask"].ctypes.data)
+    records = np.zeros(E * G * RECORD_WORDS, np.int32)
+    value = np.zeros(E, np.float32)
+    rr = np.ones((E, 2), np.float32)
+    for t in range(T):
+        emu.emu_locoval_eval_step(C.byref(st), _ptr(rr), None, _ptr(np.ascontiguousarray(dones[t])), None, None)
+        emu.emu_locoval_eval_finish(C.byref(st), _ptr(value), _ptr(records))
+    assert list(b["games"]) == [2, 2, 1] and int(b["n_full"][0]) == 2
+    raw = records.view(RECORD_DTYPE).reshape(E, G)
+    assert list(raw["steps"][0]) == [1, 1] and list(raw["steps"][1]) == [6, 6] and raw["steps"][2, 0] == 12
+
+
+# ------------------------------------------------------------------------------------------------------------ the command line
+def test_run_test_without_valuenet_path_fails_with_a_clear_message():
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    p = subprocess.run([sys.executable, "-m", "emloco_amd.run", "--test", "--num_envs", "4", "--policy_random_init"], cwd=ROOT, env=env,
+                       capture_output=True, text=True, timeout=300)
+    assert p.returncode != 0
+    assert "--valuenet_path" in p.stderr and "required" in p.stderr, p.stderr
+
+
+def test_shipped_config_has_the_player_section():
+    import yaml
+    from emloco_amd.learning.amp_policy import DEFAULT_CFG
+    player = yaml.safe_load(open(DEFAULT_CFG))["params"]["config"]["player"]
+    assert player["games_num"] == 200 and player["deterministic"] is True
