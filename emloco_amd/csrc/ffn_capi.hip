@@ -59,8 +59,9 @@ int64_t emloco_ffn_bwd_colsum_rows(int M) { return ((int64_t)M + FFN_ROWS - 1) /
 
 int emloco_ffn_bwd_input_colsum(int M, int F, const float *dz2, const uint16_t *w2t_bf16, const uint16_t *w1t_bf16, const uint32_t *mask,
                                 uint16_t *dz1, float *dx, float drop_p, float *colpart, void *stream) {
-    if (M < 1 || F < FFN_CH || F % FFN_CH || !dz2 || !w2t_bf16 || !w1t_bf16 || !mask || !dz1 || !dx || !(drop_p >= 0.0f && drop_p < 1.0f))
-        return ffail(-1, "emloco_ffn_bwd_input: bad argument (hidden width must be a multiple of 64, 0 <= drop_p < 1)");
+    // (F <= 2048 as the forward: the mask this pass reads only ever comes from emloco_ffn_fwd*, which holds b1 in a 2048-float LDS array)
+    if (M < 1 || F < FFN_CH || F % FFN_CH || F > 2048 || !dz2 || !w2t_bf16 || !w1t_bf16 || !mask || !dz1 || !dx || !(drop_p >= 0.0f && drop_p < 1.0f))
+        return ffail(-1, "emloco_ffn_bwd_input: bad argument (hidden width must be a multiple of 64, at most 2048; 0 <= drop_p < 1)");
     if (!aligned16(dz2) || !aligned16(w2t_bf16) || !aligned16(w1t_bf16) || !aligned16(mask) || !aligned16(dz1) || !aligned16(dx))
         return ffail(-1, "emloco_ffn_bwd_input: operands must be 16-byte aligned");
     emloco::FfnArgs a{M, F, dz2, w2t_bf16, w1t_bf16, nullptr, nullptr, nullptr, dz1, const_cast<uint32_t *>(mask), dx, drop_p, 1.0f / (1.0f - drop_p), 0u, 0u, 0u, colpart};

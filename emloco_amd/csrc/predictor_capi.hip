@@ -319,9 +319,7 @@ int emloco_gather_flat(int n, const float *const *src, const int64_t *numel, con
             if (a.numel[i] > big) big = a.numel[i];
         }
         a.flat = flat;
-        long gx = (big / 4 + 255) / 256;                       // workgroups along the largest tensor: one 16-byte copy per thread, at most 64
-        gx = gx < 1 ? 1 : (gx > 64 ? 64 : gx);
-        hipLaunchKernelGGL(emloco::gather_flat_kernel, dim3((unsigned)gx, (unsigned)m), dim3(256), 0, (hipStream_t)stream, a);
+        hipLaunchKernelGGL(emloco::gather_flat_kernel, dim3(emloco::gather_flat_grid_x(big), (unsigned)m), dim3(256), 0, (hipStream_t)stream, a);
         PHIPCHK(hipGetLastError());
     }
     return 0;
@@ -339,7 +337,7 @@ int emloco_obs_normalize(int rows, int cols, const float *x, int ldx, const floa
     if (rows < 1 || cols < 1 || !x || !mean || !var || !out0 || split < 0 || split > cols || (split < cols && !out1) ||
         ldx < cols || ld0 < split || (split < cols && ld1 < cols - split))
         return pfail(-1, "emloco_obs_normalize: bad argument");
-    hipLaunchKernelGGL(emloco::obs_normalize_kernel, dim3((unsigned)((cols + 255) / 256), (unsigned)rows), dim3(256), 0,
+    hipLaunchKernelGGL(emloco::obs_normalize_kernel, dim3((unsigned)((cols + 255) / 256), (unsigned)(rows < OBS_MAX_GRID_Y ? rows : OBS_MAX_GRID_Y)), dim3(256), 0,
                        (hipStream_t)stream, rows, cols, x, ldx, mean, var, eps, clip, split, out0, ld0, out1 ? out1 : out0, ld1);
     PHIPCHK(hipGetLastError());
     return 0;

@@ -1213,6 +1213,11 @@ act_bwd_colsum_kernel(int m, int n, const float *dy, const float *y, int relu, f
 // flat[off[t] ..] = src[t][..] for the tensors of one table (blockIdx.y = tensor); 16-byte copies where both ends are aligned
 #define GATHER_MAX 96
 struct GatherArgs { const float *src[GATHER_MAX]; long numel[GATHER_MAX]; long off[GATHER_MAX]; float *flat; };
+// workgroups along the largest tensor of a table: one 16-byte copy per thread, at most 64 (the kernel strides over the rest)
+inline unsigned gather_flat_grid_x(long big) {
+    const long gx = (big / 4 + 255) / 256;
+    return (unsigned)(gx < 1 ? 1 : (gx > 64 ? 64 : gx));
+}
 __global__ void __launch_bounds__(256)
 gather_flat_kernel(GatherArgs a) {
     const int t = blockIdx.y;
@@ -1232,15 +1237,17 @@ gather_flat_kernel(GatherArgs a) {
 // Columns [0, split) go to out0 (leading dimension ld0), columns [split, cols) to out1 (ld1): the policy wants the
 // self observation in the first 368 columns of the actor-MLP input and the task observation as a separate,
 // 16-byte-aligned GEMM operand, so the split costs nothing here and saves a torch.cat and two copies.
+#define OBS_MAX_GRID_Y 65535
 __global__ void __launch_bounds__(256)
 obs_normalize_kernel(int rows, int cols, const float *x, int ldx, const float *mean, const float *var, float eps, float clip,
                      int split, float *out0, int ld0, float *out1, int ld1) {
-    const long row = blockIdx.y;
-    for (int j = blockIdx.x * 256 + threadIdx.x; j < cols; j += gridDim.x * 256) {
-        float y = (x[row * ldx + j] - mean[j]) / sqrtf(var[j] + eps);
-        y = fminf(fmaxf(y, -clip), clip);
-        if (j < split) out0[row * ld0 + j] = y; else out1[row * ld1 + (j - split)] = y;
-    }
+    // (blockIdx.y strides over the rows: the launcher caps grid.y at OBS_MAX_GRID_Y, the most a launch takes)
+    for (long row = blockIdx.y; row < rows; row += gridDim.y)
+        for (int j = blockIdx.x * 256 + threadIdx.x; j < cols; j += gridDim.x * 256) {
+            float y = (x[row * ldx + j] - mean[j]) / sqrtf(var[j] + eps);
+            y = fminf(fmaxf(y, -clip), clip);
+            if (j < split) out0[row * ld0 + j] = y; else out1[row * ld1 + (j - split)] = y;
+        }
 }
 
 // The AMP style reward of a step from the discriminator's logits (amp_continuous.py:675-692):

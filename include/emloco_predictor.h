@@ -86,7 +86,7 @@ int emloco_gemm_relu_bwd(int m, int n, int k, const float *A, int lda, const flo
  * relu, dropout p) as two CHAINED matrix products per launch -- the reduced-precision mode's path (bf16 operands into
  * v_mfma_f32_32x32x16_bf16, fp32 accumulation): the hidden tile goes from the product that makes it to the product that consumes it in
  * registers; it is also stored, as bf16, for the two weight-gradient products (ordinary GEMMs with a bf16 operand).  Model width 128,
- * F a multiple of 64; every pointer 16-byte aligned; weights are bf16 copies the caller makes per call (2 x 256 KB at F = 1024).
+ * F a multiple of 64, 64 <= F <= 2048 (all four entry points refuse anything else and write nothing); every pointer 16-byte aligned; weights are bf16 copies the caller makes per call (2 x 256 KB at F = 1024).
  *   emloco_ffn_fwd        hidden[M][F] = dropout(relu(x w1^T + b1)) (bf16), out[M][128] = dropout(hidden w2^T + b2) (fp32), mask[M][F / 32]:
  *                         one BIT per hidden unit, "active and kept" (word (row, 64-unit chunk c, h) at [row][2 c + h], bit 16 t + 4 q + e =
  *                         unit 64 c + 32 t + 8 q + 4 h + e: the units one lane of the kernel holds) -- all the input-gradient pass reads of the
@@ -198,7 +198,8 @@ int emloco_layernorm_fwd(int rows, int d, float eps, const float *x, const float
 int emloco_layernorm_fwd_save(int rows, int d, float eps, const float *x, const float *res, const float *gamma,
                               const float *beta, float *y, float *mean, float *rstd, float *xr, void *stream);
 /* dxr = dL/d(x+res); dgamma/dbeta are reduced over rows in a fixed order.  xr = x + res (the fwd input sum)
- * is recomputed from y:  xhat = (y - beta) / gamma is avoided -- pass the saved sum `xr`. */
+ * is recomputed from y:  xhat = (y - beta) / gamma is avoided -- pass the saved sum `xr`.  d <= 1024 as the forward
+ * (emloco_layernorm_fwd / _fwd_save / _bwd / _bwd2 all return non-zero for d > 1024 and write nothing). */
 int emloco_layernorm_bwd(int rows, int d, const float *xr, const float *gamma, const float *mean, const float *rstd,
                          const float *dy, float *dxr, float *dgamma, float *dbeta, float *workspace, void *stream);
 /* the same with TWO incoming gradients, added on load (dy2 may be NULL): a post-norm layer's output feeds the next sublayer AND its
@@ -218,6 +219,7 @@ int64_t emloco_colsum_workspace(int m, int n);   /* floats */
  * pacer/pacer/utils/running_mean_std.py:81-83:  y = clamp((x - mean) / sqrt(var + eps), -clip, clip), clip = 5.
  * x [rows][ldx]; mean / var are the float32 casts of the float64 running buffers.  Columns [0, split) are written to
  * out0 (leading dimension ld0), columns [split, cols) to out1 (ld1); split == cols writes everything to out0.
+ * Any rows >= 1: the launch covers at most 65 535 rows at a time and strides over the rest.
  * The MLPs themselves (amp_network_sept_builder.py:50-110: task MLP 1054->512->256, actor MLP 624->2048->1024->69)
  * run on emloco_gemm_f32 with the bias + ReLU epilogue. */
 /* AMP style reward from the discriminator's logits [n] (pacer/pacer/learning/amp_continuous.py:675-692 `_calc_disc_rewards`):

@@ -76,14 +76,46 @@ extern "C" int emu_gemm_relu_bwd_ex(int m, int n, int k, const float *A, int lda
     return 0;
 }
 
-extern "C" int emu_obs_normalize(int rows, int cols, const float *x, int ldx, const float *mean, const float *var, float eps,
-                                 float clip, int split, float *out0, int ld0, float *out1, int ld1) {
-    for (int r = 0; r < rows; ++r)
+// grid_y = 0: as emloco_obs_normalize launches it (min(rows, OBS_MAX_GRID_Y)); > 0: a smaller grid, to walk the row stride at small sizes
+extern "C" int emu_obs_normalize_grid(int rows, int cols, const float *x, int ldx, const float *mean, const float *var, float eps,
+                                      float clip, int split, float *out0, int ld0, float *out1, int ld1, int grid_y) {
+    const int gy = grid_y > 0 ? grid_y : (rows < OBS_MAX_GRID_Y ? rows : OBS_MAX_GRID_Y);
+    for (int r = 0; r < gy; ++r)
         emu::launch((unsigned)((cols + 255) / 256), 256, [&] {
-            blockIdx.y = r; gridDim.x = (cols + 255) / 256;
+            blockIdx.y = r; gridDim.x = (cols + 255) / 256; gridDim.y = gy;
             obs_normalize_kernel(rows, cols, x, ldx, mean, var, eps, clip, split, out0, ld0, out1, ld1);
         });
-    blockIdx.y = 0;
+    blockIdx.y = 0; gridDim.y = 1;
+    return 0;
+}
+extern "C" int emu_obs_normalize(int rows, int cols, const float *x, int ldx, const float *mean, const float *var, float eps,
+                                 float clip, int split, float *out0, int ld0, float *out1, int ld1) {
+    return emu_obs_normalize_grid(rows, cols, x, ldx, mean, var, eps, clip, split, out0, ld0, out1, ld1, 0);
+}
+// emloco_gather_flat as the C entry point launches it: one launch per GATHER_MAX tensors, grid.x from the launcher's own gather_flat_grid_x
+extern "C" int emu_gather_flat(int n, const float *const *src, const long *numel, const long *dst_offset, float *flat) {
+    for (int i0 = 0; i0 < n; i0 += GATHER_MAX) {
+        GatherArgs a;
+        const int m = n - i0 < GATHER_MAX ? n - i0 : GATHER_MAX;
+        long big = 0;
+        for (int i = 0; i < m; ++i) {
+            a.src[i] = src[i0 + i]; a.numel[i] = numel[i0 + i]; a.off[i] = dst_offset[i0 + i];
+            if (a.numel[i] > big) big = a.numel[i];
+        }
+        a.flat = flat;
+        const unsigned gx = gather_flat_grid_x(big);
+        for (int t = 0; t < m; ++t)
+            emu::launch(gx, 256, [&] { blockIdx.y = t; gridDim.y = m; gather_flat_kernel(a); });
+        blockIdx.y = 0; gridDim.y = 1;
+    }
+    return 0;
+}
+extern "C" int emu_act_bwd(long total, const float *dy, const float *y, int relu, float drop_p, unsigned drop_seed, float *dz) {
+    emu::launch((unsigned)((total + 255) / 256), 256, [&] { act_bwd_kernel(total, dy, y, relu, drop_p, drop_seed, dz); });
+    return 0;
+}
+extern "C" int emu_disc_reward(int n, const float *logits, float scale, float *reward) {
+    emu::launch((unsigned)((n + 255) / 256), 256, [&] { disc_reward_kernel(n, logits, scale, reward); });
     return 0;
 }
 extern "C" int emu_rms_update(int rows, int cols, const float *x, int ldx, double *mean, double *var, const double *count_in, double *count_out,

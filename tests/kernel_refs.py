@@ -1,0 +1,499 @@
+"""Plain references of the normalisation, loss-head and optimiser kernels of include/emloco_predictor.h.
+
+Every function restates one operation of the header from its documented contract and the reference project's formulas, never from a
+kernel: closed forms in torch, evaluated in the dtype given (float64 by default).  tests/test_kernel_refs_cpu.py pins each of them
+against torch autograd / torch.optim / torch.nn.functional of the textbook expression; tests/test_gpu_elementwise_matrix.py compares
+the device kernels with them.  Calling one with dtype=torch.float32 evaluates the same operation with stock float32 torch on the CPU:
+its distance to the float64 result is the "float32-reference error" the device bars are derived from.
+
+No kernel, no library, no GPU is needed to import or run this module.
+"""
+import math
+
+import torch
+
+F64 = torch.float64
+HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
+LV_HIDDEN_JOINTS = (4, 8, 9, 10, 11)        # value_pose_net.py:141-144: joints zeroed in the MLP input
+LV_SIZES = (4900, 49, 1176, 24, 24, 1)      # dparams layout of emloco_locoval_bwd: dw1 | db1 | dw2 | db2 | dw3 | db3
+
+
+def _c(t, dtype):
+    return None if t is None else torch.as_tensor(t).detach().to("cpu").to(dtype)
+
+
+def bf16_round(x):
+    """round-to-nearest-even to bf16, back as float64"""
+    return torch.as_tensor(x).float().to(torch.bfloat16).double()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# LayerNorm (post-norm encoder layer: y = LayerNorm(x + res) gamma + beta, biased variance)
+
+def layernorm_fwd(x, res, gamma, beta, eps, dtype=F64):
+    """-> y, mean [rows], rstd [rows], xr = x + res"""
+    x, res, gamma, beta = _c(x, dtype), _c(res, dtype), _c(gamma, dtype), _c(beta, dtype)
+    xr = x if res is None else x + res
+    mean = xr.mean(dim=-1)
+    c = xr - mean[:, None]
+    rstd = 1.0 / torch.sqrt((c * c).mean(dim=-1) + eps)
+    return c * rstd[:, None] * gamma + beta, mean, rstd, xr
+
+
+def layernorm_bwd(xr, gamma, mean, rstd, dy, dy2=None, dtype=F64):
+    """-> dxr, dgamma, dbeta for the incoming gradient dy (+ dy2); mean / rstd as the forward saved them"""
+    xr, gamma, mean, rstd, dy, dy2 = (_c(t, dtype) for t in (xr, gamma, mean, rstd, dy, dy2))
+    if dy2 is not None:
+        dy = dy + dy2
+    xh = (xr - mean[:, None]) * rstd[:, None]
+    g = dy * gamma
+    dxr = rstd[:, None] * (g - g.mean(dim=-1, keepdim=True) - xh * (g * xh).mean(dim=-1, keepdim=True))
+    return dxr, (dy * xh).sum(dim=0), dy.sum(dim=0)
+
+
+def layernorm_bwd_terms(xr, gamma, mean, rstd, dy, dy2=None):
+    """sum |terms| of the dgamma / dbeta reductions (the scale of a fixed-order fp32 sum's error)"""
+    xr, gamma, mean, rstd, dy, dy2 = (_c(t, F64) for t in (xr, gamma, mean, rstd, dy, dy2))
+    if dy2 is not None:
+        dy = dy + dy2
+    xh = (xr - mean[:, None]) * rstd[:, None]
+    return (dy * xh).abs().sum(dim=0), dy.abs().sum(dim=0)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# softmax over attention scores with an additive per-key bias
+
+def softmax_fwd(S, scale, key_bias=None, rows_per_seq=1, dtype=F64):
+    """S [rows][cols]; key_bias [n_seq][cols] or None; a row whose keys are all -inf gives zeros"""
+    S, key_bias = _c(S, dtype), _c(key_bias, dtype)
+    z = S * scale
+    if key_bias is not None:
+        z = z + key_bias.repeat_interleave(rows_per_seq, dim=0)
+    dead = torch.isneginf(z).all(dim=-1, keepdim=True)
+    p = torch.softmax(torch.where(dead, torch.zeros_like(z), z), dim=-1)
+    return torch.where(dead, torch.zeros_like(p), p)
+
+
+def softmax_bwd(P, dP, scale, dtype=F64):
+    P, dP = _c(P, dtype), _c(dP, dtype)
+    return scale * P * (dP - (dP * P).sum(dim=-1, keepdim=True))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# epilogue backward, column sums
+
+def act_bwd(dy, y, relu, keep, p, dtype=F64):
+    """dz = dy [relu: y > 0] [dropout: keep / (1 - p)]; with ReLU a positive forward output already means "active and kept" """
+    dy, y = _c(dy, dtype), _c(y, dtype)
+    v = dy
+    if relu:
+        v = torch.where(y > 0, v, torch.zeros_like(v))
+    if p > 0:
+        inv = torch.tensor(1.0, dtype=torch.float32) / (torch.tensor(1.0, dtype=torch.float32) - torch.tensor(p, dtype=torch.float32))
+        v = v * inv.to(dtype)                     # the documented scale is the float32 value 1 / (1 - p)
+        if not relu:
+            v = v * _c(keep, dtype)
+    return v
+
+
+def colsum(X, dtype=F64):
+    return _c(X, dtype).sum(dim=0)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# policy-input normaliser, AMP style reward, running moments
+
+def obs_normalize(x, mean, var, eps, clip, dtype=F64):
+    x, mean, var = _c(x, dtype), _c(mean, dtype), _c(var, dtype)
+    return torch.clamp((x - mean) / torch.sqrt(var + eps), -clip, clip)
+
+
+def disc_reward(logits, scale, dtype=F64):
+    """-log(max(1 - sigmoid(logit), 1e-4)) * scale"""
+    x = _c(logits, dtype)
+    prob = 1.0 / (1.0 + torch.exp(-x))
+    return -torch.log(torch.clamp_min(1.0 - prob, 0.0001)) * scale
+
+
+def disc_one_minus_sigmoid(logits):
+    return 1.0 - 1.0 / (1.0 + torch.exp(-_c(logits, F64)))
+
+
+def rms_update(x, mean, var, count, first_col=0):
+    """RunningMeanStd.forward in training mode: the batch's mean and UNBIASED variance merged with the parallel-variance rule;
+    columns below first_col keep their moments.  float64 throughout.  -> mean, var, count"""
+    x, mean, var = _c(x, F64), _c(mean, F64).clone(), _c(var, F64).clone()
+    n = x.shape[0]
+    bm = x.mean(dim=0)
+    bv = ((x - bm) ** 2).sum(dim=0) / (n - 1.0) if n > 1 else torch.full_like(bm, float("nan"))
+    d = bm - mean
+    tot = count + n
+    new_mean = mean + d * n / tot
+    new_var = (var * count + bv * n + d * d * count * n / tot) / tot
+    mean[first_col:] = new_mean[first_col:]
+    var[first_col:] = new_var[first_col:]
+    return mean, var, tot
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# chained feed-forward block on bf16 operands (the hidden layer and dz1 are stored as bf16 once)
+
+def ffn_fwd(x, w1, b1, w2, b2, keep_h=None, keep_o=None, p=0.0, rounded=True):
+    """x [M][128], w1 [F][128], w2 [128][F]; keep_h [M][F], keep_o [M][128] 0/1 or None.
+    -> hidden (as stored: bf16-rounded), active-and-kept mask [M][F] (bool), out [M][128], the pre-activation z1 (for branch distances)"""
+    r = bf16_round if rounded else (lambda t: _c(t, F64))
+    x, w1, w2, b1, b2 = r(x), r(w1), r(w2), _c(b1, F64), _c(b2, F64)
+    inv = float(torch.tensor(1.0, dtype=torch.float32) / (torch.tensor(1.0, dtype=torch.float32) - torch.tensor(p, dtype=torch.float32)))
+    z1 = x @ w1.T + b1
+    h = z1.clamp_min(0.0)
+    active = z1 > 0
+    if p > 0:
+        h = h * _c(keep_h, F64) * inv
+        active = active & (_c(keep_h, F64) > 0)
+    hidden = bf16_round(h) if rounded else h
+    out = hidden @ w2.T + b2
+    if p > 0:
+        out = out * _c(keep_o, F64) * inv
+    return hidden, active, out, z1
+
+
+def ffn_bwd_input(dz2, w1, w2, active, p=0.0, rounded=True):
+    """dz1 = (dz2 w2) o active / (1 - p) (stored bf16), dx = dz1 w1"""
+    r = bf16_round if rounded else (lambda t: _c(t, F64))
+    inv = float(torch.tensor(1.0, dtype=torch.float32) / (torch.tensor(1.0, dtype=torch.float32) - torch.tensor(p, dtype=torch.float32)))
+    dz1 = (r(dz2) @ r(w2)) * _c(active, F64) * inv
+    dz1 = bf16_round(dz1) if rounded else dz1
+    return dz1, dz1 @ r(w1)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# LocoVal MLP with yaw normalisation (value_pose_net.py:36-159)
+
+def locoval_input(traj, pose, vel):
+    """traj [B][13][>=2], pose [B][24][3], vel [B][2] -> x100 [B][100], angle [B] (differentiable in traj)"""
+    x1, y1 = traj[:, 1, 0], traj[:, 1, 1]
+    x1 = torch.where(x1.abs() < 1e-10, torch.full_like(x1, 1e-10), x1)         # epsilon guard on x (:79-83): a constant, no gradient
+    ang = torch.atan2(y1, x1)
+    c, s = torch.cos(ang)[:, None], torch.sin(ang)[:, None]
+
+    def rot(px, py):
+        return px * c + py * s, -px * s + py * c
+    tx, ty = rot(traj[:, :, 0], traj[:, :, 1])
+    px, py = rot(pose[:, :, 0], pose[:, :, 1])
+    vx, vy = rot(vel[:, 0:1], vel[:, 1:2])
+    live = torch.ones(24, dtype=traj.dtype)
+    live[list(LV_HIDDEN_JOINTS)] = 0.0
+    p3 = torch.stack([px, py, pose[:, :, 2]], dim=-1) * live[None, :, None]
+    x100 = torch.cat([torch.stack([tx, ty], dim=-1).reshape(-1, 26), p3.reshape(-1, 72), vx, vy], dim=1)
+    return x100, ang
+
+
+def locoval_fwd(traj, pose, vel, params, dtype=F64):
+    """params = (w1 [49][100], b1, w2 [24][49], b2, w3 [24], b3 [1]) -> value [B], x100, h1, h2, angle"""
+    traj, pose, vel = _c(traj, dtype), _c(pose, dtype), _c(vel, dtype)
+    w1, b1, w2, b2, w3, b3 = (_c(t, dtype) for t in params)
+    x100, ang = locoval_input(traj, pose, vel)
+    h1 = torch.relu(x100 @ w1.reshape(49, 100).T + b1)
+    h2 = torch.relu(h1 @ w2.reshape(24, 49).T + b2)
+    value = torch.sigmoid(h2 @ w3.reshape(24) + b3.reshape(()))
+    return value, x100, h1, h2, ang
+
+
+def locoval_bwd(traj, pose, vel, params, dvalue, dtype=F64):
+    """-> dparams [6174] (summed over the batch), d traj [B][13][stride] (zero beyond x, y).  Gradients by autograd of the restated
+    forward."""
+    traj = _c(traj, dtype).clone().requires_grad_(True)
+    ps = [_c(t, dtype).clone().requires_grad_(True) for t in params]
+    value = locoval_fwd_graph(traj, _c(pose, dtype), _c(vel, dtype), ps)
+    dv = _c(dvalue, dtype)
+    grads = torch.autograd.grad((value * dv).sum(), [traj] + ps)
+    return torch.cat([g.reshape(-1) for g in grads[1:]]), grads[0]
+
+
+def locoval_fwd_graph(traj, pose, vel, ps):
+    w1, b1, w2, b2, w3, b3 = ps
+    x100, _ = locoval_input(traj, pose, vel)
+    h1 = torch.relu(x100 @ w1.reshape(49, 100).T + b1)
+    h2 = torch.relu(h1 @ w2.reshape(24, 49).T + b2)
+    return torch.sigmoid(h2 @ w3.reshape(24) + b3.reshape(()))
+
+
+def locoval_input_mag(traj, pose, vel):
+    """the error scale of every element of x100: a rotation by an angle that carries a rounding error d moves a point p by |p| d, so a
+    rotated coordinate is judged against |p_x| + |p_y| of its point, not against its own size (the rotated y of waypoint 1 is ~0 by
+    construction: the yaw normalisation turns that waypoint onto the x axis)"""
+    traj, pose, vel = _c(traj, F64), _c(pose, F64), _c(vel, F64)
+    t = traj[:, :, 0].abs() + traj[:, :, 1].abs()
+    p = pose[:, :, 0].abs() + pose[:, :, 1].abs()
+    v = (vel[:, 0].abs() + vel[:, 1].abs())[:, None]
+    live = torch.ones(24, dtype=F64)
+    live[list(LV_HIDDEN_JOINTS)] = 0.0
+    p3 = torch.stack([p, p, pose[:, :, 2].abs()], dim=-1) * live[None, :, None]
+    return torch.cat([torch.stack([t, t], dim=-1).reshape(-1, 26), p3.reshape(-1, 72), v, v], dim=1)
+
+
+def locoval_bwd_terms(traj, pose, vel, params, dvalue):
+    """sum over the batch of |per-row parameter gradient| [6174]: the error scale of the fixed-order batch sum.  For dw1 the row's term
+    is |d1_j| x the MAGNITUDE of x100_k (locoval_input_mag), not |x100_k|."""
+    B = traj.shape[0]
+    tot = torch.zeros(sum(LV_SIZES), dtype=F64)
+    xmag = locoval_input_mag(traj, pose, vel)
+    for i in range(B):
+        dp, _ = locoval_bwd(traj[i:i + 1], pose[i:i + 1], vel[i:i + 1], params, dvalue[i:i + 1])
+        dp = dp.abs()
+        dp[:4900] = (dp[4900:4949, None] * xmag[i][None, :]).reshape(-1)
+        tot += dp
+    return tot
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# LocoVal fit: gradient of the sum-reduced MSE over the rows with a target, AdamW, clip + Adam
+
+def fit_grad(value, target, weight, dtype=F64):
+    """-> dvalue [n], loss sum, row count, slot [n] (rank among the valid rows, -1 elsewhere).  A weight-0 row contributes nothing,
+    whatever its value holds (NaN included)."""
+    value, target, weight = _c(value, dtype), _c(target, dtype), _c(weight, dtype)
+    live = weight != 0
+    d = torch.where(live, value - target, torch.zeros_like(value))
+    slot = torch.where(live, torch.cumsum(live.long(), 0) - 1, torch.full_like(live.long(), -1)).to(torch.int32)
+    return 2.0 * weight * d, (weight * d * d).sum(), int(live.sum()), slot
+
+
+def adamw_step(p, g, m, v, step, lr, b1, b2, eps, wd, dtype=F64):
+    """torch.optim.AdamW, step = the count AFTER this step.  -> p, m, v"""
+    p, g, m, v = (_c(t, dtype) for t in (p, g, m, v))
+    p = p * (1.0 - lr * wd)
+    m = m + (1.0 - b1) * (g - m)
+    v = v * b2 + (1.0 - b2) * g * g
+    bc1, bc2 = 1.0 - b1 ** step, 1.0 - b2 ** step
+    return p - (lr / bc1) * (m / (v.sqrt() / math.sqrt(bc2) + eps)), m, v
+
+
+def clip_coef(g, max_norm):
+    """clip_grad_norm_: -> total norm, coefficient min(1, max_norm / (norm + 1e-6)) (float64 tensors; NaN stays NaN)"""
+    norm = _c(g, F64).pow(2).sum().sqrt()
+    c = max_norm / (norm + 1e-6)
+    return norm, torch.where(c < 1.0, c, torch.where(torch.isnan(c), c, torch.ones_like(c)))
+
+
+def adam_clip_step(p, g, m, v, step, lr, b1, b2, eps, wd, max_norm, dtype=F64):
+    """clip_grad_norm_(max_norm) + torch.optim.Adam (L2 weight decay).  -> p, g (left clipped), m, v, norm, coefficient"""
+    p, g, m, v = (_c(t, dtype) for t in (p, g, m, v))
+    norm = coef = None
+    if max_norm > 0:
+        norm = g.pow(2).sum().sqrt()
+        c = max_norm / (norm + 1e-6)
+        coef = torch.where(c < 1.0, c, torch.where(torch.isnan(c), c, torch.ones_like(c)))
+        g = g * coef
+    ge = g + wd * p if wd != 0 else g
+    m = m + (1.0 - b1) * (ge - m)
+    v = v * b2 + (1.0 - b2) * ge * ge
+    bc1, bc2s = 1.0 - b1 ** step, math.sqrt(1.0 - b2 ** step)
+    return p - (lr / bc1) * (m / (v.sqrt() / bc2s + eps)), g, m, v, norm, coef
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# PPO heads
+
+def neglogp(actions, mu, logstd):
+    return 0.5 * (((actions - mu) / torch.exp(logstd)) ** 2).sum(dim=-1) + HALF_LOG_2PI * actions.shape[-1] + logstd.sum(dim=-1)
+
+
+def actor_rows(mu, logstd, actions, old_neglogp, adv, old_mu, old_sigma, e_clip):
+    """per-row [surrogate, entropy, bound loss, clipped 0/1, KL(new || old)] and the ratio"""
+    nlp = neglogp(actions, mu, logstd)
+    ratio = torch.exp(old_neglogp - nlp)
+    sur = torch.maximum(-adv * ratio, -adv * torch.clamp(ratio, 1.0 - e_clip, 1.0 + e_clip))
+    ent = (0.5 + HALF_LOG_2PI + logstd).sum(dim=-1)
+    bound = (torch.clamp_max(mu + 1.0, 0.0) ** 2 + torch.clamp_min(mu - 1.0, 0.0) ** 2).sum(dim=-1)
+    clipped = ((ratio - 1.0).abs() > e_clip).to(mu.dtype)
+    if old_mu is None:
+        kl = torch.zeros_like(sur)
+    else:
+        s = torch.exp(logstd)
+        kl = (torch.log(old_sigma / s + 1e-5) + (s ** 2 + (old_mu - mu) ** 2) / (2.0 * (old_sigma ** 2 + 1e-5)) - 0.5).sum(dim=-1)
+    return torch.stack([sur, ent, bound, clipped, kl], dim=1), ratio
+
+
+def actor_head_fwd(mu, logstd, actions, old_neglogp, adv, old_mu, old_sigma, e_clip, dtype=F64):
+    """-> out5 (means over the rows), per-row values [B][5], ratio [B]"""
+    a = [_c(t, dtype) for t in (mu, logstd, actions, old_neglogp, adv, old_mu, old_sigma)]
+    rows, ratio = actor_rows(*a, e_clip)
+    return rows.mean(dim=0), rows, ratio
+
+
+def actor_head_bwd(mu, logstd, actions, old_neglogp, adv, e_clip, grad3, dtype=F64):
+    """d(g0 mean surrogate + g1 mean entropy + g2 mean bound) / d(mu, logstd); torch's maximum hands a tie half to each side and clamp
+    passes the gradient on its closed interval"""
+    mu, logstd, actions, old_neglogp, adv, g = (_c(t, dtype) for t in (mu, logstd, actions, old_neglogp, adv, grad3))
+    B = mu.shape[0]
+    s = torch.exp(logstd)
+    t = (actions - mu) / s
+    ratio = torch.exp(old_neglogp - neglogp(actions, mu, logstd))
+    lo, hi = 1.0 - e_clip, 1.0 + e_clip
+    s1, s2 = -adv * ratio, -adv * torch.clamp(ratio, lo, hi)
+    w1 = torch.where(s1 > s2, 1.0, torch.where(s1 == s2, 0.5, 0.0)).to(dtype)
+    inr = ((ratio >= lo) & (ratio <= hi)).to(dtype)
+    c_nlp = (g[0] / B * adv * ratio * (w1 + (1.0 - w1) * inr))[:, None]
+    dmu = c_nlp * (-t / s) + g[2] / B * 2.0 * (torch.clamp_max(mu + 1.0, 0.0) + torch.clamp_min(mu - 1.0, 0.0))
+    dlogstd = c_nlp * (1.0 - t * t) + g[1] / B
+    return dmu, dlogstd
+
+
+def critic_rows(v, v_old, ret, e_clip, clip_value):
+    if clip_value:
+        vc = v_old + torch.clamp(v - v_old, -e_clip, e_clip)
+        return torch.maximum((v - ret) ** 2, (vc - ret) ** 2)
+    return (ret - v) ** 2
+
+
+def critic_head_fwd(v, v_old, ret, e_clip, clip_value, dtype=F64):
+    rows = critic_rows(_c(v, dtype), _c(v_old, dtype), _c(ret, dtype), e_clip, clip_value)
+    return rows.mean(), rows
+
+
+def critic_head_bwd(v, v_old, ret, e_clip, clip_value, grad1, dtype=F64):
+    v, v_old, ret, g = _c(v, dtype), _c(v_old, dtype), _c(ret, dtype), _c(grad1, dtype)
+    d1 = v - ret
+    grad = 2.0 * d1
+    if clip_value:
+        dlt = v - v_old
+        d2 = v_old + torch.clamp(dlt, -e_clip, e_clip) - ret
+        l1, l2 = d1 * d1, d2 * d2
+        w1 = torch.where(l1 > l2, 1.0, torch.where(l1 == l2, 0.5, 0.0)).to(dtype)
+        inr = ((dlt >= -e_clip) & (dlt <= e_clip)).to(dtype)
+        grad = w1 * 2.0 * d1 + (1.0 - w1) * 2.0 * d2 * inr
+    return g.reshape(-1)[0] * grad / v.shape[0]
+
+
+def bce_logits(x, target):
+    """BCEWithLogits per element: max(x, 0) - x t + log(1 + exp(-|x|))"""
+    return torch.clamp_min(x, 0.0) - x * target + torch.log1p(torch.exp(-x.abs()))
+
+
+def disc_head_fwd(agent, demo, dtype=F64):
+    """-> out4 = [mean bce(agent, 0), fraction agent < 0, mean bce(demo, 1), fraction demo > 0], per-row bce of both groups"""
+    a, d = _c(agent, dtype), _c(demo, dtype)
+    ra, rd = bce_logits(a, 0.0), bce_logits(d, 1.0)
+    return torch.stack([ra.mean(), (a < 0).to(dtype).mean(), rd.mean(), (d > 0).to(dtype).mean()]), ra, rd
+
+
+def disc_head_bwd(agent, demo, grad2, dtype=F64):
+    a, d, g = _c(agent, dtype), _c(demo, dtype), _c(grad2, dtype)
+    return g[0] * torch.sigmoid(a) / a.shape[0], g[1] * (torch.sigmoid(d) - 1.0) / d.shape[0]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# error measures and branch distances
+
+def err_max(got, ref):
+    """max |got - ref| over the tensor's own scale max |ref| (normalised outputs)"""
+    got, ref = _c(got, F64), _c(ref, F64)
+    assert torch.isfinite(got).all(), "non-finite output (an element not written, or a bad value)"
+    return ((got - ref).abs().max() / ref.abs().max().clamp_min(1e-300)).item()
+
+
+def err_terms(got, ref, terms):
+    """max |got - ref| / sum |terms| (sums and dot products)"""
+    got, ref, terms = _c(got, F64), _c(ref, F64), _c(terms, F64)
+    assert torch.isfinite(got).all(), "non-finite output (an element not written, or a bad value)"
+    return ((got - ref).abs() / terms.clamp_min(1e-300)).max().item()
+
+
+def near_share(dist, scale, rel=1e-5):
+    """share of the elements whose float64 distance to a branch point is below rel x the operand scale"""
+    dist = _c(dist, F64).abs()
+    return (dist < rel * scale).double().mean().item()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# seeded inputs of the random cases with a branch in them (shared by the CPU test, which counts their near-branch elements, and the
+# device matrix, which runs them)
+
+def _gen(seed):
+    g = torch.Generator(device="cpu")
+    g.manual_seed(seed)
+    return g
+
+
+def case_actor(B, A, seed):
+    """mu / logstd / actions / old statistics of a PPO minibatch: ratios spread over both sides of the clip range, some mu beyond +-1"""
+    g = _gen(seed)
+    mu = torch.randn(B, A, generator=g) * 0.7
+    logstd = torch.randn(B, A, generator=g) * 0.1 - 1.0
+    actions = mu + torch.exp(logstd) * torch.randn(B, A, generator=g)
+    old_mu = mu + 0.05 * torch.randn(B, A, generator=g)
+    old_sigma = torch.exp(logstd + 0.05 * torch.randn(B, A, generator=g))
+    nlp = neglogp(actions.double(), mu.double(), logstd.double())
+    old_neglogp = (nlp + 0.3 * torch.randn(B, generator=g).double()).float()
+    adv = torch.randn(B, generator=g)
+    return dict(mu=mu, logstd=logstd, actions=actions, old_neglogp=old_neglogp, adv=adv, old_mu=old_mu, old_sigma=old_sigma)
+
+
+def actor_branch_distances(c, e_clip):
+    """float64 distances of a case to its branch points: ratio to the clip edges (relative to 1), mu to +-1"""
+    d = {k: v.double() for k, v in c.items()}
+    ratio = torch.exp(d["old_neglogp"] - neglogp(d["actions"], d["mu"], d["logstd"]))
+    edge = torch.minimum((ratio - (1.0 - e_clip)).abs(), (ratio - (1.0 + e_clip)).abs())
+    bound = torch.minimum((d["mu"] - 1.0).abs(), (d["mu"] + 1.0).abs())
+    return edge, bound
+
+
+def case_critic(B, seed):
+    g = _gen(seed)
+    v_old = torch.randn(B, generator=g)
+    v = v_old + 0.3 * torch.randn(B, generator=g)
+    ret = v_old + 0.5 * torch.randn(B, generator=g)
+    return dict(v=v, v_old=v_old, ret=ret)
+
+
+def critic_branch_distances(c, e_clip):
+    """distance of v - v_old to +-e, and of the two losses to each other (where they are not the same expression)"""
+    v, v_old, ret = c["v"].double(), c["v_old"].double(), c["ret"].double()
+    dlt = v - v_old
+    edge = torch.minimum((dlt - e_clip).abs(), (dlt + e_clip).abs())
+    l1 = (v - ret) ** 2
+    l2 = (v_old + torch.clamp(dlt, -e_clip, e_clip) - ret) ** 2
+    tie = torch.where(dlt.abs() <= e_clip, torch.full_like(l1, float("inf")), (l1 - l2).abs())
+    return edge, tie
+
+
+def case_locoval(B, stride, seed):
+    g = _gen(seed)
+    traj = torch.zeros(B, 13, stride)
+    traj[:, :, :2] = torch.cumsum(torch.randn(B, 13, 2, generator=g) * 0.3 + torch.tensor([0.5, 0.1]), dim=1)
+    traj[:, 0] = 0
+    if stride > 2:
+        traj[:, :, 2:] = torch.randn(B, 13, stride - 2, generator=g) * 50.0        # must not enter anything
+    pose = torch.randn(B, 24, 3, generator=g) * 0.3
+    vel = torch.randn(B, 2, generator=g)
+    params = [torch.randn(49, 100, generator=g) * 0.15, torch.randn(49, generator=g) * 0.1, torch.randn(24, 49, generator=g) * 0.2,
+              torch.randn(24, generator=g) * 0.1, torch.randn(24, generator=g) * 0.3, torch.randn(1, generator=g) * 0.1]
+    dvalue = torch.randn(B, generator=g)
+    return dict(traj=traj, pose=pose, vel=vel, params=params, dvalue=dvalue)
+
+
+def locoval_branch_distances(c):
+    """pre-activations of the two ReLU layers (distance to 0) in float64"""
+    traj, pose, vel = c["traj"].double(), c["pose"].double(), c["vel"].double()
+    w1, b1, w2, b2 = (t.double() for t in c["params"][:4])
+    x100, _ = locoval_input(traj, pose, vel)
+    z1 = x100 @ w1.T + b1
+    z2 = torch.relu(z1) @ w2.T + b2
+    return z1, z2
+
+
+def case_ffn(M, F, seed):
+    g = _gen(seed)
+    return dict(x=torch.randn(M, 128, generator=g), w1=torch.randn(F, 128, generator=g) * 0.09, b1=torch.randn(F, generator=g) * 0.1,
+                w2=torch.randn(128, F, generator=g) * (1.0 / math.sqrt(F)), b2=torch.randn(128, generator=g) * 0.1,
+                dz2=torch.randn(M, 128, generator=g), res=torch.randn(M, 128, generator=g),
+                gamma=1.0 + 0.1 * torch.randn(128, generator=g), beta=0.1 * torch.randn(128, generator=g))
+
+
+def case_obs(rows, cols, seed):
+    g = _gen(seed)
+    mean = torch.randn(cols, generator=g)
+    var = torch.rand(cols, generator=g) * 2.0 + 0.05
+    x = mean + torch.sqrt(var) * torch.randn(rows, cols, generator=g) * 2.5      # ~4.5 % beyond the clamp at 5
+    return dict(x=x, mean=mean, var=var)

@@ -1447,3 +1447,109 @@ def test_ppo_loss_heads_follow_the_torch_expressions():
     np.testing.assert_allclose(out4, [la_loss.item(), (ta < 0).float().mean().item(), ld_loss.item(), (td > 0).float().mean().item()], rtol=3e-6)
     np.testing.assert_allclose(da, ta.grad.numpy(), rtol=2e-5, atol=1e-9)
     np.testing.assert_allclose(dd, td.grad.numpy(), rtol=2e-5, atol=1e-9)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# gather_flat, act_bwd, disc_reward and the row stride of obs_normalize (exports added with the element-wise device matrix)
+
+def _gather_flat_case(sizes, src_skew, dst_skew, gap=3):
+    """Sources cut from one float32 pool at offsets skewed off 16-byte alignment, destinations laid out with `gap` untouched floats
+    between slices.  Returns (pointer array, numel, offsets, flat before, expected flat, sources kept alive)."""
+    rng = np.random.default_rng(len(sizes) * 7 + src_skew + 3 * dst_skew)
+    pool = np.zeros(int(sum(sizes)) + 8 * len(sizes) + 16, np.float32)
+    base = pool.ctypes.data
+    start = (-base // 4) % 4                                    # pool[start] is 16-byte aligned
+    srcs, ptrs, offs = [], [], []
+    o, d = start, dst_skew
+    for i, n in enumerate(sizes):
+        o = o + (-(o - start)) % 4 + (src_skew * i) % 4          # aligned + skew
+        v = pool[o:o + n]
+        v[:] = rng.standard_normal(n).astype(np.float32) + 10.0 * (i + 1)
+        srcs.append(v)
+        ptrs.append(base + 4 * o)
+        o += n
+        offs.append(d)
+        d += n + gap + (dst_skew * i) % 4
+    flat = np.full(d + 16, -777.25, np.float32)
+    want = flat.copy()
+    for v, off in zip(srcs, offs):
+        want[off:off + len(v)] = v
+    return (C.c_void_p * len(sizes))(*ptrs), np.asarray(sizes, np.int64), np.asarray(offs, np.int64), flat, want, pool
+
+
+@pytest.mark.parametrize("sizes,src_skew,dst_skew", [
+    ([1, 2, 3, 4, 5, 0, 7, 1023, 1024, 1025], 0, 0),            # numel % 4 != 0, numel == 0, aligned both ends where the layout allows
+    ([5, 0, 16, 33, 4096 + 3], 1, 0),                            # sources off alignment
+    ([5, 0, 16, 33, 4096 + 3], 0, 1),                            # destinations off alignment
+    ([7] * 96 + [9], 1, 2),                                      # 97 tensors: the second launch holds one
+    ([(i * 37) % 50 for i in range(200)], 3, 1),                 # 200 tensors (three launches), several empty
+    ([3, 300000, 5, 0, 64], 0, 0),                               # one tensor far larger than the others: the 64-workgroup cap
+])
+def test_gather_flat_kernel_copies_every_slice_and_nothing_else(sizes, src_skew, dst_skew):
+    lib = emu.lib()
+    ptrs, numel, offs, flat, want, pool = _gather_flat_case(sizes, src_skew, dst_skew)
+    assert lib.emu_gather_flat(len(sizes), ptrs, P(numel), P(offs), P(flat)) == 0
+    assert np.array_equal(flat.view(np.uint32), want.view(np.uint32)), "a slice differs, or a gap / the tail was written"
+    assert (want == -777.25).sum() >= 16 + 3 * (len(sizes) - 1)
+    del pool
+
+
+@pytest.mark.parametrize("relu,p", [(1, 0.0), (0, 0.25), (1, 0.25), (0, 0.0)])
+@pytest.mark.parametrize("total", [1, 255, 256, 257, 1000])
+def test_act_bwd_kernel_matches_numpy(total, relu, p):
+    lib = emu.lib()
+    lib.emu_drop_keep.argtypes = [C.c_uint, C.c_ulonglong, C.c_float]
+    rng = np.random.default_rng(total + relu)
+    dy = rng.standard_normal(total).astype(np.float32)
+    y = rng.standard_normal(total).astype(np.float32)
+    y[::7] = 0.0                                                # y == 0 is not active
+    dz = np.full(total + 8, -777.25, np.float32)
+    seed = 0xBEEF
+    assert lib.emu_act_bwd(C.c_long(total), P(dy), P(y), relu, C.c_float(p), C.c_uint(seed), P(dz)) == 0
+    want = dy.copy()
+    if relu:
+        want = np.where(y > 0, want, np.float32(0))
+    if p > 0:
+        inv = np.float32(1.0) / (np.float32(1.0) - np.float32(p))
+        keep = np.ones(total, bool) if relu else np.array([lib.emu_drop_keep(seed, i, C.c_float(p)) for i in range(total)], bool)
+        want = np.where(keep, want * inv, np.float32(0)).astype(np.float32)
+    assert np.array_equal(dz[:total], want) and np.all(dz[total:] == -777.25)
+
+
+def test_disc_reward_kernel_matches_float64_and_its_floor():
+    lib = emu.lib()
+    x = np.concatenate([np.linspace(-12, 6.5, 300), [12.0, 20.0, 80.0, 0.0]]).astype(np.float32)
+    out = np.full(len(x) + 4, -777.25, np.float32)
+    assert lib.emu_disc_reward(len(x), P(x), C.c_float(2.0), P(out)) == 0
+    om = 1.0 - 1.0 / (1.0 + np.exp(-x.astype(np.float64)))
+    want = -np.log(np.maximum(om, 1e-4)) * 2.0
+    live = om >= 1e-3                                            # (1 - sigmoid cancels in float32: compared where it is well conditioned)
+    assert live.sum() >= 250
+    # prob carries <= 2^-24 of absolute rounding and 1 - prob another, so log's argument is off by <= 2^-23 / 1e-3 relative; times the
+    # scale, plus the result's own roundings (2^-22 of its magnitude)
+    bar = 2.0 * 2.0 ** -23 / 1e-3 + 2.0 ** -22 * np.abs(want[live]).max()
+    assert np.abs(out[:len(x)][live] - want[live]).max() <= bar
+    floor = np.float32(-np.log(np.float32(0.0001))) * np.float32(2.0)
+    assert np.all(np.abs(out[300:303] - floor) <= 2.0 ** -22 * floor) and np.all(out[len(x):] == -777.25)
+
+
+@pytest.mark.parametrize("grid_y", [0, 1, 3, 7])
+def test_obs_normalize_kernel_strides_over_rows(grid_y):
+    """the launch caps grid.y (65 535 rows at a time) and the kernel strides over the rest: the same bits whatever the grid"""
+    lib = emu.lib()
+    rng = np.random.default_rng(5)
+    rows, cols, ldx, split, ld0, ld1 = 23, 300, 310, 130, 140, 200
+    x = (rng.standard_normal((rows, ldx)) * 3).astype(np.float32)
+    mean, var = rng.standard_normal(cols).astype(np.float32), (rng.random(cols) + 0.1).astype(np.float32)
+    out0, out1 = np.full((rows, ld0), -777.25, np.float32), np.full((rows, ld1), -777.25, np.float32)
+    assert lib.emu_obs_normalize_grid(rows, cols, P(x), ldx, P(mean), P(var), C.c_float(1e-5), C.c_float(5.0), split, P(out0), ld0,
+                                      P(out1), ld1, grid_y) == 0
+    want = np.clip((x[:, :cols] - mean) / np.sqrt(var + np.float32(1e-5)), -5.0, 5.0).astype(np.float32)
+    np.testing.assert_allclose(out0[:, :split], want[:, :split], rtol=2e-6, atol=2e-6)
+    np.testing.assert_allclose(out1[:, :cols - split], want[:, split:], rtol=2e-6, atol=2e-6)
+    assert np.all(out0[:, split:] == -777.25) and np.all(out1[:, cols - split:] == -777.25)
+    if grid_y:                                                  # bit for bit what the launcher's own grid gives
+        ref0, ref1 = np.full((rows, ld0), -777.25, np.float32), np.full((rows, ld1), -777.25, np.float32)
+        assert lib.emu_obs_normalize_grid(rows, cols, P(x), ldx, P(mean), P(var), C.c_float(1e-5), C.c_float(5.0), split, P(ref0), ld0,
+                                          P(ref1), ld1, 0) == 0
+        assert np.array_equal(out0.view(np.uint32), ref0.view(np.uint32)) and np.array_equal(out1.view(np.uint32), ref1.view(np.uint32))
