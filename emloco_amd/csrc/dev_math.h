@@ -223,11 +223,18 @@ template <int CTRL> __device__ __forceinline__ float dpp_mov(float v) {
 __device__ __forceinline__ float lane_bcast(float v, int src_lane /* wave-uniform */) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src_lane));
 }
-__device__ __forceinline__ float wave_sum(float v) {
+// The sum of one 16-lane DPP row, left in every lane of that row: the four rows of a wave are summed independently (four samples per
+// wave in the narrow LocoVal kernels, locoval_variants.h).  The CPU emulation executes the same four permutations
+// (tests/emu/hip/hip_runtime.h: __builtin_amdgcn_update_dpp), so the association order is one source for both.
+__device__ __forceinline__ float row_sum(float v) {
     v += dpp_mov<0x140>(v);   // row_mirror
     v += dpp_mov<0x141>(v);   // row_half_mirror
     v += dpp_mov<0xB1>(v);    // quad_perm [1,0,3,2]
     v += dpp_mov<0x4E>(v);    // quad_perm [2,3,0,1]
+    return v;
+}
+__device__ __forceinline__ float wave_sum(float v) {
+    v = row_sum(v);
     return ((lane_bcast(v, 0) + lane_bcast(v, 16)) + lane_bcast(v, 32)) + lane_bcast(v, 48);   // fixed order r0+r1+r2+r3
 }
 

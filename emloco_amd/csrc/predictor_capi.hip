@@ -423,6 +423,80 @@ int emloco_locoval_bwd_rows(int B, const float *traj, int traj_stride, const flo
     return 0;
 }
 
+// ---- the LocoVal networks by variant (locoval_variants.h); variant 3 goes through the kernels of the entry points above
+}  // extern "C"
+namespace {
+struct KernelLaunch {
+    hipStream_t st;
+    template <class K, class... A> void operator()(K kernel, unsigned grid, unsigned block, A... args) const {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, st, args...);
+    }
+};
+bool locoval_inputs_ok(int variant, int B, const float *traj, int ts, const float *pose, const float *vel) {
+    emloco::LocoValDims d;
+    return emloco::locoval_dims(variant, &d) && B >= 1 && ts >= 2 && traj && ((variant & 2) == 0 || pose) && ((variant & 1) == 0 || vel);
+}
+}  // namespace
+extern "C" {
+
+int emloco_locoval_variant_dims(int variant, int32_t *dims4) {
+    emloco::LocoValDims d;
+    if (!dims4 || !emloco::locoval_dims(variant, &d)) return pfail(-1, "emloco_locoval_variant_dims: bad argument (variant 0..3)");
+    dims4[0] = d.in; dims4[1] = d.h1; dims4[2] = d.h2; dims4[3] = d.n_param;
+    return 0;
+}
+
+int emloco_locoval_variant_fwd_rows(int variant, int B, const float *traj, int traj_stride, const float *pose, const float *vel,
+                                    const float *w1, const float *b1, const float *w2, const float *b2, const float *w3, const float *b3,
+                                    float *value, float *x, float *h1, float *h2, float *angle, float *pose_rot, const float *row_weight,
+                                    void *stream) {
+    if (!locoval_inputs_ok(variant, B, traj, traj_stride, pose, vel) || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !value || !x || !h1 || !h2 ||
+        (pose_rot && ((variant & 2) || !pose)))
+        return pfail(-1, "emloco_locoval_variant_fwd: bad argument (pose_rot is for the variants that do not read the pose)");
+    const emloco::LocoValFwd a{B, traj, traj_stride, pose, vel, w1, b1, w2, b2, w3, b3, value, x, h1, h2, angle, pose_rot, row_weight};
+    emloco::locoval_variant_fwd(KernelLaunch{(hipStream_t)stream}, variant, a);
+    PHIPCHK(hipGetLastError());
+    return 0;
+}
+
+int emloco_locoval_variant_fwd(int variant, int B, const float *traj, int traj_stride, const float *pose, const float *vel, const float *w1,
+                               const float *b1, const float *w2, const float *b2, const float *w3, const float *b3, float *value, float *x,
+                               float *h1, float *h2, float *angle, float *pose_rot, void *stream) {
+    return emloco_locoval_variant_fwd_rows(variant, B, traj, traj_stride, pose, vel, w1, b1, w2, b2, w3, b3, value, x, h1, h2, angle, pose_rot,
+                                           nullptr, stream);
+}
+
+int64_t emloco_locoval_variant_bwd_workspace(int variant, int B) {
+    emloco::LocoValDims d;
+    if (!emloco::locoval_dims(variant, &d) || B < 1) return -1;
+    return (int64_t)B * d.n_param * (int64_t)sizeof(float);
+}
+
+int emloco_locoval_variant_bwd_rows(int variant, int B, const float *traj, int traj_stride, const float *pose, const float *vel,
+                                    const float *w1, const float *w2, const float *w3, const float *value, const float *x, const float *h1,
+                                    const float *h2, const float *angle, const float *dvalue, const int32_t *slot, const float *count,
+                                    float *dparams, float *dtraj, float *workspace, void *stream) {
+    if (!locoval_inputs_ok(variant, B, traj, traj_stride, pose, vel) || !w1 || !w2 || !w3 || !value || !x || !h1 || !h2 || !angle || !dvalue ||
+        !slot || !count || !dparams || !dtraj || !workspace)
+        return pfail(-1, "emloco_locoval_variant_bwd_rows: bad argument");
+    const emloco::LocoValBwd a{B, traj, traj_stride, pose, vel, w1, w2, w3, value, x, h1, h2, angle, dvalue, workspace, dparams, dtraj, slot, count};
+    emloco::locoval_variant_bwd(KernelLaunch{(hipStream_t)stream}, variant, a);
+    PHIPCHK(hipGetLastError());
+    return 0;
+}
+
+int emloco_locoval_variant_bwd(int variant, int B, const float *traj, int traj_stride, const float *pose, const float *vel, const float *w1,
+                               const float *w2, const float *w3, const float *value, const float *x, const float *h1, const float *h2,
+                               const float *angle, const float *dvalue, float *dparams, float *dtraj, float *workspace, void *stream) {
+    if (!locoval_inputs_ok(variant, B, traj, traj_stride, pose, vel) || !w1 || !w2 || !w3 || !value || !x || !h1 || !h2 || !angle || !dvalue ||
+        !dparams || !dtraj || !workspace)
+        return pfail(-1, "emloco_locoval_variant_bwd: bad argument");
+    const emloco::LocoValBwd a{B, traj, traj_stride, pose, vel, w1, w2, w3, value, x, h1, h2, angle, dvalue, workspace, dparams, dtraj, nullptr, nullptr};
+    emloco::locoval_variant_bwd(KernelLaunch{(hipStream_t)stream}, variant, a);
+    PHIPCHK(hipGetLastError());
+    return 0;
+}
+
 int emloco_locoval_returns(const EmlocoLocoValStep *t, const float *rewards, const float *amp_rewards, const int64_t *dones,
                            const uint8_t *inverted, void *stream) {
     if (!t || !rewards || !dones || t->n_env < 1 || !t->current_rewards || !t->current_lengths || !t->current_combined_rewards ||

@@ -1684,3 +1684,5 @@ __global__ void adam_flat_kernel(long n, float *p, float *g, float *m, float *v,
 }
 
 }  // namespace emloco
+
+#include "locoval_variants.h"       // the reduced-input LocoVal networks beside locoval_fwd_kernel / locoval_bwd_kernel

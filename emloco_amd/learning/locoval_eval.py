@@ -154,7 +154,8 @@ class LocoValEvaluator:
                            tp_loc=f(E), tp_pow=f(E), steps=i32(E), games=i32(E), done=u8(E), terminated=u8(E), inverted=u8(E),
                            n_full=i32(1), traj13=f(E, 13, 3), pose=f(E, 24, 3), vel=f(E, 2), row_mask=f(E))
         # the forward's persistent output (a game's prediction stays in its row until the game is recorded) and its scratch rows
-        self._value, self._x100, self._h1, self._h2, self._ang = f(E), f(E, 100), f(E, 49), f(E, 24), f(E)
+        n_in, n_h1, n_h2, _ = ops.locoval_dims(valuenet.variant)          # the network's input configuration (value_pose_net.py:43-52)
+        self._value, self._x100, self._h1, self._h2, self._ang = f(E), f(E, n_in), f(E, n_h1), f(E, n_h2), f(E)
         self._records = torch.zeros(E * G * RECORD_WORDS, dtype=torch.int32, device=dev)
         self._moments = torch.zeros(ops.EVAL_MOMENTS, dtype=torch.float64, device=dev)
         self._inputs = ("waypoint_traj", "init_pose", "init_vel")
@@ -224,9 +225,14 @@ class LocoValEvaluator:
         w = [n.fc1.weight, n.fc1.bias, n.fc2.weight, n.fc2.bias, n.fc3.weight, n.fc3.bias]
         for t in w:
             assert t.dtype == torch.float32 and t.is_contiguous() and t.device == self.device
-        ops._chk(ops._lib().emloco_locoval_fwd_rows(self.num_envs, P(b["traj13"]), 3, P(b["pose"]), P(b["vel"]), *[P(t) for t in w],
-                                                    P(self._value), P(self._x100), P(self._h1), P(self._h2), P(self._ang), P(b["row_mask"]),
-                                                    st), "emloco_locoval_fwd_rows")
+        if self.valuenet.variant == ops.LOCOVAL_FULL:
+            ops._chk(ops._lib().emloco_locoval_fwd_rows(self.num_envs, P(b["traj13"]), 3, P(b["pose"]), P(b["vel"]), *[P(t) for t in w],
+                                                        P(self._value), P(self._x100), P(self._h1), P(self._h2), P(self._ang), P(b["row_mask"]),
+                                                        st), "emloco_locoval_fwd_rows")
+        else:
+            ops._chk(ops._lib().emloco_locoval_variant_fwd_rows(self.valuenet.variant, self.num_envs, P(b["traj13"]), 3, P(b["pose"]), P(b["vel"]),
+                                                                *[P(t) for t in w], P(self._value), P(self._x100), P(self._h1), P(self._h2),
+                                                                P(self._ang), None, P(b["row_mask"]), st), "emloco_locoval_variant_fwd_rows")
 
     # ------------------------------------------------------------------ the run
     def envs_full(self):

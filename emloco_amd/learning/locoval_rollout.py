@@ -16,7 +16,8 @@ arithmetic, the fit runs as a masked sum over all envs, and AdamW commits its up
 episode counters are device tensors read when someone asks for them (`vnet_loss`, `fitted_episodes`, ...).
 
 Multi-GPU: every rank issues exactly one all-reduce per rollout step, whatever its own episodes did -- the flat gradient
-bucket (6 174 floats) with the loss sum and the episode count in its tail; gradients are sum-reduced and the loss is
+bucket (the network's parameters: 6 174 floats with pose + velocity, 409 for the trajectory alone) with the loss sum and the
+episode count in its tail; gradients are sum-reduced and the loss is
 divided by the global episode count (MSELoss(reduction='sum') semantics, common_agent.py:96).  All ranks step together
 when the global count is positive, so the replicas (broadcast from rank 0 at construction) stay identical.
 """
@@ -126,9 +127,15 @@ class LocoValRollout:
         from ..predictor import ops
         E, dev, task, a = self.num_actors, self.device, self.task, self.acc
         f = lambda *s: torch.zeros(*s, device=dev)
+        # every size follows the network's input configuration (value_pose_net.py:43-52): 100 / 49 / 24 / 6 174 for pose + velocity
+        # down to 26 / 12 / 6 / 409 for the trajectory alone -- the reference's default command line
+        self._variant = self.valuenet.variant
+        n_in, n_h1, n_h2, n_param = ops.locoval_dims(self._variant)
+        self._n_param = n_param
+        assert self.bucket.grads.numel() == n_param and self._flat_params.numel() == n_param
         self._fz = dict(traj13=f(E, 13, 3), pose=f(E, 24, 3), vel=f(E, 2), target=f(E), weight=f(E), value=f(E), dvalue=f(E),
-                        x100=f(E, 100), h1=f(E, 49), h2=f(E, 24), ang=f(E), dtraj=f(E, 13, 3), ws=f(E * 6174), zeros=f(E),
-                        steps=[f(1), f(1)], m=f(6174), v=f(6174), slot=torch.zeros(E, dtype=torch.int32, device=dev))
+                        x100=f(E, n_in), h1=f(E, n_h1), h2=f(E, n_h2), ang=f(E), dtraj=f(E, 13, 3), ws=f(E * n_param), zeros=f(E),
+                        steps=[f(1), f(1)], m=f(n_param), v=f(n_param), slot=torch.zeros(E, dtype=torch.int32, device=dev))
         z = self._fz
         self._check_fused_inputs()
         p = lambda t: t.data_ptr()
@@ -369,18 +376,30 @@ class LocoValRollout:
         P = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         n = self.valuenet._network
         w = [n.fc1.weight, n.fc1.bias, n.fc2.weight, n.fc2.bias, n.fc3.weight, n.fc3.bias]
-        ops._chk(lib.emloco_locoval_fwd_rows(E, P(z["traj13"]), 3, P(z["pose"]), P(z["vel"]), *[P(t) for t in w], P(z["value"]), P(z["x100"]),
-                                             P(z["h1"]), P(z["h2"]), P(z["ang"]), P(z["weight"]), st), "emloco_locoval_fwd_rows")
+        full, var = self._variant == ops.LOCOVAL_FULL, self._variant
+        if full:
+            ops._chk(lib.emloco_locoval_fwd_rows(E, P(z["traj13"]), 3, P(z["pose"]), P(z["vel"]), *[P(t) for t in w], P(z["value"]), P(z["x100"]),
+                                                 P(z["h1"]), P(z["h2"]), P(z["ang"]), P(z["weight"]), st), "emloco_locoval_fwd_rows")
+        else:
+            ops._chk(lib.emloco_locoval_variant_fwd_rows(var, E, P(z["traj13"]), 3, P(z["pose"]), P(z["vel"]), *[P(t) for t in w], P(z["value"]),
+                                                         P(z["x100"]), P(z["h1"]), P(z["h2"]), P(z["ang"]), None, P(z["weight"]), st),
+                     "emloco_locoval_variant_fwd_rows")
         ops._chk(lib.emloco_locoval_fit_grad(E, P(z["value"]), P(z["target"]), P(z["weight"]), P(z["dvalue"]), P(self.bucket.tail), P(z["slot"]), st),
                  "emloco_locoval_fit_grad")
-        ops._chk(lib.emloco_locoval_bwd_rows(E, P(z["traj13"]), 3, P(z["pose"]), P(z["vel"]), P(w[0]), P(w[2]), P(w[4]), P(z["value"]), P(z["x100"]),
-                                             P(z["h1"]), P(z["h2"]), P(z["ang"]), P(z["dvalue"]), P(z["slot"]), P(self.bucket.tail[1:]),
-                                             P(self.bucket.grads), P(z["dtraj"]), P(z["ws"]), st), "emloco_locoval_bwd_rows")
+        if full:
+            ops._chk(lib.emloco_locoval_bwd_rows(E, P(z["traj13"]), 3, P(z["pose"]), P(z["vel"]), P(w[0]), P(w[2]), P(w[4]), P(z["value"]), P(z["x100"]),
+                                                 P(z["h1"]), P(z["h2"]), P(z["ang"]), P(z["dvalue"]), P(z["slot"]), P(self.bucket.tail[1:]),
+                                                 P(self.bucket.grads), P(z["dtraj"]), P(z["ws"]), st), "emloco_locoval_bwd_rows")
+        else:
+            ops._chk(lib.emloco_locoval_variant_bwd_rows(var, E, P(z["traj13"]), 3, P(z["pose"]), P(z["vel"]), P(w[0]), P(w[2]), P(w[4]), P(z["value"]),
+                                                         P(z["x100"]), P(z["h1"]), P(z["h2"]), P(z["ang"]), P(z["dvalue"]), P(z["slot"]),
+                                                         P(self.bucket.tail[1:]), P(self.bucket.grads), P(z["dtraj"]), P(z["ws"]), st),
+                     "emloco_locoval_variant_bwd_rows")
         self.bucket.all_reduce(average=False)                                               # unconditional: one collective per step
         g = self.vnet_optimizer.param_groups[0]
         a, b = z["steps"][self._flip], z["steps"][self._flip ^ 1]
         self._flip ^= 1
-        ops._chk(lib.emloco_adamw_gated(6174, P(self._flat_params), P(self.bucket.grads), P(z["m"]), P(z["v"]), P(a), P(b), P(self.bucket.tail),
+        ops._chk(lib.emloco_adamw_gated(self._n_param, P(self._flat_params), P(self.bucket.grads), P(z["m"]), P(z["v"]), P(a), P(b), P(self.bucket.tail),
                                         float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
                                         P(self._stats), st), "emloco_adamw_gated")
 

@@ -167,7 +167,8 @@ class EvalAccumulator:
         calls = torch.stack([pred_traj, gt_traj[:, None].expand(B, M, 13, 2)], 2).reshape(B, 2 * M, 13, 2)
         valid = ~(torch.isnan(init_pose).reshape(B, -1).any(1)[:, None] | torch.isnan(pred_traj).reshape(B, M, -1).any(2))   # (B,M)
         pose_c = init_pose[:, None].expand(B, 2 * M, 24, 3).clone()
-        if self.inplace_pose:
+        reads_pose, reads_vel = getattr(valuenet, "use_pose", True), getattr(valuenet, "use_vel", True)
+        if self.inplace_pose and reads_pose:                                      # (a network that does not read the pose: nothing to reproduce)
             theta = _heading(calls) * valid.repeat_interleave(2, 1)               # skipped calls do not rotate the pose
             before = torch.cumsum(theta, 1) - theta                               # rotation already applied when call c starts
             pose_c[..., :2] = _rotate_xy(pose_c[..., :2], before[:, :, None].expand(B, 2 * M, 24))
@@ -181,7 +182,7 @@ class EvalAccumulator:
         vel_c = torch.nan_to_num(flat(init_vel[:, None].expand(B, 2 * M, 2)))
         was_inplace = getattr(valuenet, "inplace_pose", False)
         valuenet.inplace_pose = False
-        values = valuenet(safe_calls, safe_pose, vel_c).reshape(B, M, 2).double()
+        values = valuenet(safe_calls, safe_pose if reads_pose else None, vel_c if reads_vel else None).reshape(B, M, 2).double()
         valuenet.inplace_pose = was_inplace
         v_pred, v_gt = values[..., 0], values[..., 1]
         nv = int(valid.sum())

@@ -81,6 +81,13 @@ def _lib():
         lib.emloco_locoval_returns_finish.argtypes = [C.POINTER(LocoValStep), vp, vp]
         lib.emloco_locoval_fit_grad.argtypes = [ci, vp, vp, vp, vp, vp, vp, vp]
         lib.emloco_locoval_bwd_rows.argtypes = [ci, vp, ci] + [vp] * 17
+        lib.emloco_locoval_variant_dims.argtypes = [ci, vp]
+        lib.emloco_locoval_variant_fwd.argtypes = [ci, ci, vp, ci] + [vp] * 15
+        lib.emloco_locoval_variant_fwd_rows.argtypes = [ci, ci, vp, ci] + [vp] * 16
+        lib.emloco_locoval_variant_bwd.argtypes = [ci, ci, vp, ci] + [vp] * 15
+        lib.emloco_locoval_variant_bwd_rows.argtypes = [ci, ci, vp, ci] + [vp] * 17
+        lib.emloco_locoval_variant_bwd_workspace.argtypes = [ci, ci]
+        lib.emloco_locoval_variant_bwd_workspace.restype = C.c_int64
         lib.emloco_locoval_eval_step.argtypes = [C.POINTER(LocoValEval), vp, vp, vp, vp, vp, vp]
         lib.emloco_locoval_eval_finish.argtypes = [C.POINTER(LocoValEval), vp, vp, vp]
         lib.emloco_locoval_eval_reduce.argtypes = [ci, ci, vp, vp, vp, vp]
@@ -776,6 +783,69 @@ class LocoValFn(torch.autograd.Function):
         o = [0, 4900, 4949, 6125, 6149, 6173, 6174]
         g = [dparams[o[i]:o[i + 1]] for i in range(6)]
         return (dtraj, None, None, g[0].view(49, 100), g[1], g[2].view(24, 49), g[3], g[4].view(1, 24), g[5])
+
+
+LOCOVAL_TRAJ, LOCOVAL_VEL, LOCOVAL_POSE, LOCOVAL_FULL = 0, 1, 2, 3      # EMLOCO_LOCOVAL_*: (use_pose << 1) | use_vel
+
+
+def locoval_variant(use_pose, use_vel):
+    return (2 if use_pose else 0) | (1 if use_vel else 0)
+
+
+def locoval_dims(variant):
+    """(in, h1, h2, n_param) of a LocoVal variant (value_pose_net.py:43-52); what emloco_locoval_variant_dims answers."""
+    if variant not in (0, 1, 2, 3):
+        raise ValueError(f"LocoVal variant {variant!r}: expected (use_pose << 1) | use_vel in 0..3")
+    n_in = 26 + (72 if variant & 2 else 0) + (2 if variant & 1 else 0)
+    h1 = n_in // 2 - 1
+    h2 = h1 // 2
+    return n_in, h1, h2, h1 * n_in + h1 + h2 * h1 + h2 + h2 + 1
+
+
+class LocoValVariantFn(torch.autograd.Function):
+    """LocoValFn for the reduced-input networks (pose / vel / traj): the same fused forward / backward through the variant entry points.
+    `pose` / `vel` may be None where the variant does not read them; with `want_pose_rot` (variants without the pose) the third result
+    is the pose rotated by each sample's yaw, which the reference leaves in the caller's tensor (value_pose_net.py:96-97)."""
+
+    @staticmethod
+    def forward(ctx, variant, traj, pose, vel, w1, b1, w2, b2, w3, b3, want_pose_rot=False):
+        n_in, n_h1, n_h2, _ = locoval_dims(variant)
+        B, ts, dev = traj.shape[0], traj.shape[-1], traj.device
+        traj_c = traj.contiguous().float()
+        pose_c = pose.contiguous().float() if pose is not None and (variant & 2 or want_pose_rot) else None
+        vel_c = vel.contiguous().float() if vel is not None and variant & 1 else None
+        value, ang = torch.empty(B, device=dev), torch.empty(B, device=dev)
+        x, h1, h2 = torch.empty(B, n_in, device=dev), torch.empty(B, n_h1, device=dev), torch.empty(B, n_h2, device=dev)
+        pose_rot = torch.empty(B, 24, 3, device=dev) if want_pose_rot else None
+        ps = [t.contiguous() for t in (w1, b1, w2, b2, w3, b3)]
+        _chk(_lib().emloco_locoval_variant_fwd(variant, B, _p(traj_c), ts, _p(pose_c), _p(vel_c), *[_p(t) for t in ps], _p(value), _p(x), _p(h1),
+                                               _p(h2), _p(ang), _p(pose_rot), _st(traj)), "emloco_locoval_variant_fwd")
+        ctx.variant = variant
+        ctx.has_pose, ctx.has_vel = bool(variant & 2), bool(variant & 1)          # what the backward reads
+        keep = [traj_c, ps[0], ps[2], ps[4], value, x, h1, h2, ang] + ([pose_c] if ctx.has_pose else []) + ([vel_c] if ctx.has_vel else [])
+        ctx.save_for_backward(*keep)
+        if pose_rot is None:
+            pose_rot = torch.empty(0, device=dev)
+        ctx.mark_non_differentiable(x, pose_rot)
+        return value.view(B, 1), x, pose_rot
+
+    @staticmethod
+    def backward(ctx, dvalue, _dx, _dpose_rot):
+        traj, w1, w2, w3, value, x, h1, h2, ang, *rest = ctx.saved_tensors
+        pose = rest.pop(0) if ctx.has_pose else None
+        vel = rest.pop(0) if ctx.has_vel else None
+        variant = ctx.variant
+        n_in, n_h1, n_h2, n_param = locoval_dims(variant)
+        B, ts, dev = traj.shape[0], traj.shape[-1], traj.device
+        dparams = torch.empty(n_param, device=dev)
+        dtraj = torch.empty_like(traj)
+        ws = torch.empty(B * n_param, device=dev)
+        dv = dvalue.contiguous().view(B).float()
+        _chk(_lib().emloco_locoval_variant_bwd(variant, B, _p(traj), ts, _p(pose), _p(vel), _p(w1), _p(w2), _p(w3), _p(value), _p(x), _p(h1), _p(h2),
+                                               _p(ang), _p(dv), _p(dparams), _p(dtraj), _p(ws), _st(traj)), "emloco_locoval_variant_bwd")
+        sizes = [n_h1 * n_in, n_h1, n_h2 * n_h1, n_h2, n_h2, 1]
+        g = torch.split(dparams, sizes)
+        return (None, dtraj, None, None, g[0].view(n_h1, n_in), g[1], g[2].view(n_h2, n_h1), g[3], g[4].view(1, n_h2), g[5], None)
 
 
 def gemm_timing(enable=None):

@@ -193,8 +193,20 @@ def _run_test(args, env, policy_ckpt, games_num, max_steps, eval_out, eval_recor
     player = config.get("player", {})
     task = env.env.task
     bundle = AMPPolicyBundle(task, cfg_train=cfg_train, checkpoint=policy_ckpt, deterministic=bool(player.get("deterministic", True)))
-    valuenet = ValuePoseNet(use_pose=True, use_vel=True).to(task.device)
-    valuenet.load_state_dict(torch.load(args.valuenet_path, map_location=task.device))     # amp_value_players.py:301
+    state = torch.load(args.valuenet_path, map_location=task.device)
+    use_pose, use_vel = bool(args.input_init_pose), bool(args.input_init_vel)          # amp_value_players.py:294-301 (player.use_pose / use_vel)
+    fc1 = state.get("_network.fc1.weight") if hasattr(state, "get") else None
+    if not (use_pose or use_vel) and fc1 is not None and fc1.dim() == 2 and int(fc1.shape[1]) in (100, 98, 28):
+        # neither flag given: a checkpoint with pose / velocity inputs is evaluated as what it is (as before the flags were wired),
+        # an explicit flag that contradicts the checkpoint is an error below
+        use_pose, use_vel = int(fc1.shape[1]) >= 98, int(fc1.shape[1]) in (100, 28)
+        say(f"--valuenet_path holds a network with {int(fc1.shape[1])} inputs: evaluating it with use_pose={use_pose} use_vel={use_vel}")
+    valuenet = ValuePoseNet(use_pose=use_pose, use_vel=use_vel).to(task.device)
+    try:
+        valuenet.load_state_dict(state)
+    except RuntimeError as e:
+        raise SystemExit(f"run.py --test: --valuenet_path {args.valuenet_path} does not fit --input_init_pose={use_pose} "
+                         f"--input_init_vel={use_vel}: {e}")
     valuenet.eval()
     ev = LocoValEvaluator(env, bundle, valuenet, int(games_num) if games_num else int(player.get("games_num", 200)),
                           max_steps=int(max_steps) if max_steps else 27000, gamma=float(config.get("gamma", 0.99)))

@@ -266,6 +266,42 @@ int emloco_locoval_bwd(int B, const float *traj, int traj_stride, const float *p
 /* bytes of workspace emloco_locoval_bwd needs for batch B */
 int64_t emloco_locoval_bwd_workspace(int B);
 
+/* The four input configurations of the network (value_pose_net.py:22-50, the paper's input ablation; run.py --input_init_pose /
+ * --input_init_vel, train_jta.py --not_pose / --not_vel, evaluate_jta.py --no_pose / --no_vel):  variant = (use_pose << 1) | use_vel.
+ * Sizes as value_pose_net.py:43-52 (h1 = in / 2 - 1, h2 = h1 / 2):
+ *     variant   in   h1   h2   parameters     input vector x
+ *     FULL     100   49   24      6 174       [traj 26 | pose 72 | vel 2]
+ *     POSE      98   48   24      5 953       [traj 26 | pose 72]
+ *     VEL       28   13    6        468       [traj 26 | vel 2]
+ *     TRAJ      26   12    6        409       [traj 26]
+ * The yaw comes from waypoint 1 with the epsilon guard (:76-84) and rotates trajectory, pose and velocity (:92-100) in every variant;
+ * the hidden joints are zeroed only where the pose is an input (:116-127 against :110-114,129-135). */
+#define EMLOCO_LOCOVAL_TRAJ 0
+#define EMLOCO_LOCOVAL_VEL 1
+#define EMLOCO_LOCOVAL_POSE 2
+#define EMLOCO_LOCOVAL_FULL 3
+/* dims4 = {in, h1, h2, number of parameters} of a variant (value_pose_net.py:43-52) */
+int emloco_locoval_variant_dims(int variant, int32_t *dims4);
+/* emloco_locoval_fwd / _fwd_rows for any variant (net_forward of :22-33): x [B][in], h1 [B][h1], h2 [B][h2].  An input the variant does
+ * not read may be NULL.  pose_rot (optional, [B][24][3], variants without the pose only): the pose rotated by the sample's yaw -- what
+ * _rotate_normalization leaves in the caller's tensor (:96-97), no joint zeroed; the variants that read the pose have it in x[26:98].
+ * EMLOCO_LOCOVAL_FULL runs the kernels of emloco_locoval_fwd: the same bits. */
+int emloco_locoval_variant_fwd(int variant, int B, const float *traj, int traj_stride, const float *pose, const float *vel,
+                               const float *w1, const float *b1, const float *w2, const float *b2, const float *w3, const float *b3,
+                               float *value, float *x, float *h1, float *h2, float *angle, float *pose_rot, void *stream);
+int emloco_locoval_variant_fwd_rows(int variant, int B, const float *traj, int traj_stride, const float *pose, const float *vel,
+                                    const float *w1, const float *b1, const float *w2, const float *b2, const float *w3, const float *b3,
+                                    float *value, float *x, float *h1, float *h2, float *angle, float *pose_rot,
+                                    const float *row_weight, void *stream);
+/* emloco_locoval_bwd for any variant: dparams = [dw1 h1*in | db1 h1 | dw2 h2*h1 | db2 h2 | dw3 h2 | db3 1], summed over the batch in
+ * the same fixed order; d traj through the rotation and through the angle, without the terms of the inputs the variant lacks. */
+int emloco_locoval_variant_bwd(int variant, int B, const float *traj, int traj_stride, const float *pose, const float *vel,
+                               const float *w1, const float *w2, const float *w3,
+                               const float *value, const float *x, const float *h1, const float *h2, const float *angle,
+                               const float *dvalue, float *dparams, float *dtraj, float *workspace, void *stream);
+/* bytes of workspace emloco_locoval_variant_bwd / _bwd_rows need for batch B (-1: bad argument) */
+int64_t emloco_locoval_variant_bwd_workspace(int variant, int B);
+
 /* ------------------------------------------------------------------------------------------------------------
  * LocoVal training step around the MLP: the per-step body of AMPValueAgent.play_steps after env.step
  * (pacer/pacer/learning/amp_continuous_value.py:63-145; optimiser / normalisation common_agent.py:89-97,154-155), as three small
@@ -312,6 +348,13 @@ int emloco_locoval_bwd_rows(int B, const float *traj, int traj_stride, const flo
                             const float *value, const float *x100, const float *h1, const float *h2, const float *angle,
                             const float *dvalue, const int32_t *slot, const float *count, float *dparams, float *dtraj,
                             float *workspace, void *stream);
+/* emloco_locoval_bwd_rows for any variant (amp_continuous_value.py:137-139 on the network of value_pose_net.py:22-50): one
+ * n_param-float workspace row per slot */
+int emloco_locoval_variant_bwd_rows(int variant, int B, const float *traj, int traj_stride, const float *pose, const float *vel,
+                                    const float *w1, const float *w2, const float *w3,
+                                    const float *value, const float *x, const float *h1, const float *h2, const float *angle,
+                                    const float *dvalue, const int32_t *slot, const float *count, float *dparams, float *dtraj,
+                                    float *workspace, void *stream);
 /* tail2 = [loss sum, row count] after the all-reduce (NULL: always step); steps_in / steps_out: device step counters (the caller
  * swaps them after every call); stats: optional device double[5] = [last loss, last count, total loss, total count, fits] */
 int emloco_adamw_gated(int n, float *params, const float *grads, float *exp_avg, float *exp_avg_sq, const float *steps_in,
