@@ -6,6 +6,8 @@ point that needs the device raises `EmlocoError`.  Build the library with `pytho
 import ctypes as C
 import os
 
+from ._abi import EmlocoError, bind  # noqa: F401  (EmlocoError is raised under this module's name everywhere)
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EMLOCO_LIB") or os.path.join(HERE, "lib", "libemloco_hip.so")     # (EMLOCO_LIB: another build of the library, for A/B runs)
 
@@ -20,10 +22,6 @@ POST_ADVANCE, POST_OBS, POST_REWARD, POST_RESET, POST_AMP_SHIFT, POST_AMP_ROW = 
 POST_STEP = 63
 POST_SKIP_DONE = 64
 POST_AMP_DONE_ONLY = 128
-
-
-class EmlocoError(RuntimeError):
-    pass
 
 
 class SimParams(C.Structure):
@@ -130,6 +128,26 @@ class ResetPool(C.Structure):   # EmlocoResetPool
                 ("next_seed", C.c_uint64)]
 
 
+class LocoValStep(C.Structure):
+    """EmlocoLocoValStep (include/emloco_predictor.h)."""
+    _fields_ = [("n_env", C.c_int32), ("step_to_pred", C.c_int32), ("gamma", C.c_float), ("inversion_penalty", C.c_float),
+                ("min_cum_rewards", C.c_float), ("max_cum_rewards", C.c_float),
+                ("current_rewards", C.c_void_p), ("current_lengths", C.c_void_p), ("current_combined_rewards", C.c_void_p),
+                ("discount_coefs", C.c_void_p), ("waypoint_traj", C.c_void_p), ("init_pose", C.c_void_p), ("init_vel", C.c_void_p),
+                ("traj13", C.c_void_p), ("pose", C.c_void_p), ("vel", C.c_void_p), ("target", C.c_void_p), ("weight", C.c_void_p),
+                ("staged_reward", C.c_void_p), ("staged_done", C.c_void_p)]          # staged mode (both NULL: off)
+
+
+class LocoValEval(C.Structure):
+    """EmlocoLocoValEval (include/emloco_predictor.h): the per-env game state of the LocoVal evaluation (`run.py --test`)."""
+    _fields_ = [("n_env", C.c_int32), ("step_to_pred", C.c_int32), ("games_per_env", C.c_int32), ("_pad", C.c_int32),
+                ("gamma", C.c_double), ("coef", C.c_void_p), ("c_disc", C.c_void_p), ("tp_disc", C.c_void_p),
+                ("cr", C.c_void_p), ("c_loc", C.c_void_p), ("c_pow", C.c_void_p), ("tp_cr", C.c_void_p), ("tp_loc", C.c_void_p),
+                ("tp_pow", C.c_void_p), ("steps", C.c_void_p), ("games", C.c_void_p), ("done", C.c_void_p), ("terminated", C.c_void_p),
+                ("inverted", C.c_void_p), ("n_full", C.c_void_p), ("waypoint_traj", C.c_void_p), ("init_pose", C.c_void_p),
+                ("init_vel", C.c_void_p), ("traj13", C.c_void_p), ("pose", C.c_void_p), ("vel", C.c_void_p), ("row_mask", C.c_void_p)]
+
+
 def default_sim_params(**kw):
     """Engine parameters of pacer.yaml:93-104 / config.py:143-163 mapped onto EmlocoSimParams."""
     p = dict(n_sub=2, n_iter=4, h=(1.0 / 60.0) / 2, gravity_z=-9.81, contact_offset=0.02, erp=0.2,
@@ -137,21 +155,6 @@ def default_sim_params(**kw):
     p.update(kw)
     return SimParams(**p)
 
-
-# every symbol the headers declare; checked at load time
-SYMBOLS_SIM = [
-    "emloco_last_error", "emloco_device_count", "emloco_sim_create", "emloco_sim_destroy", "emloco_sim_set_models",
-    "emloco_sim_set_self_collision", "emloco_sim_set_ground_heightfield", "emloco_sim_set_ground_mesh_moves",
-    "emloco_sim_prepare", "emloco_sim_get_params", "emloco_sim_set_params", "emloco_sim_tensor",
-    "emloco_sim_set_pd_targets", "emloco_sim_set_dof_actuation_force", "emloco_sim_step", "emloco_sim_step_subset", "emloco_sim_set_cost_order", "emloco_sim_set_split", "emloco_sim_sync", "emloco_sim_set_root_state_indexed",
-    "emloco_sim_set_dof_state_indexed", "emloco_sim_refresh_bodies", "emloco_sim_num_candidates",
-    "emloco_sim_last_step_ms", "emloco_sim_enable_timing", "emloco_sim_timing_stats",
-]
-SYMBOLS_TASK = [
-    "emloco_task_post_physics", "emloco_task_amp_rows", "emloco_task_pd_targets", "emloco_task_last_ms",
-    "emloco_task_enable_timing", "emloco_task_reset", "emloco_task_reset_seeded", "emloco_task_compact_done", "emloco_task_compact_done_snapshot", "emloco_task_reset_amp_history",
-    "emloco_task_traj_reset", "emloco_task_get_heights", "emloco_task_pd_targets_copy", "emloco_task_compact_done_order", "emloco_task_reset_obs", "emloco_task_reset_obs_pooled", "emloco_task_post_physics_returns",
-]
 
 _lib = None
 
@@ -167,55 +170,8 @@ def load():
     if not os.path.exists(LIB_PATH):
         raise EmlocoError(f"{LIB_PATH} is missing: run `python -m emloco_amd.build` (hipcc, gfx950). "
                           "There is no CPU fallback.")
-    lib = C.CDLL(LIB_PATH)
-    for name in SYMBOLS_SIM + SYMBOLS_TASK:
-        if not hasattr(lib, name):
-            raise EmlocoError(f"libemloco_hip.so does not export {name}")
-    lib.emloco_last_error.restype = C.c_char_p
-    lib.emloco_sim_last_step_ms.restype = C.c_float
-    lib.emloco_task_last_ms.restype = C.c_float
-    lib.emloco_sim_create.argtypes = [C.POINTER(SimParams), C.c_int, C.POINTER(C.c_void_p)]
-    lib.emloco_sim_destroy.argtypes = [C.c_void_p]
-    lib.emloco_sim_set_models.argtypes = [C.c_void_p, C.POINTER(ModelDesc)]
-    lib.emloco_sim_prepare.argtypes = [C.c_void_p]
-    lib.emloco_sim_get_params.argtypes = [C.c_void_p, C.POINTER(SimParams)]
-    lib.emloco_sim_set_params.argtypes = [C.c_void_p, C.POINTER(SimParams)]
-    lib.emloco_sim_tensor.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
-    lib.emloco_sim_set_pd_targets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.emloco_sim_set_dof_actuation_force.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.emloco_sim_step.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    lib.emloco_sim_set_cost_order.argtypes = [C.c_void_p, C.c_int]
-    lib.emloco_sim_set_split.argtypes = [C.c_void_p, C.c_int]
-    lib.emloco_sim_step_subset.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    lib.emloco_sim_sync.argtypes = [C.c_void_p, C.c_void_p]
-    lib.emloco_sim_set_root_state_indexed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    lib.emloco_sim_set_dof_state_indexed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    lib.emloco_sim_refresh_bodies.argtypes = [C.c_void_p, C.c_void_p]
-    lib.emloco_sim_num_candidates.argtypes = [C.c_void_p]
-    lib.emloco_sim_last_step_ms.argtypes = [C.c_void_p]
-    lib.emloco_sim_enable_timing.argtypes = [C.c_void_p, C.c_int]
-    lib.emloco_sim_timing_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float)]
-    lib.emloco_task_post_physics.argtypes = [C.POINTER(TaskBufs), C.c_int, C.c_void_p, C.c_int, C.c_void_p]
-    lib.emloco_task_post_physics_returns.argtypes = [C.POINTER(TaskBufs), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.emloco_task_amp_rows.argtypes = [C.c_int] + [C.c_void_p] * 9 + [C.c_int, C.c_void_p, C.c_void_p]
-    lib.emloco_task_pd_targets.argtypes = [C.c_int] + [C.c_void_p] * 5 + [C.c_void_p]
-    lib.emloco_task_enable_timing.argtypes = [C.c_int]
-    lib.emloco_task_reset.argtypes = [C.c_void_p, C.POINTER(ResetBufs), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    lib.emloco_task_reset_seeded.argtypes = [C.c_void_p, C.POINTER(ResetBufs), C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p]
-    lib.emloco_task_traj_reset.argtypes = [C.POINTER(ResetBufs), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.emloco_task_get_heights.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_int,
-                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.emloco_task_compact_done.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    lib.emloco_task_compact_done_snapshot.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.emloco_task_reset_amp_history.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    lib.emloco_task_pd_targets_copy.argtypes = [C.c_int] + [C.c_void_p] * 5 + [C.c_void_p, C.c_void_p]
-    lib.emloco_task_compact_done_order.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.emloco_task_reset_obs_pooled.argtypes = [C.c_void_p, C.POINTER(ResetBufs), C.POINTER(TaskBufs), C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                                                 C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(ResetPool), C.c_void_p]
-    lib.emloco_task_reset_obs.argtypes = [C.c_void_p, C.POINTER(ResetBufs), C.POINTER(TaskBufs), C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                                          C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
-    _lib = lib
-    return lib
+    _lib = bind(C.CDLL(LIB_PATH))         # every prototype of include/*.h, typed (_abi.py)
+    return _lib
 
 
 def check(rc, what=""):

@@ -12,23 +12,7 @@ import torch
 
 from ..predictor import ops
 
-_BOUND = False
-
-
-def _lib():
-    global _BOUND
-    lib = ops._lib()
-    if not _BOUND:
-        vp, cf, ci = C.c_void_p, C.c_float, C.c_int
-        lib.emloco_ppo_actor_head_fwd.argtypes = [ci, ci] + [vp] * 7 + [cf, vp, vp, vp]
-        lib.emloco_ppo_actor_head_bwd.argtypes = [ci, ci] + [vp] * 5 + [cf, vp, vp, vp, vp]
-        lib.emloco_ppo_critic_head_fwd.argtypes = [ci, vp, vp, vp, cf, ci, vp, vp, vp]
-        lib.emloco_ppo_critic_head_bwd.argtypes = [ci, vp, vp, vp, cf, ci, vp, vp, vp]
-        lib.emloco_ppo_disc_head_fwd.argtypes = [ci, ci, vp, vp, vp, vp, vp]
-        lib.emloco_ppo_disc_head_bwd.argtypes = [ci, ci, vp, vp, vp, vp, vp, vp]
-        lib.emloco_ppo_gather_rows.argtypes = [ci, ci, vp, vp, vp, vp, vp]
-        _BOUND = True
-    return lib
+_lib = ops._lib
 
 
 def gather_rows(idx, srcs, dsts):

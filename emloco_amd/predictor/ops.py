@@ -9,110 +9,15 @@ import os
 import torch
 
 from .. import _lib as L
+from .._lib import LocoValEval, LocoValStep  # noqa: F401  (re-exported: callers say ops.LocoValStep)
 from ..sim import current_stream_handle
 
 GEMM_BIAS, GEMM_RELU, GEMM_ACC, GEMM_DROPOUT = 1, 2, 4, 8
-_bound = False
-
-
-class LocoValStep(C.Structure):
-    """EmlocoLocoValStep (include/emloco_predictor.h)."""
-    _fields_ = [("n_env", C.c_int32), ("step_to_pred", C.c_int32), ("gamma", C.c_float), ("inversion_penalty", C.c_float),
-                ("min_cum_rewards", C.c_float), ("max_cum_rewards", C.c_float),
-                ("current_rewards", C.c_void_p), ("current_lengths", C.c_void_p), ("current_combined_rewards", C.c_void_p),
-                ("discount_coefs", C.c_void_p), ("waypoint_traj", C.c_void_p), ("init_pose", C.c_void_p), ("init_vel", C.c_void_p),
-                ("traj13", C.c_void_p), ("pose", C.c_void_p), ("vel", C.c_void_p), ("target", C.c_void_p), ("weight", C.c_void_p),
-                ("staged_reward", C.c_void_p), ("staged_done", C.c_void_p)]          # staged mode (both NULL: off)
-
-
-class LocoValEval(C.Structure):
-    """EmlocoLocoValEval (include/emloco_predictor.h): the per-env game state of the LocoVal evaluation (`run.py --test`)."""
-    _fields_ = [("n_env", C.c_int32), ("step_to_pred", C.c_int32), ("games_per_env", C.c_int32), ("_pad", C.c_int32),
-                ("gamma", C.c_double), ("coef", C.c_void_p), ("c_disc", C.c_void_p), ("tp_disc", C.c_void_p),
-                ("cr", C.c_void_p), ("c_loc", C.c_void_p), ("c_pow", C.c_void_p), ("tp_cr", C.c_void_p), ("tp_loc", C.c_void_p),
-                ("tp_pow", C.c_void_p), ("steps", C.c_void_p), ("games", C.c_void_p), ("done", C.c_void_p), ("terminated", C.c_void_p),
-                ("inverted", C.c_void_p), ("n_full", C.c_void_p), ("waypoint_traj", C.c_void_p), ("init_pose", C.c_void_p),
-                ("init_vel", C.c_void_p), ("traj13", C.c_void_p), ("pose", C.c_void_p), ("vel", C.c_void_p), ("row_mask", C.c_void_p)]
-
-
 EVAL_MOMENTS = 20          # EMLOCO_EVAL_MOMENTS
 
 
 def _lib():
-    global _bound
-    lib = L.require_device()
-    if not _bound:
-        vp, ci, cf, cl = C.c_void_p, C.c_int, C.c_float, C.c_int64
-        lib.emloco_gemm_f32.argtypes = [ci, ci, ci, ci, cf, vp, ci, cl, ci, vp, ci, cl, ci, vp, ci, cl, vp, ci, ci, vp, vp]
-        lib.emloco_gemm_f32_ex.argtypes = [ci, ci, ci, ci, cf, vp, ci, cl, ci, vp, ci, cl, ci, vp, ci, cl, vp, ci, ci, vp, cf, C.c_uint32, vp]
-        lib.emloco_act_bwd.argtypes = [cl, vp, vp, ci, cf, C.c_uint32, vp, vp]
-        lib.emloco_act_bwd_colsum.argtypes = [ci, ci, vp, vp, ci, cf, C.c_uint32, vp, vp, vp, vp]
-        lib.emloco_softmax_fwd.argtypes = [ci, ci, ci, cf, vp, vp, vp, vp]
-        lib.emloco_softmax_bwd.argtypes = [ci, ci, cf, vp, vp, vp, vp]
-        lib.emloco_layernorm_fwd.argtypes = [ci, ci, cf, vp, vp, vp, vp, vp, vp, vp, vp]
-        lib.emloco_layernorm_fwd_save.argtypes = [ci, ci, cf, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        lib.emloco_layernorm_bwd.argtypes = [ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        lib.emloco_layernorm_bwd2.argtypes = [ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        lib.emloco_colsum.argtypes = [ci, ci, vp, vp, vp, vp]
-        lib.emloco_colsum_ex.argtypes = [ci, ci, vp, vp, vp, ci, vp]
-        lib.emloco_attention_fwd.argtypes = [ci, ci, ci, ci, cf, vp, vp, vp, vp, vp]
-        lib.emloco_attention_bwd.argtypes = [ci, ci, ci, ci, cf, vp, vp, vp, vp, vp, vp, vp, vp]
-        lib.emloco_attention_fwd_ex.argtypes = [ci, ci, ci, ci, cf, vp, vp, vp, vp, ci, vp]
-        lib.emloco_attention_bwd_ex.argtypes = [ci, ci, ci, ci, cf, vp, vp, vp, vp, vp, vp, vp, ci, vp]
-        lib.emloco_gemm_relu_bwd_workspace.argtypes = [ci, ci]
-        lib.emloco_gemm_relu_bwd_workspace.restype = C.c_int64
-        lib.emloco_gemm_relu_bwd.argtypes = [ci, ci, ci, vp, ci, vp, ci, ci, vp, vp, cf, vp, vp, ci, vp]
-        lib.emloco_attention_fwd_queries.argtypes = [ci, ci, ci, ci, ci, cf, vp, vp, vp, vp, ci, cf, C.c_uint32, vp]
-        lib.emloco_attention_bwd_queries.argtypes = [ci, ci, ci, ci, ci, cf, vp, vp, vp, vp, vp, vp, vp, ci, cf, C.c_uint32, vp]
-        lib.emloco_attention_keep_mask.argtypes = [C.c_uint32, ci, ci, cf, vp]
-        lib.emloco_dropout_keep_mask.argtypes = [C.c_uint32, C.c_uint64, C.c_int64, cf, vp]
-        lib.emloco_attention_fwd_dropout.argtypes = [ci, ci, ci, ci, cf, vp, vp, vp, vp, ci, cf, C.c_uint32, vp]
-        lib.emloco_attention_bwd_dropout.argtypes = [ci, ci, ci, ci, cf, vp, vp, vp, vp, vp, vp, vp, ci, cf, C.c_uint32, vp]
-        lib.emloco_colsum_workspace.argtypes = [ci, ci]
-        lib.emloco_colsum_workspace.restype = C.c_int64
-        lib.emloco_layernorm_bwd_workspace.argtypes = [ci, ci]
-        lib.emloco_layernorm_bwd_workspace.restype = C.c_int64
-        lib.emloco_locoval_fwd.argtypes = [ci, vp, ci] + [vp] * 14
-        lib.emloco_locoval_fwd_rows.argtypes = [ci, vp, ci] + [vp] * 15
-        lib.emloco_locoval_bwd.argtypes = [ci, vp, ci] + [vp] * 15
-        lib.emloco_locoval_bwd_workspace.argtypes = [ci]
-        lib.emloco_locoval_bwd_workspace.restype = C.c_int64
-        lib.emloco_locoval_returns.argtypes = [C.POINTER(LocoValStep), vp, vp, vp, vp, vp]
-        lib.emloco_locoval_returns_finish.argtypes = [C.POINTER(LocoValStep), vp, vp]
-        lib.emloco_locoval_fit_grad.argtypes = [ci, vp, vp, vp, vp, vp, vp, vp]
-        lib.emloco_locoval_bwd_rows.argtypes = [ci, vp, ci] + [vp] * 17
-        lib.emloco_locoval_variant_dims.argtypes = [ci, vp]
-        lib.emloco_locoval_variant_fwd.argtypes = [ci, ci, vp, ci] + [vp] * 15
-        lib.emloco_locoval_variant_fwd_rows.argtypes = [ci, ci, vp, ci] + [vp] * 16
-        lib.emloco_locoval_variant_bwd.argtypes = [ci, ci, vp, ci] + [vp] * 15
-        lib.emloco_locoval_variant_bwd_rows.argtypes = [ci, ci, vp, ci] + [vp] * 17
-        lib.emloco_locoval_variant_bwd_workspace.argtypes = [ci, ci]
-        lib.emloco_locoval_variant_bwd_workspace.restype = C.c_int64
-        lib.emloco_locoval_eval_step.argtypes = [C.POINTER(LocoValEval), vp, vp, vp, vp, vp, vp]
-        lib.emloco_locoval_eval_finish.argtypes = [C.POINTER(LocoValEval), vp, vp, vp]
-        lib.emloco_locoval_eval_reduce.argtypes = [ci, ci, vp, vp, vp, vp]
-        lib.emloco_adamw_gated.argtypes = [ci] + [vp] * 7 + [cf] * 5 + [vp, vp]
-        lib.emloco_adam_clip_flat.argtypes = [C.c_int64] + [vp] * 4 + [cf, C.c_double, C.c_double] + [cf] * 5 + [vp, vp]
-        lib.emloco_adam_clip_flat_counted.argtypes = [C.c_int64] + [vp] * 4 + [cf, C.c_double, C.c_double] + [cf] * 3 + [vp, vp, vp]
-        lib.emloco_gather_flat.argtypes = [ci, vp, vp, vp, vp, vp]
-        lib.emloco_adam_clip_flat_workspace.argtypes = [C.c_int64]
-        lib.emloco_gemm_split_image_words.argtypes = [C.c_int, C.c_int]
-        lib.emloco_gemm_split_image_words.restype = C.c_int64
-        lib.emloco_gemm_split_pack.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
-        lib.emloco_adam_clip_flat_workspace.restype = C.c_int64
-        lib.emloco_gemm_enable_timing.argtypes = [ci]
-        lib.emloco_ffn_fwd.argtypes = [ci, ci] + [vp] * 8 + [cf, C.c_uint32, C.c_uint32, vp]
-        lib.emloco_ffn_bwd_input.argtypes = [ci, ci] + [vp] * 6 + [cf, vp]
-        lib.emloco_ffn_bwd_input_colsum.argtypes = [ci, ci] + [vp] * 6 + [cf, vp, vp]
-        lib.emloco_ffn_fwd_norm.argtypes = [ci, ci] + [vp] * 10 + [cf] + [vp] * 4 + [cf, C.c_uint32, C.c_uint32, vp]
-        lib.emloco_ffn_bwd_colsum_rows.argtypes = [ci]
-        lib.emloco_ffn_bwd_colsum_rows.restype = C.c_int64
-        lib.emloco_ffn_keep_mask.argtypes = [C.c_uint32, cl, cl, ci, cf, vp]
-        lib.emloco_disc_reward.argtypes = [ci, vp, cf, vp, vp]
-        lib.emloco_gemm_timing_stats.argtypes = [C.POINTER(ci), C.POINTER(cf), C.POINTER(C.c_double)]
-        lib.emloco_gemm_timing_bytes.argtypes = [C.POINTER(C.c_double)]
-        _bound = True
-    return lib
+    return L.require_device()
 
 
 def _p(t, offset=0):

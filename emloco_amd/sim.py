@@ -83,14 +83,11 @@ class NativeSim:
                                       f(sc["cap_b"]), f(sc["cap_r"]), float(sc["k"]), float(sc["c"]), float(sc["max_pen"]), float(sc.get("mu", 1.0)),
                                       int(sc["seg_body"].shape[0]) if sc.get("seg_body") is not None else 0,
                                       sc["seg_body"].ctypes.data_as(C.POINTER(C.c_uint8)) if sc.get("seg_body") is not None else None)
-            lib.emloco_sim_set_self_collision.argtypes = [C.c_void_p, C.POINTER(L.SelfCollisionDesc)]
             L.check(lib.emloco_sim_set_self_collision(self._h, C.byref(scd)), "emloco_sim_set_self_collision")
         if heightfield is not None:
             hf = np.ascontiguousarray(heightfield["samples"], dtype=np.int16)
             if hf.ndim != 2:
                 raise L.EmlocoError("heightfield samples must be a 2-D int16 array [nx][ny]")
-            lib.emloco_sim_set_ground_heightfield.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float,
-                                                              C.c_float, C.c_float]
             L.check(lib.emloco_sim_set_ground_heightfield(
                 self._h, hf.ctypes.data, hf.shape[0], hf.shape[1], float(heightfield["horizontal_scale"]),
                 float(heightfield["vertical_scale"]), float(heightfield.get("origin_x", 0.0)),
@@ -100,7 +97,6 @@ class NativeSim:
                 my = np.ascontiguousarray(heightfield["move_y"], dtype=np.int8)
                 if mx.shape != hf.shape or my.shape != hf.shape:
                     raise L.EmlocoError("heightfield move_x / move_y must have the samples' shape")
-                lib.emloco_sim_set_ground_mesh_moves.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
                 L.check(lib.emloco_sim_set_ground_mesh_moves(self._h, mx.ctypes.data, my.ctypes.data), "emloco_sim_set_ground_mesh_moves")
         L.check(lib.emloco_sim_prepare(self._h), "emloco_sim_prepare")
         self.root_state = self._tensor(L.T_ROOT_STATE)

@@ -5,6 +5,8 @@ import subprocess
 
 import numpy as np
 
+from emloco_amd._lib import ModelDesc, SelfCollisionDesc
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(os.path.dirname(_HERE))
 _EXTRA = os.environ.get("EMLOCO_EMU_EXTRA", "").split()          # e.g. -DEMLOCO_SIM_PAIR=1: the experimental two-envs-per-wave rigid-body kernel
@@ -48,25 +50,11 @@ def _p(a, t=C.c_float):
     return a.ctypes.data_as(C.POINTER(t))
 
 
-class ModelDesc(C.Structure):
-    _fields_ = [("n_env", C.c_int32), ("parent", C.POINTER(C.c_int32)), ("geom_type", C.POINTER(C.c_int32)),
-                ("joint_off", C.POINTER(C.c_float)), ("mass", C.POINTER(C.c_float)), ("com", C.POINTER(C.c_float)),
-                ("inertia", C.POINTER(C.c_float)), ("geom_a", C.POINTER(C.c_float)), ("geom_b", C.POINTER(C.c_float)),
-                ("geom_r", C.POINTER(C.c_float)), ("kp", C.POINTER(C.c_float)), ("kd", C.POINTER(C.c_float)),
-                ("armature", C.POINTER(C.c_float)), ("effort", C.POINTER(C.c_float))]
-
-
 def model_desc(arr):
     return ModelDesc(arr["mass"].shape[0], _p(arr["parent"], C.c_int32), _p(arr["geom_type"], C.c_int32),
                      _p(arr["joint_off"]), _p(arr["mass"]), _p(arr["com"]), _p(arr["inertia"]), _p(arr["geom_a"]),
                      _p(arr["geom_b"]), _p(arr["geom_r"]), _p(arr["kp"]), _p(arr["kd"]), _p(arr["armature"]),
                      _p(arr["effort"]))
-
-
-class SelfCollisionDesc(C.Structure):
-    _fields_ = [("n_pairs", C.c_int32), ("pairs", C.POINTER(C.c_uint8)), ("cap_a", C.POINTER(C.c_float)),
-                ("cap_b", C.POINTER(C.c_float)), ("cap_r", C.POINTER(C.c_float)), ("k", C.c_float), ("c", C.c_float),
-                ("max_pen", C.c_float), ("mu", C.c_float), ("n_seg", C.c_int32), ("seg_body", C.POINTER(C.c_uint8))]
 
 
 def sim_step(osim, n_calls=1, expect_error=None):

@@ -25,8 +25,11 @@ def test_library_exports_every_declared_symbol():
         assert len(names) >= 5
         for n in names:
             assert hasattr(lib, n), f"{n} declared in include/{header} but not exported"
-    assert set(_lib.SYMBOLS_SIM) <= set(_declared("emloco_sim.h"))
-    assert set(_lib.SYMBOLS_TASK) <= set(_declared("emloco_task.h"))
+    # what the binding gives types to is exactly the declared names (a CDLL keeps every function it was asked for), none declared twice
+    from emloco_amd import _abi
+    bound = {n for n in vars(_abi.bind(lib)) if n.startswith("emloco_")}
+    assert bound == {n for h in _abi.HEADERS for n in _declared(h)} == set(_abi.prototypes())
+    assert len(bound) == sum(len(_abi.parse(h)) for h in _abi.HEADERS)
     # ... and the other way round: nothing is exported behind the headers' back (round-4 review: four diagnostic exports were)
     import subprocess
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout

@@ -100,23 +100,7 @@ MARGIN = 8.0                            # device bar = MARGIN x the float32 refe
 
 def _lib():
     from emloco_amd.predictor import ops
-    from emloco_amd.learning import ppo_heads                                   # noqa: F401  (declares the PPO entry points' argument types)
-    lib = ops._lib()
-    ci, cf, vp, cd = C.c_int, C.c_float, C.c_void_p, C.c_double
-    lib.emloco_colsum_ex.argtypes = [ci, ci, vp, vp, vp, ci, vp]
-    lib.emloco_obs_normalize.argtypes = [ci, ci, vp, ci, vp, vp, cf, cf, ci, vp, ci, vp, ci, vp]
-    lib.emloco_rms_update.argtypes = [ci, ci, vp, ci, vp, vp, vp, vp, ci, vp]
-    lib.emloco_rms_update_chunked.argtypes = [ci, ci, vp, ci, vp, vp, vp, vp, ci, vp, vp]
-    lib.emloco_rms_update_workspace.argtypes = [ci, ci]
-    lib.emloco_rms_update_workspace.restype = C.c_int64
-    lib.emloco_ppo_actor_head_fwd.argtypes = [ci, ci] + [vp] * 7 + [cf, vp, vp, vp]
-    lib.emloco_ppo_actor_head_bwd.argtypes = [ci, ci] + [vp] * 5 + [cf, vp, vp, vp, vp]
-    lib.emloco_ppo_critic_head_fwd.argtypes = [ci, vp, vp, vp, cf, ci, vp, vp, vp]
-    lib.emloco_ppo_critic_head_bwd.argtypes = [ci, vp, vp, vp, cf, ci, vp, vp, vp]
-    lib.emloco_ppo_disc_head_fwd.argtypes = [ci, ci, vp, vp, vp, vp, vp]
-    lib.emloco_ppo_disc_head_bwd.argtypes = [ci, ci, vp, vp, vp, vp, vp, vp]
-    lib.emloco_ppo_gather_rows.argtypes = [ci, ci, vp, vp, vp, vp, vp]
-    return lib
+    return ops._lib()
 
 
 def _gen(seed):
@@ -1037,7 +1021,6 @@ def _ffn_case(lib, tab, M, F, seed, p, fails):
 def test_ffn_matrix_against_float64():
     """F = 64 (one chunk) .. 2048 (the limit, served), M over the wave and workgroup tails, with and without dropout"""
     lib = _lib()
-    lib.emloco_ffn_keep_mask.argtypes = [C.c_uint32, C.c_int64, C.c_int64, C.c_int, C.c_float, C.c_void_p]
     tab, fails = Table("ffn"), []
     for M, F, seed in FFN_CASES:
         for p in ((0.0, 0.1) if M in (33, 255, 257) else (0.0,)):

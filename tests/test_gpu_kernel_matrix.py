@@ -50,10 +50,7 @@ BAR_SPLIT2 = 3 * 2.0 ** -16             # two pieces: the three dropped piece pr
 
 def _lib():
     from emloco_amd.predictor import ops
-    lib = ops._lib()
-    lib.emloco_gemm_set_small_tile.argtypes = [C.c_int]
-    lib.emloco_colsum_ex.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    return lib
+    return ops._lib()
 
 
 def _ptr(t, off=0):
@@ -411,7 +408,6 @@ def test_gemm_piece_image_gives_the_same_bits_as_the_matrix():
     """EMLOCO_GEMM_B_SPLITIMG: B as its piece image, packed from either layout of the weight, on both tiles, with split k and an
     epilogue -- bit-equal to the launch on the matrix; with EMLOCO_GEMM_SPLIT2 the image (three pieces) wins: the three-piece bits"""
     lib = _lib()
-    lib.emloco_gemm_split_image_words.restype = C.c_int64
     for (m, n, k, ks, epi) in ((300, 129, 44, 1, 0), (129, 264, 257, 1, BIAS | RELU), (1, 33, 17, 1, 0), (65, 65, 300, 3, BIAS)):
         for trans in (0, 1):
             for tile in (0, 1):
@@ -517,7 +513,6 @@ def test_gemm_relu_bwd_is_the_masked_gemm_and_its_column_sums(m, n, k, tb, mode)
     flags = base | (C16 | MASK16 if hid16 else 0)
     Bp, ldbp, tbp = Bst, ldb, tb
     if mode == "split_img":
-        lib.emloco_gemm_split_image_words.restype = C.c_int64
         words = lib.emloco_gemm_split_image_words(n, k)
         Bp = torch.zeros(words, dtype=torch.int32, device=DEV)
         assert lib.emloco_gemm_split_pack(_ptr(Bst), n, k, ldb, tb, _ptr(Bp), _stream()) == 0

@@ -266,7 +266,6 @@ def test_split_launch_lost_handover_is_an_error_not_silent_corruption():
     gsim.sync()
     _compare(osim, gsim, E, what="before the poisoned launch")
     before = gsim.rigid_body_state.view(E, 24, 13)[5].clone()
-    gsim.lib.emloco_sim_debug_poison_part.argtypes = [L.C.c_void_p, L.C.c_int, L.C.c_int]
     L.check(gsim.lib.emloco_sim_debug_poison_part(gsim._h, 5, 1 << 14), "poison")
     osim.step(1)
     gsim.step(2)

@@ -19,7 +19,6 @@ models = varied_models(64, seed=11); models = [models[i % 64] for i in range(E)]
 sim = NativeSim(models, L.default_sim_params())
 sim.root_state[:, 2] = 0.93
 lib = L.load()
-lib.emloco_sim_profile.argtypes = [C.c_void_p, C.POINTER(C.c_longlong), C.c_int]
 buf = (C.c_longlong * 256)()
 lib.emloco_sim_profile(sim._h, buf, 256)          # first call allocates the stamp buffer
 for _ in range(40): sim.step(2)                    # settle onto the ground so contacts are active
