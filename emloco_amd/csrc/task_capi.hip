@@ -15,6 +15,9 @@ bool g_timing = false, g_pending = false;
 float g_last_ms = -1.0f;
 thread_local std::string g_terr;
 long long *g_chain_prof = nullptr;
+// an AMP row holds 12 root values, 6 per subset joint, the subset's velocities, 12 key-body values and 11 betas: 35 + 3 n_sub values,
+// which must fit EMLOCO_AMP_ROW (a wider row would run into the next row and past the last one)
+bool bad_dof_subset(int n_sub) { return n_sub < 0 || n_sub % 3 != 0 || 35 + 3 * n_sub > EMLOCO_AMP_ROW; }
 int tfail(int code, const char *what, hipError_t e = hipSuccess) {
     char buf[512];
     if (e != hipSuccess) snprintf(buf, sizeof(buf), "%s: %s", what, hipGetErrorString(e));
@@ -64,7 +67,7 @@ int emloco_task_post_physics(const EmlocoTaskBufs *b, int mode, const int32_t *d
     if ((mode & EMLOCO_POST_SKIP_DONE) && !b->reset_buf) return tfail(-1, "emloco_task_post_physics: SKIP_DONE needs reset_buf");
     if ((mode & EMLOCO_POST_RESET) && (!b->reset_buf || !b->terminate_buf || !b->contact_force || !b->contact_body_mask))
         return tfail(-1, "emloco_task_post_physics: reset buffers missing");
-    if ((mode & (EMLOCO_POST_AMP_ROW | EMLOCO_POST_AMP_SHIFT)) && (!b->amp_obs_buf || !b->dof_subset || !b->key_bodies || b->n_dof_subset > 64 || b->n_dof_subset % 3))
+    if ((mode & (EMLOCO_POST_AMP_ROW | EMLOCO_POST_AMP_SHIFT)) && (!b->amp_obs_buf || !b->dof_subset || !b->key_bodies || bad_dof_subset(b->n_dof_subset)))
         return tfail(-1, "emloco_task_post_physics: AMP buffers missing");
     const int count = dev_env_ids ? n : b->n_env;
     if (count < 0 || count > b->n_env) return tfail(-1, "emloco_task_post_physics: bad env count");
@@ -92,7 +95,7 @@ int emloco_task_post_physics_returns(const EmlocoTaskBufs *b, int mode, const vo
         return tfail(-1, "emloco_task_post_physics_returns: task buffers missing");
     if ((mode & EMLOCO_POST_OBS) && (!b->obs_buf || !b->flip_obs_buf || !b->heightfield || !b->betas || !b->left_to_right))
         return tfail(-1, "emloco_task_post_physics_returns: observation buffers missing");
-    if ((mode & (EMLOCO_POST_AMP_ROW | EMLOCO_POST_AMP_SHIFT)) && (!b->amp_obs_buf || !b->dof_subset || !b->key_bodies || !b->betas || b->n_dof_subset > 64 || b->n_dof_subset % 3))
+    if ((mode & (EMLOCO_POST_AMP_ROW | EMLOCO_POST_AMP_SHIFT)) && (!b->amp_obs_buf || !b->dof_subset || !b->key_bodies || !b->betas || bad_dof_subset(b->n_dof_subset)))
         return tfail(-1, "emloco_task_post_physics_returns: AMP buffers missing");
     hipStream_t st = (hipStream_t)stream;
     if (g_timing) THIPCHK(hipEventRecord(g_ev0, st));
@@ -108,7 +111,7 @@ int emloco_task_amp_rows(int n, const float *root_pos, const float *root_rot, co
                          int n_dof_subset, float *out, void *stream) {
     if (n < 0 || !root_pos || !root_rot || !root_vel || !root_ang_vel || !dof_pos || !dof_vel || !key_pos || !betas || !dof_subset || !out)
         return tfail(-1, "emloco_task_amp_rows: bad argument");
-    if (n_dof_subset > 64 || n_dof_subset % 3) return tfail(-1, "emloco_task_amp_rows: dof subset must be <= 64 and a multiple of 3");
+    if (bad_dof_subset(n_dof_subset)) return tfail(-1, "emloco_task_amp_rows: dof subset must be a multiple of 3 in [0, 57] (a row of 35 + 3 n values within 206)");
     if (n == 0) return 0;
     hipLaunchKernelGGL(emloco::amp_rows_kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream, n, root_pos, root_rot,
                        root_vel, root_ang_vel, dof_pos, dof_vel, key_pos, betas, dof_subset, n_dof_subset, out);
@@ -291,7 +294,7 @@ int emloco_task_reset_obs_pooled(EmlocoSim *sim, const EmlocoResetBufs *rb, cons
         return tfail(-1, "emloco_task_reset_obs: no valid locations");
     if ((b->flags & EMLOCO_RESET_REAL_PATH) && b->n_real > 0 && !b->real_traj) return tfail(-1, "emloco_task_reset_obs: real_path without data");
     if (!pb->rb_state || !pb->progress_buf || !pb->traj_verts || !pb->obs_buf || !pb->flip_obs_buf || !pb->heightfield || !pb->betas ||
-        !pb->left_to_right || !pb->amp_obs_buf || !pb->dof_subset || !pb->key_bodies || !pb->dof_state || pb->n_dof_subset > 64 || pb->n_dof_subset % 3)
+        !pb->left_to_right || !pb->amp_obs_buf || !pb->dof_subset || !pb->key_bodies || !pb->dof_state || bad_dof_subset(pb->n_dof_subset))
         return tfail(-1, "emloco_task_reset_obs: missing observation buffers");
     emloco::ChainArgs a;
     a.n = n;

@@ -52,7 +52,7 @@ typedef struct {
     int32_t n_env;
     int32_t hf_rows, hf_cols;       /* height map shape (first index = x) */
     int32_t head_body;              /* sensor frame body (terrain_obs_root "head" -> 13) */
-    int32_t n_dof_subset;           /* 57 */
+    int32_t n_dof_subset;           /* 57; a multiple of 3, at most 57 (an AMP row is 35 + 3 n_dof_subset values, EMLOCO_AMP_ROW at most) */
     float dt;                       /* control dt = controlFrequencyInv * sim.dt */
     float traj_dur;                 /* num_verts * vertex dt (traj_generator.py:270-273) */
     float sample_dt;                /* trajSampleTimestep */
@@ -104,7 +104,8 @@ int emloco_task_post_physics_returns(const EmlocoTaskBufs *bufs, int mode, const
                                      const uint8_t *dev_inverted, void *stream);
 
 /* AMP rows from explicit states (history back-fill from the motion library, humanoid_amp.py:486-535):
- * n rows; inputs [n][3|4|3|3|69|69|4*3|17]; out [n][206]. */
+ * n rows; inputs [n][3|4|3|3|69|69|4*3|17]; out [n][206], of which a row fills its first 35 + 3 n_dof_subset values (n_dof_subset:
+ * a multiple of 3, at most 57: refused otherwise). */
 int emloco_task_amp_rows(int n, const float *root_pos, const float *root_rot, const float *root_vel,
                          const float *root_ang_vel, const float *dof_pos, const float *dof_vel,
                          const float *key_pos, const float *betas, const int32_t *dof_subset,
@@ -218,7 +219,10 @@ int emloco_task_get_heights(const int16_t *dev_heightfield, int rows, int cols, 
                             int n, int grid, float *dev_heights, int64_t *dev_px, int64_t *dev_py, void *stream);
 
 /* Device-side `reset_buf.nonzero()`: dev_ids[0..count) = ascending indices of the non-zero flags, the rest of the n
- * entries = -1, dev_ids[n] = count.  Every *_indexed / env-id-list entry point of this library skips negative ids, so
+ * entries = -1, dev_ids[n] = count.  Every *_indexed / env-id-list entry point of this library takes such a list -- negative ids
+ * only BEHIND the last valid one -- and skips its padding (the list kernels walk a list of more than 256 entries with a stride of 256
+ * and stop at the first negative id they meet, so an entry behind a negative id in the middle of a list may be dropped: its env is
+ * then left exactly as it was).  emloco_task_post_physics and emloco_sim_step_subset skip negative ids anywhere in their list.  So
  *   emloco_task_compact_done(reset_buf, E, ids, s); emloco_task_reset(sim, bufs, ids, E, rnd, s);
  *   emloco_task_post_physics(bufs, EMLOCO_POST_OBS | EMLOCO_POST_AMP_ROW, ids, E, s);
  * resets exactly the finished envs without the host ever reading the count (the reference's loop,

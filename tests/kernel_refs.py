@@ -497,3 +497,320 @@ def case_obs(rows, cols, seed):
     var = torch.rand(cols, generator=g) * 2.0 + 0.05
     x = mean + torch.sqrt(var) * torch.randn(rows, cols, generator=g) * 2.5      # ~4.5 % beyond the clamp at 5
     return dict(x=x, mean=mean, var=var)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# device-matrix bookkeeping shared by the conformance matrices
+
+MARGIN = 8.0                            # device bar = MARGIN x the float32 reference's own error
+
+
+class Table:
+    """collects (float32-reference error, device error) per output of a family; asserts device <= MARGIN x max float32 error"""
+
+    def __init__(self, family, executor="device"):
+        self.family, self.rows, self.executor = family, [], executor
+
+    def add(self, case, name, dev_err, f32_err):
+        self.rows.append((case, name, dev_err, f32_err))
+
+    def check(self):
+        names = sorted({r[1] for r in self.rows})
+        bad = []
+        print()
+        for n in names:
+            f32 = max(r[3] for r in self.rows if r[1] == n)
+            dev = max(r[2] for r in self.rows if r[1] == n)
+            bar = MARGIN * f32
+            print(f"  [{self.family}] {n:<12} float32 reference {f32:.3e}   bar {bar:.3e}   {self.executor} {dev:.3e}")
+            bad += [(r[0], n, r[2], bar) for r in self.rows if r[1] == n and not r[2] <= bar]
+        assert not bad, (f"{len(bad)} of {len(self.rows)} figures above {MARGIN} x the float32 reference's error", bad[:10])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the rollout's task kernels (include/emloco_task.h): quaternions are xyzw, every formula restated from the definitions the header
+# cites (the reference's torch_utils helpers and observation builders), in the dtype given
+
+F32 = torch.float32
+LEFT_TO_RIGHT = (0, 5, 6, 7, 8, 1, 2, 3, 4, 9, 10, 11, 12, 13, 19, 20, 21, 22, 23, 14, 15, 16, 17, 18)
+KEY_BODIES = (7, 3, 22, 17)
+CONTACT_BODIES = (7, 3, 8, 4)
+HEAD_BODY = 13
+DOF_SUBSET = tuple(3 * j + k for j in range(23) if j not in (3, 7, 17, 22) for k in range(3))      # every joint but toes and hands
+
+
+def quat_rotate(q, v):
+    """my_quat_rotate: v (2 w^2 - 1) + 2 w (q_v x v) + 2 q_v (q_v . v)"""
+    qv, w = q[..., :3], q[..., 3:4]
+    qv, v = torch.broadcast_tensors(qv, v)
+    return v * (2.0 * w * w - 1.0) + torch.cross(qv, v, dim=-1) * w * 2.0 + qv * (qv * v).sum(-1, keepdim=True) * 2.0
+
+
+def quat_mul(a, b):
+    """Hamilton product"""
+    x1, y1, z1, w1 = a.unbind(-1)
+    x2, y2, z2, w2 = b.unbind(-1)
+    return torch.stack([w1 * x2 + x1 * w2 + y1 * z2 - z1 * y2, w1 * y2 - x1 * z2 + y1 * w2 + z1 * x2,
+                        w1 * z2 + x1 * y2 - y1 * x2 + z1 * w2, w1 * w2 - x1 * x2 - y1 * y2 - z1 * z2], dim=-1)
+
+
+def _axis(q, k):
+    e = torch.zeros(3, dtype=q.dtype)
+    e[k] = 1.0
+    return e
+
+
+def calc_heading(q):
+    """the angle about z of the rotated x axis"""
+    r = quat_rotate(q, _axis(q, 0))
+    return torch.atan2(r[..., 1], r[..., 0])
+
+
+def quat_about_z(angle):
+    z = torch.zeros_like(angle)
+    return torch.stack([z, z, torch.sin(angle / 2.0), torch.cos(angle / 2.0)], dim=-1)
+
+
+def heading_inv(q):
+    return quat_about_z(-calc_heading(q))
+
+
+def quat_to_tan_norm(q):
+    return torch.cat([quat_rotate(q, _axis(q, 0)), quat_rotate(q, _axis(q, 2))], dim=-1)
+
+
+def exp_map_to_quat(e):
+    """rotation vector -> quaternion: the angle wrapped to (-pi, pi], an angle of at most 1e-5 is the identity"""
+    angle = e.norm(dim=-1, keepdim=True)
+    axis = e / angle
+    angle = torch.atan2(torch.sin(angle), torch.cos(angle))
+    small = ~(angle.abs() > 1e-5)
+    angle = torch.where(small, torch.zeros_like(angle), angle)
+    axis = torch.where(small, _axis(e, 2).expand_as(axis), axis)
+    q = torch.cat([axis * torch.sin(angle / 2.0), torch.cos(angle / 2.0)], dim=-1)
+    return q / q.norm(dim=-1, keepdim=True)
+
+
+def pd_targets(actions, offset, scale, zero_mask, dtype=F64):
+    """offset + scale a, exactly 0 where the mask is set"""
+    a, o, s = _c(actions, dtype), _c(offset, dtype), _c(scale, dtype)
+    m = torch.as_tensor(zero_mask).to("cpu") != 0
+    return torch.where(m, torch.zeros_like(a), o + s * a)
+
+
+def pd_targets_mag(actions, offset, scale):
+    a, o, s = _c(actions, F64), _c(offset, F64), _c(scale, F64)
+    return o.abs() + (s * a).abs()
+
+
+def amp_row(root_pos, root_rot, root_vel, root_ang_vel, dof_pos, dof_vel, key_pos, betas, dof_subset=DOF_SUBSET, dtype=F64):
+    """[n][35 + 3 n_sub] (206 for the shipped 57-entry subset): root rotation as tangent | normal in the heading frame (6), local root
+    velocity and angular velocity (6), the subset's joints as tangent | normal (6 each), the subset's dof velocities, the key bodies
+    relative to the root in the heading frame (12), betas[:11]"""
+    rp, rr, rv, ra, dp, dv, kp, bt = (_c(t, dtype) for t in (root_pos, root_rot, root_vel, root_ang_vel, dof_pos, dof_vel, key_pos, betas))
+    sub = torch.as_tensor(dof_subset).long()
+    n = rp.shape[0]
+    hinv = heading_inv(rr)
+    joints = quat_to_tan_norm(exp_map_to_quat(dp[:, sub].reshape(n, -1, 3))).reshape(n, -1)
+    keys = quat_rotate(hinv[:, None, :], kp.reshape(n, 4, 3) - rp[:, None, :]).reshape(n, 12)
+    return torch.cat([quat_to_tan_norm(quat_mul(hinv, rr)), quat_rotate(hinv, rv), quat_rotate(hinv, ra), joints, dv[:, sub], keys, bt[:, :11]], dim=1)
+
+
+def amp_blocks(n_sub=57):
+    nj = n_sub // 3
+    a = 12 + 6 * nj
+    return (("rotation", 0, 6), ("velocity", 6, 12), ("dof_pos", 12, a), ("dof_vel", a, a + n_sub), ("key_pos", a + n_sub, a + n_sub + 12))
+
+
+def self_obs(body_pos, body_rot, body_vel, body_ang_vel, betas, dtype=F64):
+    """368 values: bodies 1..23 relative to the root in the heading frame (69), every body's rotation as tangent | normal (144), linear
+    (72) and angular (72) velocities in the heading frame, betas[:11]"""
+    p, r, v, a, bt = (_c(t, dtype) for t in (body_pos, body_rot, body_vel, body_ang_vel, betas))
+    E = p.shape[0]
+    hinv = heading_inv(r[:, 0])[:, None, :]
+    local = quat_rotate(hinv, p - p[:, :1])[:, 1:]
+    rot = quat_to_tan_norm(quat_mul(hinv.expand(E, 24, 4), r))
+    return torch.cat([local.reshape(E, 69), rot.reshape(E, 144), quat_rotate(hinv, v).reshape(E, 72), quat_rotate(hinv, a).reshape(E, 72),
+                      bt[:, :11]], dim=1)
+
+
+def mirror_bodies(body_pos, body_rot, body_vel, body_ang_vel, left_to_right=LEFT_TO_RIGHT):
+    """the left-right mirrored state: y of positions and velocities, x and z of rotations and angular velocities change sign, and
+    the bodies trade places through left_to_right"""
+    p, r, v, a = (torch.as_tensor(t).clone() for t in (body_pos, body_rot, body_vel, body_ang_vel))
+    l2r = torch.as_tensor(left_to_right).long()
+    p[..., 1] *= -1
+    v[..., 1] *= -1
+    r[..., 0] *= -1
+    r[..., 2] *= -1
+    a[..., 0] *= -1
+    a[..., 2] *= -1
+    return p[:, l2r], r[:, l2r], v[:, l2r], a[:, l2r]
+
+
+def flip_self_obs(body_pos, body_rot, body_vel, body_ang_vel, betas, left_to_right=LEFT_TO_RIGHT, dtype=F64):
+    return self_obs(*mirror_bodies(body_pos, body_rot, body_vel, body_ang_vel, left_to_right), betas, dtype=dtype)
+
+
+def traj_calc_pos(verts, t, traj_dur, dtype=F64):
+    """the polyline verts [E][V][3] at time t [E] or [E][k]: phase = clip(t / traj_dur, 0, 1), linear between the two vertices"""
+    verts, t = _c(verts, dtype), _c(t, dtype)
+    V = verts.shape[1]
+    seg = torch.clamp(t / traj_dur, 0.0, 1.0) * (V - 1)
+    i0, i1 = torch.floor(seg).long(), torch.ceil(seg).long()
+    lerp = (seg - i0.to(dtype))[..., None]
+    idx = lambda i: torch.gather(verts, 1, i.reshape(verts.shape[0], -1, 1).expand(-1, -1, 3)).reshape(*t.shape, 3)
+    return (1.0 - lerp) * idx(i0) + lerp * idx(i1)
+
+
+def traj_sample_times(progress, dt, sample_dt, n=15, dtype=F64):
+    """progress dt + k sample_dt with dt and sample_dt as the float32 numbers the launch carries"""
+    dt32, sdt32 = torch.tensor(dt, dtype=F32).to(dtype), torch.tensor(sample_dt, dtype=F32).to(dtype)
+    return torch.as_tensor(progress).to(dtype)[:, None] * dt32 + torch.arange(n).to(dtype)[None, :] * sdt32
+
+
+def location_obs(root, samples, dtype=F64):
+    """root [E][>=7] (position, rotation), samples [E][k][3] -> [E][2 k]: x, y of sample - root in the heading frame"""
+    root, samples = _c(root, dtype), _c(samples, dtype)
+    hinv = heading_inv(root[:, 3:7])[:, None, :]
+    return quat_rotate(hinv, samples - root[:, None, :3])[..., :2].reshape(root.shape[0], -1)
+
+
+def reward(root_pos, target, dof_force, dof_vel, power_coef, dtype=F64):
+    """-> rew, loc = exp(-2 |target - root|_xy^2), power = -coef sum |force x velocity|, and sum |terms| of the power sum"""
+    rp, tg, f, v = (_c(t, dtype) for t in (root_pos, target, dof_force, dof_vel))
+    coef = torch.tensor(power_coef, dtype=F32).to(dtype)
+    d = tg[:, :2] - rp[:, :2]
+    loc = torch.exp(-2.0 * (d * d).sum(-1))
+    terms = (f * v).abs().sum(-1)
+    power = -coef * terms
+    return loc + power, loc, power, coef * terms
+
+
+def reset_flags(progress, contact_force, contact_body_mask, root_pos, target, fail_dist, max_episode_length, dtype=F64):
+    """-> reset, terminate (int64) and the distances of every env to the four thresholds [E][4]: |sum of the unmasked bodies' contact
+    forces| - 50, |target - root|_xy^2 - fail_dist^2, progress - 1, progress - (max_episode_length - 1)"""
+    cf, rp, tg = (_c(t, dtype) for t in (contact_force, root_pos, target))
+    prog = torch.as_tensor(progress).to("cpu").to(dtype)
+    live = (torch.as_tensor(contact_body_mask).to("cpu") == 0).to(dtype)
+    s = (cf * live[None, :, None]).sum(dim=1)
+    mag = torch.sqrt((s * s).sum(-1))
+    d = tg[:, :2] - rp[:, :2]
+    d2 = (d * d).sum(-1)
+    dist = torch.stack([mag - 50.0, d2 - fail_dist * fail_dist, prog - 1.0, prog - (max_episode_length - 1.0)], dim=1)
+    term = ((dist[:, 0] > 0) & (dist[:, 2] > 0)) | (dist[:, 1] > 0)
+    reset = torch.where(dist[:, 3] >= 0, torch.ones_like(term), term)
+    return reset.long(), term.long(), dist
+
+
+def reset_near(dist, fail_dist, rel=1e-5):
+    """envs within rel (relative) of a threshold of reset_flags: judged against the fp32 oracle only (progress is an integer: never near)"""
+    return (dist[:, 0].abs() < rel * 50.0) | (dist[:, 1].abs() < rel * fail_dist * fail_dist)
+
+
+def task_branch_distances(c):
+    """float64 distances (with their scales) of a case_task state to every clamp / branch of the observations and flags:
+    the +-3 clip of the height observations is measured where the heights exist (height_clip_distance); here: the 1e-5 and pi
+    thresholds of the joints' rotation vectors, the clip of the trajectory phase, and the flags' thresholds"""
+    dp = c["dof_state"][:, :, 0].double().reshape(-1, 23, 3).norm(dim=-1)
+    t = traj_sample_times(c["progress"], c["dt"], c["sample_dt"]) / c["traj_dur"]
+    _, _, dist = reset_flags(c["progress"], c["contact_force"], c["contact_body_mask"], c["rb_state"][:, 0, :3],
+                             traj_calc_pos(c["traj_verts"], traj_sample_times(c["progress"], c["dt"], c["sample_dt"], 1), c["traj_dur"])[:, 0],
+                             c["fail_dist"], c["max_episode_length"])
+    return {"joint angle 1e-5": (dp - 1e-5, 1.0), "joint angle pi": (dp - math.pi, math.pi), "phase clip": (t - 1.0, 1.0),
+            "contact 50 N": (dist[:, 0], 50.0), "fail distance": (dist[:, 1], c["fail_dist"] ** 2)}
+
+
+def height_clip_distance(center_mean, heights):
+    """|mean(centre) - h| - 3 of the height observations clip(mean(centre) - h, -3, 3) x 5"""
+    return (_c(center_mean, F64)[:, None] - _c(heights, F64)).abs() - 3.0
+
+
+def case_task(E, seed, max_episode_length=168.0):
+    """A physically plausible but hard rollout state of E envs: roots 40-120 m from the origin (body - root and target - root cancel),
+    headings over the full circle (some within 1e-3 of 0 and of +-pi), bodies pitched past vertical, progress over [0, max_len]
+    (0, 1, 2, max_len - 2, max_len - 1 among them), contact-force sums from 0 to 200 N, targets on both sides of the fail distance."""
+    g = _gen(seed)
+    rnd = lambda *s: torch.rand(*s, generator=g)
+    nrm = lambda *s: torch.randn(*s, generator=g)
+    ang = (rnd(E) * 2.0 - 1.0) * math.pi
+    special = torch.tensor([0.0, 5e-4, -5e-4, math.pi - 5e-4, -math.pi + 5e-4, math.pi - 1e-6, -math.pi + 1e-6])
+    k = torch.arange(E)
+    pick = (k % 5 == 1) | (E <= 7)
+    ang = torch.where(pick, special[k % 7], ang)
+    rad = 40.0 + 80.0 * rnd(E)
+    phi = (rnd(E) * 2.0 - 1.0) * math.pi
+    if E > 3:                                           # some envs in the negative quadrants, off the map's low sides
+        phi[::4] = phi[::4].abs() * 0.5                 # ... and a quarter of them over the map
+    root_pos = torch.stack([rad * torch.cos(phi), rad * torch.sin(phi), 0.85 + 0.2 * rnd(E)], dim=1)
+
+    def quat(axis, a):
+        axis = axis / axis.norm(dim=-1, keepdim=True)
+        return torch.cat([axis * torch.sin(a / 2.0)[..., None], torch.cos(a / 2.0)[..., None]], dim=-1)
+
+    yaw = quat(torch.tensor([0.0, 0.0, 1.0]).expand(E, 3), ang).double()
+    pitch_a = torch.where((k % 3 == 0) & ~pick, 1.2 + 1.2 * rnd(E), 0.3 * nrm(E))  # a third pitched 70-140 degrees: past vertical
+    wobble = torch.where(pick[:, None], torch.zeros(E, 3), 0.2 * nrm(E, 3))        # (a pitch about y itself keeps the chosen heading)
+    pitch = quat(torch.tensor([0.0, 1.0, 0.0]).expand(E, 3) + wobble, pitch_a).double()
+    root_rot = quat_mul(yaw, pitch)
+    rb = torch.zeros(E, 24, 13, dtype=F64)
+    rb[:, :, :3] = root_pos[:, None, :].double() + (nrm(E, 24, 3) * 0.45).double()
+    rb[:, 0, :3] = root_pos.double()
+    body_q = quat(nrm(E, 24, 3), nrm(E, 24) * 1.5).double()
+    rb[:, :, 3:7] = quat_mul(root_rot[:, None, :].expand(E, 24, 4), body_q)
+    rb[:, 0, 3:7] = root_rot
+    rb[:, HEAD_BODY, :2] = rb[:, 0, :2] + 0.2 * nrm(E, 2).double()
+    rb[:, :, 7:10] = (nrm(E, 24, 3) * 1.5).double()
+    rb[:, :, 10:13] = (nrm(E, 24, 3) * 4.0).double()
+    rb = rb.float()
+    dof_state = torch.stack([nrm(E, 69) * 0.5, nrm(E, 69) * 3.0], dim=-1)
+    dof_state[:, 0:3, 0] *= 0.01                                                  # a nearly straight joint (small rotation vector)
+    dof_force = nrm(E, 69) * 40.0
+    betas = nrm(E, 17)
+    ml = int(max_episode_length)
+    edge = torch.tensor([0, 1, 2, ml - 2, ml - 1, ml])
+    progress = torch.where(k % 4 == 0, edge[(k // 4) % 6], (rnd(E) * (ml + 1)).long().clamp(max=ml))
+    if E < 24:
+        progress = edge[k % 6] if E >= 6 else progress
+    # trajectory: a walk of ~1.2 m/s from near the root; a fifth of the envs starts 3-5.5 m away (both sides of the 4 m fail distance)
+    dt, sample_dt = 1.0 / 30.0, 0.4
+    vert_dt = ml * dt / 100.0
+    head = (rnd(E) * 2.0 - 1.0) * math.pi
+    step = torch.stack([torch.cos(head), torch.sin(head)], dim=1)[:, None, :] * (1.2 * vert_dt) + 0.01 * nrm(E, 101, 2)
+    path = torch.cumsum(step, dim=1) - step[:, :1]
+    off_r = torch.where(k % 5 == 2, 3.0 + 2.5 * rnd(E), 1.5 * rnd(E))
+    off_a = (rnd(E) * 2.0 - 1.0) * math.pi
+    verts = torch.zeros(E, 101, 3)
+    verts[:, :, :2] = path
+    # the offset is placed so that the sample at the env's own progress sits off_r from the root
+    now = traj_calc_pos(verts, progress.double() * float(torch.tensor(dt, dtype=F32)), 101 * vert_dt)[:, :2].float()
+    verts[:, :, :2] += (root_pos[:, :2] + torch.stack([off_r * torch.cos(off_a), off_r * torch.sin(off_a)], dim=1) - now)[:, None, :]
+    verts[:, :, 2] = nrm(E, 101) * 0.01
+    mask = torch.zeros(24, dtype=torch.uint8)
+    mask[list(CONTACT_BODIES)] = 1
+    cf = nrm(E, 24, 3) * 3.0
+    cf[:, list(CONTACT_BODIES)] = nrm(E, 4, 3) * 400.0                             # the feet carry the weight and must not count
+    want = 200.0 * rnd(E)                                                          # the unmasked sum's size: 0 .. 200 N
+    want[::7] = 0.0
+    live = (mask == 0).float()
+    s = (cf * live[None, :, None]).sum(1)
+    dirn = nrm(E, 3)
+    dirn = dirn / dirn.norm(dim=-1, keepdim=True)
+    cf[:, 11] += dirn * want[:, None] - s
+    if E > 1:
+        cf[::7] = 0.0
+        cf[::7, list(CONTACT_BODIES)] = 300.0
+    return dict(rb_state=rb, dof_state=dof_state, dof_force=dof_force, contact_force=cf, betas=betas, traj_verts=verts,
+                progress=progress.long(), contact_body_mask=mask, dt=dt, sample_dt=sample_dt, traj_dur=101 * vert_dt,
+                fail_dist=4.0, max_episode_length=float(ml), power_coef=0.0005)
+
+
+def task_map(rows=520, cols=610, seed=3):
+    """a non-square int16 height map (0.1 m cells, 0.005 m units): the envs of case_task stand 40-120 m out in every direction, so
+    their probes leave it on all four sides (negative world coordinates included) and some stand on it; steps of up to +-4 m so that the
+    +-3 clip of the height observations is reached"""
+    g = _gen(seed)
+    i, j = torch.arange(rows)[:, None], torch.arange(cols)[None, :]
+    coarse = torch.randint(-800, 800, (rows // 8 + 1, cols // 8 + 1), generator=g)[i // 8, j // 8]
+    fine = torch.randint(-3, 4, (rows, cols), generator=g)
+    return (coarse + fine).to(torch.int16)

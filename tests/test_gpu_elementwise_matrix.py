@@ -95,7 +95,7 @@ NORM_BAR = COLSUM_C + ULP4              # clip norm: a fixed-order sum of (posit
                                         # roundings); the squared norm, the coefficient (half the sum's relative error) and g x coefficient all stay below it
 ROW_BAR = 2.0 ** -19                    # constructed actor rows: neglogp is a sum of <= 4 terms of magnitude <= 4.5, each addition rounding at 2^-24: <= 2^-20
                                         # absolute in the exponent, which expf turns into a relative error of the ratio, plus expf's own 2 ulp (2^-22)
-MARGIN = 8.0                            # device bar = MARGIN x the float32 reference's own error
+MARGIN, Table = R.MARGIN, R.Table      # device bar = MARGIN x the float32 reference's own error (kernel_refs.Table, shared with the task matrix)
 
 
 def _lib():
@@ -160,28 +160,6 @@ def _unaligned(t):
 def _got(o):
     torch.cuda.synchronize()
     return o.got()[0].reshape(o.shape[1:]).cpu()
-
-
-class Table:
-    """collects (float32-reference error, device error) per output of a family; asserts device <= MARGIN x max float32 error"""
-
-    def __init__(self, family):
-        self.family, self.rows = family, []
-
-    def add(self, case, name, dev_err, f32_err):
-        self.rows.append((case, name, dev_err, f32_err))
-
-    def check(self):
-        names = sorted({r[1] for r in self.rows})
-        bad = []
-        print()
-        for n in names:
-            f32 = max(r[3] for r in self.rows if r[1] == n)
-            dev = max(r[2] for r in self.rows if r[1] == n)
-            bar = MARGIN * f32
-            print(f"  [{self.family}] {n:<12} float32 reference {f32:.3e}   bar {bar:.3e}   device {dev:.3e}")
-            bad += [(r[0], n, r[2], bar) for r in self.rows if r[1] == n and not r[2] <= bar]
-        assert not bad, (f"{len(bad)} of {len(self.rows)} figures above {MARGIN} x the float32 reference's error", bad[:10])
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -193,6 +193,36 @@ def test_reset_done_equals_reset_of_nonzero():
     assert torch.equal(ta._traj_gen._traj_verts, tb._traj_gen._traj_verts) if hasattr(ta._traj_gen, "_traj_verts") else True
 
 
+def test_fused_reset_above_256_envs_in_one_call_equals_chunks_of_200():
+    """The list-driven reset kernels walk a list of more than 256 entries with a stride of 256 workgroups: `_fused_reset_envs(ids, rnd)`
+    of all 640 envs, then of 300 scattered ones, in one call against the same ids and random rows issued in chunks of 200 -- two
+    identically seeded envs, every buffer test_reset_done_equals_reset_of_nonzero compares, bit for bit."""
+    from emloco_amd import _lib as L
+    args = ["--random_heading", "--init_heading", "--heading_inversion", "--adjust_root_vel"]
+    E = 640
+    envs = [_make_env(E, args), _make_env(E, args)]
+    dev = envs[0].task.device
+    g = torch.Generator(device=dev)
+    scattered = torch.randperm(E, generator=torch.Generator().manual_seed(6))[:300].to(dev)
+    for k, ids in enumerate((torch.arange(E, device=dev), scattered)):
+        g.manual_seed(700 + k)
+        rnd = torch.rand(ids.numel(), L.RESET_RND, device=dev, generator=g)
+        envs[0].task._fused_reset_envs(ids, rnd=rnd)
+        for lo in range(0, ids.numel(), 200):
+            envs[1].task._fused_reset_envs(ids[lo:lo + 200].contiguous(), rnd=rnd[lo:lo + 200].contiguous())
+        torch.cuda.synchronize()
+        ta, tb = envs[0].task, envs[1].task
+        for name in ("_root_states", "_dof_state", "obs_buf", "_amp_obs_buf", "progress_buf", "reset_buf", "rew_buf", "waypoint_traj",
+                     "init_pose", "init_vel", "_motion_start_times", "_sampled_motion_ids"):
+            assert torch.equal(getattr(ta, name), getattr(tb, name)), (k, name)
+        assert torch.equal(ta._traj_gen._verts, tb._traj_gen._verts) and torch.equal(ta.inverted, tb.inverted), k
+        if k == 0:
+            g.manual_seed(900)
+            act = torch.randn(E, 69, device=dev, generator=g) * 0.3
+            for e in envs:
+                e.step(act)
+
+
 def test_seeded_reset_done_draws_uniform_rows_on_the_device():
     """reset_done() without explicit rows: the rows come from the stateless device generator, only for the finished envs;
     same seed and call count -> same bytes, the values are uniform on [0, 1), and the resets it produces are as varied as
@@ -630,6 +660,19 @@ def test_observations_on_a_side_stream_give_the_same_rollout():
 @pytest.mark.gpu
 @pytest.mark.parametrize("seeded,pool,amp_early", [(False, 64, False), (True, 64, False), (True, 8, False), (True, 0, False), (True, 64, True)])
 def test_fused_chain_gives_the_same_rollout(seeded, pool, amp_early, monkeypatch):
+    _fused_chain_rollout(seeded, pool, amp_early, monkeypatch)
+
+
+@pytest.mark.gpu
+def test_fused_chain_gives_the_same_rollout_above_256_finished_envs(monkeypatch):
+    """The same comparison at 640 envs over ten steps with a pool of 64: all 640 finish at step 0 and 300 scattered ones at step 3, so
+    the reset role and the 14 history roles of the fused launch walk their lists with the 256-workgroup stride, with pool hits and
+    entries beyond the pool."""
+    forced = torch.randperm(640, generator=torch.Generator().manual_seed(4))[:300]
+    _fused_chain_rollout(True, 64, False, monkeypatch, E=640, steps=10, forced=forced)
+
+
+def _fused_chain_rollout(seeded, pool, amp_early, monkeypatch, E=96, steps=30, forced=None):
     """task.fused_chain: post_physics_step launches only progress / reward / flags (+ the terminal AMP rows of the finished envs),
     reset_done() is two launches -- emloco_task_compact_done_order (compaction + flag snapshot + the next step's dispatch order) and
     emloco_task_reset_obs (reset chain of the finished envs, their AMP history, their observations AND the deferred observation /
@@ -642,7 +685,7 @@ def test_fused_chain_gives_the_same_rollout(seeded, pool, amp_early, monkeypatch
     monkeypatch.setenv("EMLOCO_RESET_POOL", str(pool))
     args = ["--random_heading", "--init_heading", "--heading_inversion", "--adjust_root_vel"]
     torch.manual_seed(11)
-    envs = [_make_env(96, args), _make_env(96, args)]
+    envs = [_make_env(E, args), _make_env(E, args)]
     envs[1].task.fused_chain = True
     envs[1].task.fused_amp_early = amp_early        # AMP rows of every env in the flags launch (a discriminator reads them before the resets)
     for e in envs:
@@ -651,17 +694,20 @@ def test_fused_chain_gives_the_same_rollout(seeded, pool, amp_early, monkeypatch
     g = torch.Generator(device=dev)
     names = ("_root_states", "_dof_state", "_rigid_body_state", "obs_buf", "_flip_obs_buf", "_amp_obs_buf", "progress_buf", "reset_buf",
              "rew_buf", "reward_raw", "_terminate_buf", "waypoint_traj", "init_pose", "init_vel", "inverted")
-    for k in range(30):
+    for k in range(steps):
         g.manual_seed(100 + k)
-        act = torch.randn(96, 69, device=dev, generator=g) * 0.3
+        act = torch.randn(E, 69, device=dev, generator=g) * 0.3
         g.manual_seed(500 + k)
-        rnd = None if seeded else torch.rand(96, L.RESET_RND, device=dev, generator=g)
+        rnd = None if seeded else torch.rand(E, L.RESET_RND, device=dev, generator=g)
         for e in envs:
             t = e.task
             if k == 0:
                 t.reset_buf[:] = 1
             if k % 7 == 3:
-                t.reset_buf[5:40:3] = 1
+                if forced is None:
+                    t.reset_buf[5:40:3] = 1
+                else:
+                    t.reset_buf[forced.to(dev)] = 1
             t.reset_done(rnd=rnd)
         assert envs[1].task._obs_deferred == 0
         torch.cuda.synchronize()
@@ -679,7 +725,7 @@ def test_fused_chain_gives_the_same_rollout(seeded, pool, amp_early, monkeypatch
             assert torch.equal(envs[0].task._amp_obs_buf, envs[1].task._amp_obs_buf), (k, "AMP observations of every env right after the step")
         for name in ("_rigid_body_state", "rew_buf", "progress_buf", "_terminate_buf"):
             assert torch.equal(getattr(envs[0].task, name), getattr(envs[1].task, name)), (k, name, "after step")
-    assert int((envs[0].task.progress_buf == 0).sum()) < 96            # natural / forced resets happened, not only the first
+    assert int((envs[0].task.progress_buf == 0).sum()) < E            # natural / forced resets happened, not only the first
     if seeded and pool > 0:                                            # the pool was in use: the last launch tagged its draw
         t = envs[1].task
         assert int((t._pool_tag[t._pool_flip] != 0).sum()) >= min(pool, 32)

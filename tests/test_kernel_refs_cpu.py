@@ -403,3 +403,97 @@ def test_obs_cases_stay_off_the_clamp_edge(rows, cols, seed):
     assert R.near_share(y.abs() - 5.0, 5.0) <= SHARE_CAP
     if rows * cols > 1000:
         assert (y > 5).any() and (y < -5).any()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the task references (include/emloco_task.h) against the committed fixtures of the reference's own results, at the tolerances
+# tests/test_oracle_golden.py states for those fixtures; and the near-branch shares of the case_task states the task matrix runs
+
+import task_cases as TC            # noqa: E402
+
+
+def _golden(name):
+    return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", name + ".npz"))
+
+
+def _allclose(got, want, rtol, atol, what):
+    np.testing.assert_allclose(torch.as_tensor(got).double().numpy(), want, rtol=rtol, atol=atol, err_msg=what)
+
+
+def test_task_refs_match_the_golden_fixtures():
+    g = _golden("pd_targets")
+    zero = np.zeros(69, np.uint8)
+    for j in (3, 7, 17, 22):
+        zero[3 * j:3 * j + 3] = 1
+    _allclose(R.pd_targets(g["actions"], g["offset"], g["scale"], zero), g["pd_tar"], 1e-6, 1e-6, "pd_targets")
+    g = _golden("amp_obs")
+    assert tuple(g["dof_subset"].tolist()) == R.DOF_SUBSET
+    row = R.amp_row(g["root_pos"], g["root_rot"], g["root_vel"], g["root_ang_vel"], g["dof_pos"], g["dof_vel"], g["key_pos"], g["betas"], g["dof_subset"])
+    assert row.shape == (16, 206) and R.amp_blocks(57)[-1][2] + 11 == 206
+    _allclose(row, g["amp_obs"], 1e-5, 2e-5, "amp_row")
+    g = _golden("self_obs")
+    a = (g["body_pos"], g["body_rot"], g["body_vel"], g["body_ang_vel"], g["betas"])
+    _allclose(R.self_obs(*a), g["obs"], 1e-5, 2e-5, "self_obs")
+    _allclose(R.flip_self_obs(*a), g["flip_obs"], 1e-5, 2e-5, "flip_self_obs")
+    g = _golden("traj_samples")
+    dur = float(np.float32(g["traj_dur"]))
+    s = R.traj_calc_pos(g["verts"], R.traj_sample_times(g["progress"], float(g["dt"]), 0.4), dur)
+    _allclose(s[:, 0], g["tar_pos"], 1e-6, 1e-5, "tar_pos")
+    _allclose(s, g["samples"], 1e-6, 1e-5, "samples")
+    _allclose(R.location_obs(g["root_states"], g["samples"]), g["loc_obs"], 1e-5, 2e-5, "loc_obs")
+    g = _golden("reward_reset")
+    rew, loc, power, terms = R.reward(g["root_pos"], g["tar_pos"], g["dof_force"], g["dof_vel"], 0.0005)
+    _allclose(loc, g["loc_reward"], 1e-5, 1e-6, "loc_reward")
+    _allclose(power, g["power_reward"], 1e-5, 1e-6, "power_reward")
+    _allclose(rew, g["rew"], 1e-5, 1e-6, "rew")
+    assert (terms >= power.abs() * (1 - 1e-12)).all()
+    mask = np.zeros(24, np.uint8)
+    mask[list(R.CONTACT_BODIES)] = 1
+    args = (g["progress"], g["contact"], mask, g["body_pos"][:, 0], g["tar_pos"], 4.0, 168.0)
+    # the masks are defined in fp32 threshold arithmetic: the fixture holds an env whose force sum (30, 40, 0.01) N has a magnitude of
+    # exactly 50 in fp32 and of 50.000001 in float64.  Evaluated in fp32 the reference reproduces every mask; evaluated in float64 it
+    # reproduces every env it does not itself report within 1e-5 of a threshold -- that env and one exactly on the threshold.
+    rs, tm, _ = R.reset_flags(*args, dtype=torch.float32)
+    assert np.array_equal(rs.numpy(), g["reset"]) and np.array_equal(tm.numpy(), g["terminate"])
+    rs, tm, dist = R.reset_flags(*args)
+    near = R.reset_near(dist, 4.0).numpy()
+    assert 1 <= near.sum() <= 2 and near[10] and abs(dist[10, 0].item()) < 2e-6          # (the other one sits exactly on 50 N)
+    assert np.array_equal(rs.numpy()[~near], g["reset"][~near]) and np.array_equal(tm.numpy()[~near], g["terminate"][~near])
+    assert dist.shape == (64, 4) and torch.equal(dist[:, 2], torch.as_tensor(g["progress"]).double() - 1) and torch.equal(dist[:, 3], dist[:, 2] - 166)
+    g = _golden("task_obs_flip")                         # the mirrored task observations: y of the 15 samples negated, the grid's j reversed
+    t = torch.as_tensor(g["task_obs"])
+    flip = torch.cat([t[:, :30] * torch.tensor([1.0, -1.0]).repeat(15), t[:, 30:].reshape(-1, 32, 32).flip(2).reshape(-1, 1024)], dim=1)
+    assert np.array_equal(flip.numpy(), g["flip_task_obs"])
+
+
+TASK_CASES = sorted(set(TC.AMP_CASES + TC.POST_CASES + [TC.ALGEBRA_CASE]))
+
+
+@pytest.mark.parametrize("E,seed", TASK_CASES)
+def test_task_cases_are_hard_and_stay_off_the_branches(E, seed):
+    import oracle
+    c = R.case_task(E, seed)
+    for name, (dist, scale) in R.task_branch_distances(c).items():
+        assert R.near_share(dist, scale) <= SHARE_CAP, name
+    assert TC.joint_band(c, R.DOF_SUBSET).double().mean().item() <= SHARE_CAP                      # (the band the judges leave out)
+    hf = R.task_map().numpy()
+    rb = c["rb_state"].numpy()
+    center = oracle.get_center_heights(np.ascontiguousarray(rb[:, 0]), hf).astype(np.float64).mean(axis=1)
+    heights = oracle.get_heights(np.ascontiguousarray(rb[:, R.HEAD_BODY, :7]), hf)
+    clip = R.height_clip_distance(center, heights)
+    assert R.near_share(clip, 3.0) <= SHARE_CAP
+    root = c["rb_state"][:, 0, :3].double()
+    assert (root[:, :2].norm(dim=1) >= 40 - 1e-3).all() and (root[:, :2].norm(dim=1) <= 120 + 1e-3).all()
+    if E >= 63:
+        head = R.calc_heading(c["rb_state"][:, 0, 3:7].double())
+        tilt = R.quat_rotate(c["rb_state"][:, 0, 3:7].double(), torch.tensor([0.0, 0.0, 1.0], dtype=F64))[:, 2]
+        assert (head.abs() < 1e-3).any() and (head.abs() > np.pi - 1e-3).any() and (head > 2).any() and (head < -2).any()
+        assert (tilt < 0).any(), "no body pitched past vertical"
+        ml = int(c["max_episode_length"])
+        assert set([0, 1, 2, ml - 2, ml - 1]) <= set(c["progress"].tolist())
+        rs, tm, dist = R.reset_flags(c["progress"], c["contact_force"], c["contact_body_mask"], root,
+                                     TC.post_reference(c, False)["target"], c["fail_dist"], c["max_episode_length"])
+        mag = dist[:, 0] + 50.0
+        assert mag.min() == 0 and mag.max() > 150 and ((mag > 50) & (c["progress"] == 1)).any() and ((mag > 50) & (c["progress"] == 2)).any()
+        assert (dist[:, 1] > 0).any() and (dist[:, 1] < 0).any() and 0 < tm.sum() < E and (rs != tm).any()
+        assert (clip > 0).any() and (clip < 0).any(), "the +-3 clip of the height observations is not reached from both sides"
