@@ -148,6 +148,20 @@ class LocoValEval(C.Structure):
                 ("init_vel", C.c_void_p), ("traj13", C.c_void_p), ("pose", C.c_void_p), ("vel", C.c_void_p), ("row_mask", C.c_void_p)]
 
 
+EVAL_MAX_NETS = 8           # EMLOCO_EVAL_MAX_NETS
+
+
+class LocoValNet(C.Structure):
+    """EmlocoLocoValNet (include/emloco_predictor.h): one network of the evaluation's table."""
+    _fields_ = [("variant", C.c_int32), ("_pad", C.c_int32), ("w1", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p),
+                ("w3", C.c_void_p), ("b3", C.c_void_p), ("value", C.c_void_p)]
+
+
+class LocoValNets(C.Structure):
+    """EmlocoLocoValNets: the networks scored on the same games (emloco_locoval_eval_fwd_multi / _finish_multi)."""
+    _fields_ = [("n_nets", C.c_int32), ("_pad", C.c_int32), ("net", LocoValNet * EVAL_MAX_NETS)]
+
+
 def default_sim_params(**kw):
     """Engine parameters of pacer.yaml:93-104 / config.py:143-163 mapped onto EmlocoSimParams."""
     p = dict(n_sub=2, n_iter=4, h=(1.0 / 60.0) / 2, gravity_z=-9.81, contact_offset=0.02, erp=0.2,

@@ -42,6 +42,20 @@ int emloco_locoval_eval_finish(const EmlocoLocoValEval *s, const float *value, E
     return 0;
 }
 
+int emloco_locoval_eval_finish_multi(const EmlocoLocoValEval *s, const EmlocoLocoValNets *nets, EmlocoLocoValRecord *records, void *stream) {
+    if (!s || s->n_env < 1 || s->games_per_env < 1 || !nets || !records || !s->n_full || !s->games || !s->done || !s->steps)
+        return efail(-1, "emloco_locoval_eval_finish_multi: bad argument");
+    if (nets->n_nets < 1 || nets->n_nets > EMLOCO_EVAL_MAX_NETS)
+        return efail(-1, "emloco_locoval_eval_finish_multi: n_nets outside 1 .. EMLOCO_EVAL_MAX_NETS");
+    for (int k = 0; k < nets->n_nets; ++k)
+        if (nets->net[k].variant < 0 || nets->net[k].variant > 3 || !nets->net[k].value)
+            return efail(-1, "emloco_locoval_eval_finish_multi: a network with a bad variant or no value plane");
+    hipLaunchKernelGGL(emloco::locoval_eval_finish_multi_kernel, dim3((unsigned)((s->n_env + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       *s, *nets, records);
+    EHIPCHK(hipGetLastError());
+    return 0;
+}
+
 int emloco_locoval_eval_reduce(int n_env, int games_per_env, const EmlocoLocoValRecord *records, const int32_t *games, double *moments,
                                void *stream) {
     if (n_env < 1 || games_per_env < 1 || !records || !games || !moments) return efail(-1, "emloco_locoval_eval_reduce: bad argument");

@@ -68,17 +68,17 @@ locoval_eval_step_kernel(EmlocoLocoValEval s, const float *reward_raw, const flo
     s.inverted[e] = (inverted && inverted[e]) ? 1 : 0;
 }
 
-// One thread per env, after emloco_locoval_fwd_rows has evaluated the rows of this step's first steps: a game that ended this step is
-// recorded at records[e][games[e]] while the env's quota is not met (each env owns its slots: no append, no atomics on the records,
-// the same records whatever the schedule), then the per-game state starts over.  A game that ends at its first step records the
+// One env after the forward has evaluated the rows of this step's first steps: a game that ended this step is recorded at
+// records[k][e][games[e]] for each of the n_nets networks (value_of(k): network k's value plane; the planes differ in `value` and `sq_err`
+// alone) while the env's quota is not met (each env owns its slots: no append, no atomics on the records, the same records whatever the
+// schedule), then the per-game state starts over -- once, however many networks.  A game that ends at its first step records the
 // prediction made at that very step.
-__global__ void __launch_bounds__(256)
-locoval_eval_finish_kernel(EmlocoLocoValEval s, const float *value, EmlocoLocoValRecord *records) {
+template <class VALUES>
+__device__ __forceinline__ void locoval_eval_finish_env(const EmlocoLocoValEval &s, int e, int n_nets, VALUES value_of, EmlocoLocoValRecord *records) {
 #ifndef EMLOCO_EMU
 #pragma clang fp contract(off)
 #endif
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= s.n_env || !s.done[e]) return;
+    if (!s.done[e]) return;
     const int g = s.games[e];
     if (g < s.games_per_env) {
         const int steps = s.steps[e];
@@ -88,19 +88,22 @@ locoval_eval_finish_kernel(EmlocoLocoValEval s, const float *value, EmlocoLocoVa
         const float tp_cr = at_end ? cr : s.tp_cr[e];
         EmlocoLocoValRecord r;
         r.disc_to_pred = at_end ? s.c_disc[e] : s.tp_disc[e];
-        r.value = value[e];
         r.cr_to_pred = tp_cr;                   // :208 -- `rewards` holds the UNnormalised return
         r.loc_to_pred = at_end ? s.c_loc[e] : s.tp_loc[e];
         r.pow_to_pred = at_end ? s.c_pow[e] : s.tp_pow[e];
         // :195, fp32, a true division (the reference on the CPU; torch on a GPU would multiply by the fp32 reciprocal of 110)
         r.norm = (tp_cr - kEvalMinReward) / (kEvalMaxReward - kEvalMinReward);
-        const float diff = r.value - r.norm;
-        r.sq_err = diff * diff;                 // :196, MSELoss of one element
         r.cr_end = cr;                          // :203
         r.steps = steps;                        // :204
         r.terminated = s.terminated[e];
         r.inverted = s.inverted[e];
-        records[(long)e * s.games_per_env + g] = r;
+        const long plane = (long)s.n_env * s.games_per_env;
+        for (int k = 0; k < n_nets; ++k) {
+            r.value = value_of(k)[e];
+            const float diff = r.value - r.norm;
+            r.sq_err = diff * diff;             // :196, MSELoss of one element
+            records[k * plane + (long)e * s.games_per_env + g] = r;
+        }
         s.games[e] = g + 1;
         if (g + 1 == s.games_per_env) atomicAdd(s.n_full, 1);     // an integer count: its final value does not depend on the order
     }
@@ -111,6 +114,28 @@ locoval_eval_finish_kernel(EmlocoLocoValEval s, const float *value, EmlocoLocoVa
     s.c_loc[e] = 0.0f;
     s.c_pow[e] = 0.0f;
     s.steps[e] = 0;
+}
+
+// One thread per env, after emloco_locoval_fwd_rows: the single network's records [n_env][games_per_env]
+__global__ void __launch_bounds__(256)
+locoval_eval_finish_kernel(EmlocoLocoValEval s, const float *value, EmlocoLocoValRecord *records) {
+#ifndef EMLOCO_EMU
+#pragma clang fp contract(off)
+#endif
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= s.n_env) return;
+    locoval_eval_finish_env(s, e, 1, [=](int) { return value; }, records);
+}
+
+// One thread per env, after emloco_locoval_eval_fwd_multi: records [n_nets][n_env][games_per_env]
+__global__ void __launch_bounds__(256)
+locoval_eval_finish_multi_kernel(EmlocoLocoValEval s, EmlocoLocoValNets t, EmlocoLocoValRecord *records) {
+#ifndef EMLOCO_EMU
+#pragma clang fp contract(off)
+#endif
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= s.n_env) return;
+    locoval_eval_finish_env(s, e, t.n_nets, [&](int k) { return (const float *)t.net[k].value; }, records);
 }
 
 // One workgroup: thread t sums the contiguous slots [t c, (t + 1) c) of records (env-major, game-minor; only the recorded games), then a

@@ -37,13 +37,7 @@ struct LocoValBwd {
     const float *count /* with slot: the number of slots in use */;
 };
 
-// the yaw of value_pose_net.py:76-84 (waypoint 1, epsilon guard on x)
-__device__ __forceinline__ float locoval_yaw(const float *traj, int ts) {
-    float xv = traj[ts + 0];
-    const float yv = traj[ts + 1];
-    if (fabsf(xv) < 1e-10f) xv = 1e-10f;
-    return atan2f(yv, xv);
-}
+// (the yaw itself, locoval_yaw, stands with the other shared pieces of the forwards in predictor_kernels.hip)
 // d angle / d waypoint 1 times dth, added to that waypoint's gradient (ox, oy); the guarded x carries no gradient
 __device__ __forceinline__ void locoval_yaw_bwd(const float *traj, int ts, float dth, float &ox, float &oy) {
     float xv = traj[ts], yv = traj[ts + 1];
@@ -71,37 +65,23 @@ locoval_pose_fwd_kernel(LocoValFwd a) {
     const float ang = locoval_yaw(tr, a.ts);
     const float c = cosf(ang), s = sinf(ang);
     if (lane == 0 && a.angle) a.angle[i] = ang;
-    if (lane < 13) {
-        const float px = tr[lane * a.ts], py = tr[lane * a.ts + 1];
-        x[2 * lane] = px * c + py * s;
-        x[2 * lane + 1] = -px * s + py * c;
-    }
-    if (lane < 24) {
-        const bool hidden = lane == 4 || lane == 8 || lane == 9 || lane == 10 || lane == 11;
-        const float px = po[lane * 3], py = po[lane * 3 + 1], pz = po[lane * 3 + 2];
-        x[26 + lane * 3] = hidden ? 0.0f : px * c + py * s;
-        x[26 + lane * 3 + 1] = hidden ? 0.0f : -px * s + py * c;
-        x[26 + lane * 3 + 2] = hidden ? 0.0f : pz;
-    }
+    if (lane < 13) locoval_norm_traj(lane, tr, a.ts, c, s, x);
+    if (lane < 24) locoval_norm_pose(lane, po, c, s, x + 26);
     __syncthreads();
     for (int k = lane; k < LVP_IN; k += 64) a.x[(long)i * LVP_IN + k] = x[k];
     if (lane < LVP_H1) {
-        float acc = a.b1[lane];
-        for (int k = 0; k < LVP_IN; ++k) acc += a.w1[lane * LVP_IN + k] * x[k];
-        acc = acc > 0.0f ? acc : 0.0f;
+        const float acc = locoval_unit<LVP_IN>(a.b1[lane], a.w1 + lane * LVP_IN, 1, x);
         h1[lane] = acc; a.h1[(long)i * LVP_H1 + lane] = acc;
     }
     __syncthreads();
     if (lane < LVP_H2) {
-        float acc = a.b2[lane];
-        for (int k = 0; k < LVP_H1; ++k) acc += a.w2[lane * LVP_H1 + k] * h1[k];
-        acc = acc > 0.0f ? acc : 0.0f;
+        const float acc = locoval_unit<LVP_H1>(a.b2[lane], a.w2 + lane * LVP_H1, 1, h1);
         h2[lane] = acc; a.h2[(long)i * LVP_H2 + lane] = acc;
     }
     __syncthreads();
     float p = lane < LVP_H2 ? a.w3[lane] * h2[lane] : 0.0f;
     p = wave_sum(p);
-    if (lane == 0) a.value[i] = 1.0f / (1.0f + expf(-(p + a.b3[0])));
+    if (lane == 0) a.value[i] = locoval_head(p, a.b3[0]);
 }
 
 // this sample's parameter-gradient share to ws[row][5953] and d traj (locoval_bwd_kernel without the velocity terms)
@@ -203,16 +183,8 @@ locoval_row_fwd_kernel(LocoValFwd a) {
         const float ang = locoval_yaw(tr, a.ts);
         const float c = cosf(ang), s = sinf(ang);
         if (l == 0 && a.angle) a.angle[i] = ang;
-        if (l < 13) {
-            const float px = tr[l * a.ts], py = tr[l * a.ts + 1];
-            xs[sm][2 * l] = px * c + py * s;
-            xs[sm][2 * l + 1] = -px * s + py * c;
-        }
-        if (VEL && l == 13) {
-            const float *ve = a.vel + (long)i * 2;
-            xs[sm][IN - 2] = ve[0] * c + ve[1] * s;
-            xs[sm][IN - 1] = -ve[0] * s + ve[1] * c;
-        }
+        if (l < 13) locoval_norm_traj(l, tr, a.ts, c, s, xs[sm]);
+        if (VEL && l == 13) locoval_norm_vel(a.vel + (long)i * 2, c, s, xs[sm] + IN - 2);
         if (a.pose_rot)
             for (int j = l; j < 24; j += 16) {
                 const float *po = a.pose + (long)i * 72 + j * 3;
@@ -227,23 +199,19 @@ locoval_row_fwd_kernel(LocoValFwd a) {
     if (act) {
         for (int k = l; k < IN; k += 16) a.x[(long)i * IN + k] = xs[sm][k];
         if (l < H1) {
-            float acc = b1s[l];
-            for (int k = 0; k < IN; ++k) acc += w1t[k * 16 + l] * xs[sm][k];
-            acc = acc > 0.0f ? acc : 0.0f;
+            const float acc = locoval_unit<IN>(b1s[l], w1t + l, 16, xs[sm]);
             h1s[sm][l] = acc; a.h1[(long)i * H1 + l] = acc;
         }
     }
     __syncthreads();
     if (act && l < H2) {
-        float acc = b2s[l];
-        for (int k = 0; k < H1; ++k) acc += w2s[l * H1 + k] * h1s[sm][k];
-        acc = acc > 0.0f ? acc : 0.0f;
+        const float acc = locoval_unit<H1>(b2s[l], w2s + l * H1, 1, h1s[sm]);
         h2s[sm][l] = acc; a.h2[(long)i * H2 + l] = acc;
     }
     __syncthreads();
     float p = (act && l < H2) ? w3s[l] * h2s[sm][l] : 0.0f;
     p = row_sum(p);
-    if (act && l == 0) a.value[i] = 1.0f / (1.0f + expf(-(p + b3s[0])));
+    if (act && l == 0) a.value[i] = locoval_head(p, b3s[0]);
 }
 
 template <int VEL> __global__ void __launch_bounds__(256)

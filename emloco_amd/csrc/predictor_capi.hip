@@ -459,6 +459,24 @@ int emloco_locoval_variant_fwd_rows(int variant, int B, const float *traj, int t
     return 0;
 }
 
+// the evaluation's forward for a table of networks (locoval_multi.h; the other emloco_locoval_eval_* entry points: eval_capi.hip)
+int emloco_locoval_eval_fwd_multi(const EmlocoLocoValEval *s, const EmlocoLocoValNets *nets, void *stream) {
+    if (!s || s->n_env < 1 || !nets || !s->traj13 || !s->pose || !s->vel || !s->row_mask)
+        return pfail(-1, "emloco_locoval_eval_fwd_multi: bad argument");
+    if (nets->n_nets < 1 || nets->n_nets > EMLOCO_EVAL_MAX_NETS)
+        return pfail(-1, "emloco_locoval_eval_fwd_multi: n_nets outside 1 .. EMLOCO_EVAL_MAX_NETS");
+    for (int k = 0; k < nets->n_nets; ++k) {
+        const EmlocoLocoValNet &n = nets->net[k];
+        emloco::LocoValDims d;
+        if (!emloco::locoval_dims(n.variant, &d) || !n.w1 || !n.b1 || !n.w2 || !n.b2 || !n.w3 || !n.b3 || !n.value)
+            return pfail(-1, "emloco_locoval_eval_fwd_multi: a network with a bad variant or a NULL pointer");
+    }
+    hipLaunchKernelGGL(emloco::locoval_eval_fwd_multi_kernel, dim3((unsigned)s->n_env), dim3(64), 0, (hipStream_t)stream, (int)s->n_env,
+                       (const float *)s->traj13, (const float *)s->pose, (const float *)s->vel, (const float *)s->row_mask, *nets);
+    PHIPCHK(hipGetLastError());
+    return 0;
+}
+
 int emloco_locoval_variant_fwd(int variant, int B, const float *traj, int traj_stride, const float *pose, const float *vel, const float *w1,
                                const float *b1, const float *w2, const float *b2, const float *w3, const float *b3, float *value, float *x,
                                float *h1, float *h2, float *angle, float *pose_rot, void *stream) {

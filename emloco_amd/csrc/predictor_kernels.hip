@@ -1385,31 +1385,52 @@ rms_merge_kernel(int chunks, int cols, const double *part, double *mean, double 
 #define LV_H1 49
 #define LV_H2 24
 
+// The pieces every LocoVal forward is made of (the full kernel below, the reduced-input kernels of locoval_variants.h and the
+// evaluation's several-networks kernel of locoval_multi.h call these and nothing else for their arithmetic: one statement of each
+// expression, so the same inputs give the same bits whichever kernel runs them).
+// the yaw of value_pose_net.py:76-84 (waypoint 1, epsilon guard on x)
+__device__ __forceinline__ float locoval_yaw(const float *traj, int ts) {
+    float xv = traj[ts + 0];
+    const float yv = traj[ts + 1];
+    if (fabsf(xv) < 1e-10f) xv = 1e-10f;
+    return atan2f(yv, xv);
+}
+// bmm(v, R) with R = [[c, -s], [s, c]]:  (x, y) -> (x c + y s, -x s + y c)   (:92-100)
+__device__ __forceinline__ void locoval_norm_traj(int l /* waypoint < 13 */, const float *traj, int ts, float c, float s, float *x) {
+    const float px = traj[l * ts], py = traj[l * ts + 1];
+    x[2 * l] = px * c + py * s;
+    x[2 * l + 1] = -px * s + py * c;
+}
+// x = the 72 pose inputs; the hidden joints zeroed (:141-144)
+__device__ __forceinline__ void locoval_norm_pose(int j /* joint < 24 */, const float *pose, float c, float s, float *x) {
+    const bool hidden = j == 4 || j == 8 || j == 9 || j == 10 || j == 11;
+    const float px = pose[j * 3], py = pose[j * 3 + 1], pz = pose[j * 3 + 2];
+    x[j * 3] = hidden ? 0.0f : px * c + py * s;
+    x[j * 3 + 1] = hidden ? 0.0f : -px * s + py * c;
+    x[j * 3 + 2] = hidden ? 0.0f : pz;
+}
+__device__ __forceinline__ void locoval_norm_vel(const float *vel, float c, float s, float *x /* the 2 velocity inputs */) {
+    x[0] = vel[0] * c + vel[1] * s;
+    x[1] = -vel[0] * s + vel[1] * c;
+}
+// one unit of a ReLU layer: relu(b + sum_k w[k ws] x[k]), k ascending
+template <int N> __device__ __forceinline__ float locoval_unit(float b, const float *w, int ws, const float *x) {
+    float a = b;
+    for (int k = 0; k < N; ++k) a += w[k * ws] * x[k];
+    return a > 0.0f ? a : 0.0f;
+}
+// the output layer after its sum over the units (p) : sigmoid(p + b3)
+__device__ __forceinline__ float locoval_head(float p, float b3) { return 1.0f / (1.0f + expf(-(p + b3))); }
+
 // value_pose_net.py:73-103 _rotate_normalization + :141-147 forward_full input assembly
 __device__ __forceinline__ void locoval_input(int lane, const float *traj, int ts, const float *pose, const float *vel,
                                               float *x /* LDS [100] */, float *ang_out) {
-    float xv = traj[ts + 0], yv = traj[ts + 1];
-    if (fabsf(xv) < 1e-10f) xv = 1e-10f;                 // epsilon guard on x (:79-83)
-    const float ang = atan2f(yv, xv);
+    const float ang = locoval_yaw(traj, ts);
     const float c = cosf(ang), s = sinf(ang);
     if (lane == 0 && ang_out) *ang_out = ang;
-    // bmm(v, R) with R = [[c, -s], [s, c]]:  (x, y) -> (x c + y s, -x s + y c)
-    if (lane < 13) {
-        const float px = traj[lane * ts], py = traj[lane * ts + 1];
-        x[2 * lane] = px * c + py * s;
-        x[2 * lane + 1] = -px * s + py * c;
-    }
-    if (lane < 24) {
-        const bool hidden = lane == 4 || lane == 8 || lane == 9 || lane == 10 || lane == 11;
-        const float px = pose[lane * 3], py = pose[lane * 3 + 1], pz = pose[lane * 3 + 2];
-        x[26 + lane * 3] = hidden ? 0.0f : px * c + py * s;
-        x[26 + lane * 3 + 1] = hidden ? 0.0f : -px * s + py * c;
-        x[26 + lane * 3 + 2] = hidden ? 0.0f : pz;
-    }
-    if (lane == 0) {
-        x[98] = vel[0] * c + vel[1] * s;
-        x[99] = -vel[0] * s + vel[1] * c;
-    }
+    if (lane < 13) locoval_norm_traj(lane, traj, ts, c, s, x);
+    if (lane < 24) locoval_norm_pose(lane, pose, c, s, x + 26);
+    if (lane == 0) locoval_norm_vel(vel, c, s, x + 98);
 }
 
 __global__ void __launch_bounds__(64)
@@ -1426,22 +1447,18 @@ locoval_fwd_kernel(int B, const float *traj, int ts, const float *pose, const fl
     __syncthreads();
     for (int k = lane; k < LV_IN; k += 64) x100[(long)i * LV_IN + k] = x[k];
     if (lane < LV_H1) {
-        float a = b1[lane];
-        for (int k = 0; k < LV_IN; ++k) a += w1[lane * LV_IN + k] * x[k];
-        a = a > 0.0f ? a : 0.0f;
+        const float a = locoval_unit<LV_IN>(b1[lane], w1 + lane * LV_IN, 1, x);
         h1[lane] = a; h1o[(long)i * LV_H1 + lane] = a;
     }
     __syncthreads();
     if (lane < LV_H2) {
-        float a = b2[lane];
-        for (int k = 0; k < LV_H1; ++k) a += w2[lane * LV_H1 + k] * h1[k];
-        a = a > 0.0f ? a : 0.0f;
+        const float a = locoval_unit<LV_H1>(b2[lane], w2 + lane * LV_H1, 1, h1);
         h2[lane] = a; h2o[(long)i * LV_H2 + lane] = a;
     }
     __syncthreads();
     float p = lane < LV_H2 ? w3[lane] * h2[lane] : 0.0f;
     p = wave_sum(p);
-    if (lane == 0) value[i] = 1.0f / (1.0f + expf(-(p + b3[0])));
+    if (lane == 0) value[i] = locoval_head(p, b3[0]);
 }
 
 // per-sample backward: writes this sample's parameter-gradient contribution to ws[i][6174] and d traj
@@ -1686,3 +1703,4 @@ __global__ void adam_flat_kernel(long n, float *p, float *g, float *m, float *v,
 }  // namespace emloco
 
 #include "locoval_variants.h"       // the reduced-input LocoVal networks beside locoval_fwd_kernel / locoval_bwd_kernel
+#include "locoval_multi.h"          // several LocoVal networks on the same rows in one launch (the evaluation, run.py --compare_valuenet)

@@ -14,6 +14,13 @@ games -- into a slot of its own (records[env][game]: fixed order, deterministic)
 nothing more.  The host reads one device counter (envs whose quota is met) every `poll_every` steps and nothing else until the end,
 when one launch reduces the records to a moment vector (in double, fixed order); ranks all-reduce that vector once, and
 `report_from_moments` turns it into the reference's numbers and printed lines.
+
+Several networks (a list for `valuenet`; `run.py --compare_valuenet`): the games are played once and every network is scored on exactly
+those games.  What the bookkeeping keeps per game does not depend on the network, so the step is still three launches
+(emloco_locoval_eval_step -> emloco_locoval_eval_fwd_multi -> emloco_locoval_eval_finish_multi: the staged inputs are normalised once
+per row and every network of the table evaluated on them, each game recorded once per network), the records are N planes that differ
+in `value` and `sq_err` alone and equal bit for bit what N single-network runs on the same games record, and `paired_from_records`
+compares the networks game by game.
 """
 import math
 
@@ -99,13 +106,37 @@ def report_from_moments(m):
     return r
 
 
+SHARED_FIELDS = tuple(k for k in RECORD_DTYPE.names if k not in ("value", "sq_err"))      # the same in every network's plane
+
+
+def paired_from_records(recs):
+    """The comparison of N networks scored on the same games, in float64 from their record arrays (one per network, the same games
+    in the same order): per network the MSE (mean of `sq_err`) and Pearson r of `value` against the return up to step_to_pred, and
+    for each pair a < b the differences b - a.  The games count is the same for every network by construction; a difference in it
+    or in any shared column is an error."""
+    n = len(recs[0])
+    for r in recs[1:]:
+        assert len(r) == n, "the networks of one evaluation record the same games"
+        for k in SHARED_FIELDS:
+            assert np.array_equal(r[k], recs[0][k]), f"record column {k} differs between networks scored on the same games"
+    mse, corr = [], []
+    for r in recs:
+        v, y = r["value"].astype(np.float64), r["cr_to_pred"].astype(np.float64)
+        mse.append(float(np.mean(r["sq_err"].astype(np.float64))) if n else float("nan"))
+        ok = n > 1 and v.std() > 0 and y.std() > 0
+        corr.append(float(np.corrcoef(v, y)[0, 1]) if ok else float("nan"))
+    pairs = [dict(a=a, b=b, d_mse=mse[b] - mse[a], d_corr_total=corr[b] - corr[a]) for a in range(len(recs)) for b in range(a + 1, len(recs))]
+    return dict(games=int(n), mse=mse, corr_total=corr, pairs=pairs)
+
+
 class LocoValEvaluator:
     """Plays `games_num` games (all ranks together) of a frozen policy and scores a LocoVal network on them.
 
     vec_env: the RLGPUEnv / VecTaskPythonWrapper of the task (this rank's shard of the envs).
     policy_bundle: an AMPPolicyBundle (the deterministic action of its FrozenPolicy, the style reward of its FrozenDisc), or a
       callable obs -> actions (then `disc_reward`, a callable amp_obs -> (E,), or None for a style reward of 0).
-    valuenet: a ValuePoseNet on the task's device (the fused HIP forward evaluates it).
+    valuenet: a ValuePoseNet on the task's device (the fused HIP forward evaluates it), or a list of 1 .. EVAL_MAX_NETS of them (any
+      variants): all are scored on the same games, and `report` / `records` answer per network.
     max_steps: the step cap of the reference's player (rl_games BasePlayer: 27 000); a run whose games never finish stops there and
       the report states the shortfall."""
 
@@ -117,7 +148,11 @@ class LocoValEvaluator:
         self.env, self.task = env, env.task
         task = self.task
         self.device = torch.device(task.device)
-        if self.device.type != "cuda" or not isinstance(valuenet, ValuePoseNet):
+        self.multi = isinstance(valuenet, (list, tuple))
+        nets = list(valuenet) if self.multi else [valuenet]
+        if self.multi and not 1 <= len(nets) <= ops.EVAL_MAX_NETS:
+            raise ValueError(f"LocoValEvaluator: {len(nets)} networks; one evaluation scores 1 to {ops.EVAL_MAX_NETS}")
+        if self.device.type != "cuda" or not all(isinstance(n, ValuePoseNet) for n in nets):
             raise RuntimeError("LocoValEvaluator runs its bookkeeping and the LocoVal forward as HIP kernels: it needs a gfx950 device, "
                                "libemloco_hip.so and the HIP ValuePoseNet (there is no CPU path in the product)")
         for flag in ("fused_chain", "overlap_obs", "overlap_reset"):
@@ -129,7 +164,7 @@ class LocoValEvaluator:
             task.enable_amp_ring(False)
         if int(games_num) < 1:
             raise ValueError("games_num must be at least 1")
-        self.valuenet = valuenet
+        self.valuenets, self.valuenet = nets, nets[0]
         if hasattr(policy_bundle, "frozen"):
             bundle = policy_bundle
             self.policy = lambda obs: bundle.frozen.act(obs, deterministic=True, generator=bundle.generator)
@@ -154,10 +189,22 @@ class LocoValEvaluator:
                            tp_loc=f(E), tp_pow=f(E), steps=i32(E), games=i32(E), done=u8(E), terminated=u8(E), inverted=u8(E),
                            n_full=i32(1), traj13=f(E, 13, 3), pose=f(E, 24, 3), vel=f(E, 2), row_mask=f(E))
         # the forward's persistent output (a game's prediction stays in its row until the game is recorded) and its scratch rows
-        n_in, n_h1, n_h2, _ = ops.locoval_dims(valuenet.variant)          # the network's input configuration (value_pose_net.py:43-52)
-        self._value, self._x100, self._h1, self._h2, self._ang = f(E), f(E, n_in), f(E, n_h1), f(E, n_h2), f(E)
-        self._records = torch.zeros(E * G * RECORD_WORDS, dtype=torch.int32, device=dev)
-        self._moments = torch.zeros(ops.EVAL_MOMENTS, dtype=torch.float64, device=dev)
+        N = len(nets)
+        if self.multi:          # a value plane and a record plane per network: the table of emloco_locoval_eval_fwd_multi / _finish_multi
+            self._values = f(N, E)
+            self._records = torch.zeros(N * E * G * RECORD_WORDS, dtype=torch.int32, device=dev)
+            self._moments = torch.zeros(N, ops.EVAL_MOMENTS, dtype=torch.float64, device=dev)
+            self._nets = ops.LocoValNets(n_nets=N)
+            self._net_weights = []
+            for k, net in enumerate(nets):
+                w = self._weights(net)
+                self._net_weights.append(w)
+                self._nets.net[k] = ops.LocoValNet(net.variant, 0, *[t.data_ptr() for t in w], self._values[k].data_ptr())
+        else:
+            n_in, n_h1, n_h2, _ = ops.locoval_dims(valuenet.variant)          # the network's input configuration (value_pose_net.py:43-52)
+            self._value, self._x100, self._h1, self._h2, self._ang = f(E), f(E, n_in), f(E, n_h1), f(E, n_h2), f(E)
+            self._records = torch.zeros(E * G * RECORD_WORDS, dtype=torch.int32, device=dev)
+            self._moments = torch.zeros(ops.EVAL_MOMENTS, dtype=torch.float64, device=dev)
         self._inputs = ("waypoint_traj", "init_pose", "init_vel")
         p = lambda t: t.data_ptr()
         self._s = ops.LocoValEval(E, self.step_to_pred, G, 0, self.gamma, *[p(b[k]) for k in (
@@ -173,6 +220,19 @@ class LocoValEvaluator:
         if tuple(t.shape) != want or t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device:
             raise RuntimeError(f"LocoValEvaluator: task.{name} must be a contiguous float32 {want} tensor on {self.device}")
         return t
+
+    def _weights(self, net):
+        n = net._network
+        w = [n.fc1.weight, n.fc1.bias, n.fc2.weight, n.fc2.bias, n.fc3.weight, n.fc3.bias]
+        for t in w:
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.device == self.device
+        return w
+
+    def _check_nets(self):
+        """The table holds the parameters' addresses: a network whose parameters moved since the evaluator was built is an error."""
+        for k, (net, w) in enumerate(zip(self.valuenets, self._net_weights)):
+            if any(a is not b for a, b in zip(self._weights(net), w)) or self._nets.net[k].w1 != w[0].data_ptr():
+                raise RuntimeError(f"LocoValEvaluator: the parameters of network {k} were replaced after the evaluator took their addresses")
 
     def _check_inputs(self):
         for k, ptr in zip(self._inputs, (self._s.waypoint_traj, self._s.init_pose, self._s.init_vel)):
@@ -213,6 +273,12 @@ class LocoValEvaluator:
         ops._chk(lib.emloco_locoval_eval_step(C.byref(self._s), P(reward_raw.contiguous()), P(disc), P(dones.contiguous()),
                                               P(None if terminate is None else terminate.contiguous()),
                                               P(None if inverted is None else inverted.contiguous()), st), "emloco_locoval_eval_step")
+        if self.multi:
+            self._check_nets()
+            ops._chk(lib.emloco_locoval_eval_fwd_multi(C.byref(self._s), C.byref(self._nets), st), "emloco_locoval_eval_fwd_multi")
+            ops._chk(lib.emloco_locoval_eval_finish_multi(C.byref(self._s), C.byref(self._nets), P(self._records), st),
+                     "emloco_locoval_eval_finish_multi")
+            return
         self._forward(st)
         ops._chk(lib.emloco_locoval_eval_finish(C.byref(self._s), P(self._value), P(self._records), st), "emloco_locoval_eval_finish")
 
@@ -253,6 +319,15 @@ class LocoValEvaluator:
         from ..predictor import ops
         from ..sim import current_stream_handle
         P = lambda t: C.c_void_p(t.data_ptr())
+        if self.multi:                              # one reduction per record plane -> [N][EVAL_MOMENTS], still one collective
+            rec = self._records.view(len(self.valuenets), -1)
+            for k in range(len(self.valuenets)):
+                ops._chk(ops._lib().emloco_locoval_eval_reduce(self.num_envs, self.games_per_env, P(rec[k]), P(self._b["games"]),
+                                                               P(self._moments[k]), current_stream_handle(self.device)),
+                         "emloco_locoval_eval_reduce")
+            m = self._moments.clone()
+            D.all_reduce_(m)
+            return m.cpu().numpy()
         ops._chk(ops._lib().emloco_locoval_eval_reduce(self.num_envs, self.games_per_env, P(self._records), P(self._b["games"]),
                                                        P(self._moments), current_stream_handle(self.device)), "emloco_locoval_eval_reduce")
         m = self._moments.clone()
@@ -260,7 +335,28 @@ class LocoValEvaluator:
         return m.cpu().numpy()
 
     def report(self, say=print):
-        m = self.moments()
+        """One network: the report dict.  A list of networks: {"networks": [the report of each, as a single run of it gives],
+        "paired": paired_from_records of all ranks' records}; the lines of every network are said under a `network k` heading."""
+        if not self.multi:
+            return self._report(self.moments(), say)
+        reps = []
+        for k, m in enumerate(self.moments()):
+            if say is not None:
+                say(f"network {k} (variant {self.valuenets[k].variant}: {self.valuenets[k].layer_sizes[0]} inputs)")
+            reps.append(self._report(m, say))
+        recs = self.records()
+        if D.is_distributed():                      # the paired block covers the games of every rank, as the moments do
+            parts = [None] * D.world_size()
+            torch.distributed.all_gather_object(parts, recs)
+            recs = [np.concatenate([p[k] for p in parts]) for k in range(len(recs))]
+        paired = paired_from_records(recs)
+        assert all(r["games"] == paired["games"] for r in reps), "every network is scored on the same games"
+        if say is not None:
+            for pr in paired["pairs"]:
+                say(f"network {pr['b']} - network {pr['a']}: MSE {pr['d_mse']:+.6f}, Pearson r (total) {pr['d_corr_total']:+.4f}")
+        return {"networks": reps, "paired": paired}
+
+    def _report(self, m, say):
         rep = report_from_moments(m)
         full = torch.tensor([float(self.envs_full()), float(self.steps_run)], dtype=torch.float64, device=self.device)
         D.all_reduce_(full)
@@ -282,11 +378,22 @@ class LocoValEvaluator:
                 say(ln)
         return rep
 
-    def records(self):
-        """This rank's recorded games as a numpy structured array (RECORD_DTYPE) with `env` and `game` columns, env-major."""
+    def records(self, net=None):
+        """This rank's recorded games as a numpy structured array (RECORD_DTYPE) with `env` and `game` columns, env-major.  With a list
+        of networks: the list of their N arrays (the same games in the same order; `value` and `sq_err` are the network's), or the
+        array of network `net`."""
         E, G = self.num_envs, self.games_per_env
-        raw = self._records.cpu().numpy().view(RECORD_DTYPE).reshape(E, G)
-        games = self._b["games"].cpu().numpy()
+        if self.multi:
+            planes = self._records.cpu().numpy().view(RECORD_DTYPE).reshape(len(self.valuenets), E, G)
+            games = self._b["games"].cpu().numpy()
+            out = [self._records_of(planes[k], games) for k in (range(len(planes)) if net is None else [net])]
+            return out if net is None else out[0]
+        assert net in (None, 0)
+        return self._records_of(self._records.cpu().numpy().view(RECORD_DTYPE).reshape(E, G), self._b["games"].cpu().numpy())
+
+    @staticmethod
+    def _records_of(raw, games):
+        G = raw.shape[1]
         env, game = np.nonzero(np.arange(G)[None, :] < games[:, None])
         rec = raw[env, game]
         out = np.zeros(len(rec), dtype=[(k, RECORD_DTYPE.fields[k][0]) for k in RECORD_DTYPE.names] + [("env", "<i4"), ("game", "<i4")])

@@ -8,10 +8,11 @@ runs the LocoVal rollout loop of `learning/locoval_rollout.py` (AMPValueAgent.pl
 frozen random-init policy, and prints the reference's `fps_step` counter (common_agent.py:187).
 
     python -m emloco_amd.run --test --num_envs 4096 --policy_checkpoint policy.pth --valuenet_path LocoVal.pth \
-        [--games_num N] [--eval_out report.json] [--eval_records games.npz]
+        [--games_num N] [--eval_out report.json] [--eval_records games.npz] [--compare_valuenet Other.pth ...]
 
 is the reference's `pacer/run.py --test --valuenet_path ...` (AMPPlayerContinuousValue.run): the frozen policy plays
-deterministically and LocoVal is scored against the discounted returns of the games (`learning/locoval_eval.py`).
+deterministically and LocoVal is scored against the discounted returns of the games (`learning/locoval_eval.py`).  Every `--compare_valuenet` adds a network (its input configuration read off its fc1 width) that is
+scored on the very same games, played once: the input ablation on one set of trajectories.
 """
 import random
 import sys
@@ -90,6 +91,36 @@ def _pop_opt(argv, name, default=None):
     return default
 
 
+LOCOVAL_WIDTHS = {100: 3, 98: 2, 28: 1, 26: 0}          # fc1 width -> variant (use_pose << 1) | use_vel (value_pose_net.py:43-50)
+MAX_NETS = 8                                             # EMLOCO_EVAL_MAX_NETS
+
+
+def _pop_all(argv, name):
+    """Remove every `name VALUE` from argv and return the VALUEs in order."""
+    out = []
+    while name in argv:
+        out.append(_pop_opt(argv, name))
+    return out
+
+
+def load_compare_valuenets(paths):
+    """The checkpoints of --compare_valuenet on the host: [(path, variant, state dict)], the variant inferred from the fc1 width.  A file
+    whose width is no LocoVal network's, or a network beyond the eighth of the run (--valuenet_path counts), stops the run."""
+    out = []
+    for i, path in enumerate(paths):
+        if 1 + i >= MAX_NETS:
+            raise SystemExit(f"run.py --test: --compare_valuenet {path} is network {2 + i} of the run; one run scores at most {MAX_NETS} "
+                             "(--valuenet_path and seven --compare_valuenet)")
+        state = torch.load(path, map_location="cpu")
+        fc1 = state.get("_network.fc1.weight") if hasattr(state, "get") else None
+        width = int(fc1.shape[1]) if fc1 is not None and fc1.dim() == 2 else None
+        if width not in LOCOVAL_WIDTHS:
+            raise SystemExit(f"run.py --test: --compare_valuenet {path}: fc1 has {width} inputs, no LocoVal network's "
+                             f"({' / '.join(str(w) for w in LOCOVAL_WIDTHS)})")
+        out.append((path, LOCOVAL_WIDTHS[width], state))
+    return out
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     # --test (the reference's player, amp_value_players.py): its own options, checked before anything touches a device
@@ -97,6 +128,9 @@ def main(argv=None):
     eval_out = _pop_opt(argv, "--eval_out")
     eval_records = _pop_opt(argv, "--eval_records")
     max_steps = _pop_opt(argv, "--max_steps")
+    compare = _pop_all(argv, "--compare_valuenet")
+    if compare and "--test" not in argv:
+        raise SystemExit("run.py: --compare_valuenet adds networks to the evaluation of --test")
     if "--test" in argv:
         vp = _pop_opt(list(argv), "--valuenet_path", "")
         if not vp:
@@ -106,6 +140,7 @@ def main(argv=None):
             raise SystemExit("run.py --test: give the policy to play, --policy_checkpoint <policy.pth> or --policy_random_init")
         if "--train_policy" in argv:
             raise SystemExit("run.py: --test and --train_policy exclude each other")
+        compare = load_compare_valuenets(compare)
     from . import configure_runtime
     configure_runtime()                                  # entry point: 16 hardware queues, ahead of the first GPU call (emloco_amd/__init__.py)
     steps = 100
@@ -144,7 +179,7 @@ def main(argv=None):
     env = RLGPUEnv(create_rlgpu_env(args, cfg, cfg_train, rank=rank))
     say = print if rank == 0 else (lambda *a, **k: None)
     if args.test:
-        _run_test(args, env, policy_ckpt, games_num, max_steps, eval_out, eval_records, rank, world, say)
+        _run_test(args, env, policy_ckpt, games_num, max_steps, eval_out, eval_records, rank, world, say, compare)
         return
     if train_policy:
         import yaml
@@ -181,7 +216,7 @@ def main(argv=None):
         torch.distributed.destroy_process_group()
 
 
-def _run_test(args, env, policy_ckpt, games_num, max_steps, eval_out, eval_records, rank, world, say):
+def _run_test(args, env, policy_ckpt, games_num, max_steps, eval_out, eval_records, rank, world, say, compare=()):
     """--test: LocoValEvaluator with the frozen policy (deterministic actions) and the LocoVal network of --valuenet_path."""
     import json
     import yaml
@@ -208,6 +243,10 @@ def _run_test(args, env, policy_ckpt, games_num, max_steps, eval_out, eval_recor
         raise SystemExit(f"run.py --test: --valuenet_path {args.valuenet_path} does not fit --input_init_pose={use_pose} "
                          f"--input_init_vel={use_vel}: {e}")
     valuenet.eval()
+    if compare:
+        _run_compare(args, env, bundle, valuenet, compare, int(games_num) if games_num else int(player.get("games_num", 200)),
+                     int(max_steps) if max_steps else 27000, float(config.get("gamma", 0.99)), eval_out, eval_records, rank, world, say)
+        return
     ev = LocoValEvaluator(env, bundle, valuenet, int(games_num) if games_num else int(player.get("games_num", 200)),
                           max_steps=int(max_steps) if max_steps else 27000, gamma=float(config.get("gamma", 0.99)))
     t0 = time.time()
@@ -230,6 +269,57 @@ def _run_test(args, env, policy_ckpt, games_num, max_steps, eval_out, eval_recor
     if eval_out and rank == 0:
         with open(eval_out, "w") as f:
             json.dump({k: v for k, v in rep.items()}, f, indent=1, default=float)
+    if world > 1:
+        torch.distributed.destroy_process_group()
+
+
+def compare_columns(recs):
+    """The --eval_records columns of N networks' record arrays (the same games): the shared per-game columns once, `value_<i>` and
+    `sq_err_<i>` per network."""
+    cols = {k: recs[0][k] for k in recs[0].dtype.names if k not in ("value", "sq_err")}
+    for i, r in enumerate(recs):
+        cols[f"value_{i}"], cols[f"sq_err_{i}"] = r["value"], r["sq_err"]
+    return cols
+
+
+def _run_compare(args, env, bundle, valuenet, compare, games_num, max_steps, gamma, eval_out, eval_records, rank, world, say):
+    """--test with --compare_valuenet: the network of --valuenet_path and the added ones on the same games, played once."""
+    import json
+    from .learning.locoval_eval import LocoValEvaluator
+    from .learning.value_pose_net import ValuePoseNet
+    task = env.env.task
+    nets, paths = [valuenet], [args.valuenet_path]
+    for path, variant, state in compare:
+        with torch.random.fork_rng(devices=[]):             # an added network's initialisation draws nothing from the run's random stream
+            net = ValuePoseNet(use_pose=bool(variant & 2), use_vel=bool(variant & 1)).to(task.device)
+        try:
+            net.load_state_dict(state)
+        except RuntimeError as e:
+            raise SystemExit(f"run.py --test: --compare_valuenet {path} does not load as the network its fc1 width names: {e}")
+        nets.append(net.eval())
+        paths.append(path)
+    ev = LocoValEvaluator(env, bundle, nets, games_num, max_steps=max_steps, gamma=gamma)
+    t0 = time.time()
+    rep = ev.run(say=say)
+    torch.cuda.synchronize()
+    seconds = time.time() - t0
+    say(f"{ev.steps_run} steps of {ev.envs_total} envs in {seconds:.2f} s, {len(nets)} networks on the same games")
+    if eval_records:
+        parts = [compare_columns(ev.records())]
+        if world > 1:
+            gathered = [None] * world
+            torch.distributed.all_gather_object(gathered, parts[0])
+            parts = gathered
+        if rank == 0:
+            cols = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
+            cols["rank"] = np.concatenate([np.full(len(p["env"]), r, np.int32) for r, p in enumerate(parts)])
+            np.savez(eval_records, **cols)
+    if eval_out and rank == 0:
+        for r in rep["networks"]:
+            r["seconds"] = seconds
+        with open(eval_out, "w") as f:
+            json.dump({"networks": [dict(path=p, variant=n.variant, report=r) for p, n, r in zip(paths, nets, rep["networks"])],
+                       "paired": rep["paired"]}, f, indent=1, default=float)
     if world > 1:
         torch.distributed.destroy_process_group()
 

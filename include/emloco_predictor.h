@@ -418,6 +418,39 @@ int emloco_locoval_eval_finish(const EmlocoLocoValEval *s, const float *value, E
 int emloco_locoval_eval_reduce(int n_env, int games_per_env, const EmlocoLocoValRecord *records, const int32_t *games,
                                double *moments, void *stream);
 
+/* Several LocoVal networks scored on the SAME games (`run.py --test --valuenet_path A --compare_valuenet B ...`: the input ablation
+ * of value_pose_net.py:22-50 read off one set of trajectories).  Everything the bookkeeping keeps per game is the same whatever the
+ * network -- only `value` (amp_value_players.py:128-134,206) and `sq_err` (:196) belong to a network -- so N networks share the
+ * rollout, emloco_locoval_eval_step and its staged inputs, and the step is still three launches:
+ *   emloco_locoval_eval_step -> emloco_locoval_eval_fwd_multi -> emloco_locoval_eval_finish_multi
+ * The table goes to the kernels by value; its pointers are device addresses. */
+#define EMLOCO_EVAL_MAX_NETS 8
+typedef struct EmlocoLocoValNet {
+    int32_t variant;                /* EMLOCO_LOCOVAL_*, as emloco_locoval_variant_dims */
+    int32_t _pad;
+    const float *w1, *b1, *w2, *b2, *w3, *b3;       /* fc1 / fc2 / fc3 of that variant's sizes (row-major, as nn.Linear) */
+    float *value;                   /* out [n_env]: this network's value plane (kept between steps, as `value` of the single path) */
+} EmlocoLocoValNet;
+typedef struct EmlocoLocoValNets {
+    int32_t n_nets;                 /* 1 .. EMLOCO_EVAL_MAX_NETS */
+    int32_t _pad;
+    EmlocoLocoValNet net[EMLOCO_EVAL_MAX_NETS];
+} EmlocoLocoValNets;
+/* The forward of :128-134 for every network of the table on the rows with s->row_mask == 1 (the games' first steps), from the inputs
+ * emloco_locoval_eval_step staged in s->traj13 / pose / vel: they are read and yaw-normalised (value_pose_net.py:73-103) once per row,
+ * every network runs on that one vector, and nothing but the value planes is written (the reference's in-place pose rotation of
+ * :96-97 is not mirrored into the staged pose, here as in emloco_locoval_fwd_rows: no network sees what another left).  For each
+ * network the values are bit for bit those of emloco_locoval_variant_fwd_rows (emloco_locoval_fwd_rows for EMLOCO_LOCOVAL_FULL) called
+ * with that network alone; rows with mask 0 keep their values.  -1: a NULL argument, n_nets outside 1 .. EMLOCO_EVAL_MAX_NETS or a
+ * variant outside 0 .. 3. */
+int emloco_locoval_eval_fwd_multi(const EmlocoLocoValEval *s, const EmlocoLocoValNets *nets, void *stream);
+/* emloco_locoval_eval_finish for the table: a game that ended this step is recorded once per network, records[net][env][game]
+ * ([n_nets] planes of [n_env][games_per_env]), the planes equal in every field but `value` (net[k].value) and `sq_err`; `games`,
+ * `n_full` and the per-game state advance once.  Each plane goes to emloco_locoval_eval_reduce as it is.  With one network the
+ * records are those of emloco_locoval_eval_finish byte for byte.  Errors as emloco_locoval_eval_fwd_multi. */
+int emloco_locoval_eval_finish_multi(const EmlocoLocoValEval *s, const EmlocoLocoValNets *nets, EmlocoLocoValRecord *records,
+                                     void *stream);
+
 /* torch.nn.utils.clip_grad_norm_(params, max_norm) + torch.optim.Adam.step() (train_jta.py:317-318,411; train_jrdb.py likewise) on ONE
  * flat fp32 buffer of n parameters with their gradients, first and second moments laid out alike -- three launches (block sums of
  * squares, the clip coefficient from them in a fixed order, the update) where the foreach implementations issue ~25.  The gradient is
