@@ -23,7 +23,7 @@ LIB = os.path.join(LIBDIR, "libemloco_hip.so")
 # (tests/test_gpu_sim.py); eleven further scheduler / vectoriser switches were within +-1 % or worse (tools/exp/run_flag_variants.sh).
 UNITS = [
     ("sim_capi.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
-    ("task_capi.hip", ["-ffp-contract=off"]),
+    ("task_capi.hip", ["-ffp-contract=off"]),            # + traj_kernels.hip (emloco_traj_densify): fixed fp32 order, as its CPU emulation
     ("predictor_capi.hip", ["-fno-slp-vectorize"]),      # split-mode GEMMs: 183.6 -> 176.5 ms per fp32-class train step, policy 0.341 -> 0.311 ms
     ("attention_capi.hip", []),                          # the fused attention keeps the SLP vectoriser (bf16 kernels 8-18 % slower without)
     ("ffn_capi.hip", []),                                # the chained feed-forward kernels (round 5)

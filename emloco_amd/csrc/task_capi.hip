@@ -5,6 +5,7 @@
 #include "task_kernels.hip"
 #include "reset_kernels.hip"
 #include "chain_kernels.hip"
+#include "traj_kernels.hip"
 #include "sim_state.h"
 #include "../../include/emloco_predictor.h"
 
@@ -322,6 +323,21 @@ int emloco_task_reset_obs_pooled(EmlocoSim *sim, const EmlocoResetBufs *rb, cons
     const unsigned grid = (unsigned)(a.n_slots + a.h_slots * a.n_hist + (a.pool_next ? a.pool_k * 2 : 0) + (a.live_mode ? pb->n_env : 0));
     if (n == 0 && !a.live_mode && !a.pool_next) return 0;
     hipLaunchKernelGGL(emloco::reset_obs_kernel, dim3(grid), dim3(64), 0, (hipStream_t)stream, *pb, keyed, sim->dev, a);
+    THIPCHK(hipGetLastError());
+    return 0;
+}
+
+int emloco_traj_densify(const float *knot_t, int n_knots, const float *dev_way, int64_t n_traj, const float *query_t, int n_query,
+                        float *dev_out, uint8_t *dev_valid, int flags, void *stream) {
+    static_assert(EMLOCO_DENSIFY_ORIGIN == emloco::DENSIFY_FLAG_ORIGIN && EMLOCO_DENSIFY_MAX_KNOTS == emloco::DENSIFY_MAX_KNOTS &&
+                  EMLOCO_DENSIFY_MAX_QUERY == emloco::DENSIFY_MAX_QUERY, "include/emloco_task.h and traj_kernels.hip disagree");
+    emloco::DensifyArgs a;
+    const char *why = emloco::densify_pack(knot_t, n_knots, (long long)n_traj, query_t, n_query, flags, &a);
+    if (why) { char buf[128]; snprintf(buf, sizeof(buf), "emloco_traj_densify: %s", why); return tfail(-1, buf); }
+    if (n_traj == 0) return 0;
+    if (!dev_way || !dev_out) return tfail(-1, "emloco_traj_densify: null waypoints or output");
+    const unsigned grid = (unsigned)((n_traj + emloco::DENSIFY_TPB - 1) / emloco::DENSIFY_TPB);
+    hipLaunchKernelGGL(emloco::traj_densify_kernel, dim3(grid), dim3(emloco::DENSIFY_THREADS), 0, (hipStream_t)stream, a, dev_way, dev_out, dev_valid);
     THIPCHK(hipGetLastError());
     return 0;
 }

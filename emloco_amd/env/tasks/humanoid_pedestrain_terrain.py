@@ -56,7 +56,8 @@ class HumanoidPedestrianTerrain(humanoid_traj.HumanoidTraj):
         self.init_pose = torch.zeros(self.num_envs, 24, 3).to(self.device)
         self.init_vel = torch.zeros(self.num_envs, 2).to(self.device)
         self._fused_reset = bool(cfg["env"].get("fused_reset", True)) and self._state_init == self.StateInit.Random \
-            and not flags.vru and not flags.add_noise and not flags.fixed_path and not flags.slow
+            and not flags.vru and not flags.add_noise and not flags.fixed_path and not flags.slow \
+            and not flags.pred_path                  # predicted paths are placed by the host reset (TrajGenerator.reset), which knows the row
         self._reset_bufs = None
         return
 

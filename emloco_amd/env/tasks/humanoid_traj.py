@@ -31,7 +31,8 @@ class HumanoidTraj(HumanoidAMPTask):
                                                       self._speed_min, self._speed_max, self._accel_max,
                                                       self._sharp_turn_prob, self._motion_lib,
                                                       hybridInitProb=self._hybrid_init_prob, flags=flags,
-                                                      traj_data=self.cfg["env"].get("traj_data", None))
+                                                      traj_data=self.cfg["env"].get("traj_data", None),
+                                                      pred_traj_data=self.cfg["env"].get("pred_traj_data", None))
         env_ids = torch.arange(self.num_envs, device=self.device, dtype=torch.long)
         self._traj_gen.reset(env_ids, self._humanoid_root_states[:, 0:3], self._humanoid_root_states[:, 7:10],
                              self._sampled_motion_ids[env_ids], self._motion_start_times[env_ids])

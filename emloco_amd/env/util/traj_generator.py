@@ -7,17 +7,39 @@ reproduces the reference's vertices (pinned by tests/test_host_logic.py against 
 post-physics kernel and is kept here for host callers.
 
 Real-world paths (`flags.real_path`): `traj_data` is a list of dicts {id: {'traj': (>=101,3) array, 'pose': ...}}
-in the format load_jta_traj.py:109-114 writes; pass it in (or a pickle path) instead of the hard-coded files.
+in the format load_jta_traj.py:109-114 writes; pass it in (or a pickle path) instead of the hard-coded files
+(`python -m emloco_amd.predictor.export_trajs` writes them).
+
+Predicted paths (`flags.pred_path`, :53-54,163-175): `pred_traj_data` is a dict {key: {'coord_dense': (>=101,3) array, ...}} or the path
+of its pickle (`evaluate_jta --save_pred_trajs` writes one; default: the reference's data/traj/traj_pred_data.pkl).  Every env walks one
+row, sampled without replacement, moved so that its first vertex sits on the env's root position.
 """
+import os
 import random
 
 import numpy as np
 import torch
 
+PRED_TRAJ_FILE = "data/traj/traj_pred_data.pkl"          # traj_generator.py:54
+
+
+def load_pred_traj_data(src=None):
+    """The table of predicted paths: a dict as it is, a pickle path loaded; a missing file is an error that names it."""
+    src = PRED_TRAJ_FILE if src is None else src
+    if isinstance(src, (str, os.PathLike)):
+        if not os.path.isfile(src):
+            raise FileNotFoundError(f"--pred_path: the predicted-path table {src} does not exist (--pred_traj_file PATH or "
+                                    "cfg['env']['pred_traj_data'] names it; `evaluate_jta --save_pred_trajs` writes one)")
+        import joblib
+        src = joblib.load(src)
+    if not isinstance(src, dict) or not all("coord_dense" in v for v in src.values()):
+        raise ValueError("--pred_path: the predicted-path table is a dict {key: {'coord_dense': (>=101, 3) array}}")
+    return src
+
 
 class TrajGenerator():
     def __init__(self, num_envs, episode_dur, num_verts, device, dtheta_max, speed_min, speed_max, accel_max,
-                 sharp_turn_prob, motion_lib=None, hybridInitProb=0.5, flags=None, traj_data=None):
+                 sharp_turn_prob, motion_lib=None, hybridInitProb=0.5, flags=None, traj_data=None, pred_traj_data=None):
         self._device = device
         self._dt = episode_dur / (num_verts - 1)
         self._dtheta_max = dtheta_max
@@ -40,6 +62,12 @@ class TrajGenerator():
                     import joblib
                     d = joblib.load(d)
                 self.traj_data.append(d)
+        self.traj_pred_data = None
+        self.last_pred_rows = None              # table row (position in the table's key order) every env walked at its last reset
+        if self._flags is not None and getattr(self._flags, "pred_path", False):
+            self.traj_pred_data = load_pred_traj_data(pred_traj_data)
+            self.last_pred_rows = torch.full((num_envs,), -1, dtype=torch.int64)
+        self.pred_row_log = None                # a list: every reset under pred_path appends (env ids, table rows) as int64 arrays
         self.heading = torch.zeros(num_envs, 1)
 
     # ------------------------------------------------------------------ random draws, in the reference's order (:63-78)
@@ -129,6 +157,19 @@ class TrajGenerator():
             traj[..., 0:2] += init_pos[real_mask, 0:2].unsqueeze(1)
             self._verts[env_ids[real_mask]] = traj
 
+        elif getattr(f, "pred_path", False):                                        # :163-175
+            rows = d.get("pred_rids", None)                 # explicit sample: positions in the table's key order
+            if rows is None:
+                rows = self._sample_pred_rows(n)
+            rows = [int(r) for r in rows]
+            assert len(rows) == n
+            keys = list(self.traj_pred_data.keys())
+            traj = torch.stack([torch.from_numpy(np.asarray(self.traj_pred_data[keys[r]]["coord_dense"]))[:num_verts] for r in rows],
+                               dim=0).to(self._device).float()
+            traj[..., 0:2] = traj[..., 0:2] - (traj[..., 0, 0:2] - init_pos[..., 0:2])[:, None]      # no speed rescaling (:174)
+            self._verts[env_ids] = traj
+            self._note_pred_rows(env_ids, rows)
+
         if f.init_heading:                                                          # :176-235
             verts = self._verts[env_ids].clone()
             dinit = verts[:, 1, :2] - verts[:, 0, :2]
@@ -155,6 +196,26 @@ class TrajGenerator():
         if f.add_noise:
             self._verts[env_ids] += torch.randn_like(self._verts[env_ids]) * 0.5
 
+    def _sample_pred_rows(self, n):
+        """n distinct rows of the predicted-path table, as the reference's random.sample(traj_data.keys(), n) (:165)."""
+        size = len(self.traj_pred_data)
+        if n > size:
+            raise ValueError(f"--pred_path: {n} envs reset at once but the predicted-path table holds {size} rows "
+                             "(rows are sampled without replacement: the table needs at least as many rows as envs)")
+        return random.sample(range(size), n)
+
+    def _note_pred_rows(self, env_ids, rows):
+        ids = torch.as_tensor(env_ids).cpu().to(torch.int64)
+        rows = torch.as_tensor(rows, dtype=torch.int64)
+        self.last_pred_rows[ids] = rows
+        if self.pred_row_log is not None:
+            self.pred_row_log.append((ids.numpy().copy(), rows.numpy().copy()))
+
+    def pred_rows(self):
+        """The predicted paths as one (n_rows, num_verts, 3) float32 table in the table's key order."""
+        nv = self.get_num_verts()
+        return np.stack([np.asarray(v["coord_dense"], np.float32)[:nv] for v in self.traj_pred_data.values()])
+
     def real_rows(self):
         """The real paths as one (n_real, num_verts, 3) float32 table, datasets concatenated in order (row = the id
         `random.sample(range(jta_num + jrdb_num), ...)` indexes, traj_generator.py:128-143)."""
@@ -167,7 +228,13 @@ class TrajGenerator():
     def reset_on_device(self, env_ids, init_pos, root_vel, rnd=None, real_pick=None, real_pick_key=0):
         """`reset` as one kernel launch (emloco_task_traj_reset, reset_kernels.hip): random rows `rnd` [n][RESET_RND]
         uniform in [0, 1) laid out as include/emloco_task.h describes (drawn with torch.rand when omitted), real-path rows
-        from `real_pick` (int32 [n]) or the keyed permutation.  Needs the gfx950 library and CUDA tensors."""
+        from `real_pick` (int32 [n]) or the keyed permutation.  Needs the gfx950 library and CUDA tensors.
+        `flags.pred_path` goes through the same kernel's real-path table: every env takes a row (hybrid_prob -1), the speed rescaling
+        is off (:163-175); rows from `real_pick` or, when omitted, sampled on the host as `reset` samples them.  The reference places a
+        predicted row as row - (first - root) (:174), the kernel a table row as (row - first) + root: in float32 the two differ by an
+        ulp per vertex, which the heading block magnifies by the path's vertex count.  So the rows of the call are placed on the
+        device in the reference's order and handed over as the call's table with their own first vertex as the root: the kernel's
+        (v - v0) + v0 gives v back, and what reaches the heading block is what `reset` has there, bit for bit."""
         import ctypes as C
         from ... import _lib as L
         from ...sim import current_stream_handle
@@ -177,26 +244,40 @@ class TrajGenerator():
             return
         f = self._flags
         dev = self._verts.device
+        pred = bool(getattr(f, "pred_path", False)) and not f.real_path          # (`reset`: the real-path branch comes first)
+        if f.fixed_path or f.slow or f.add_noise:
+            raise NotImplementedError("reset_on_device: fixed_path / slow / add_noise stay on the host path (reset)")
         if rnd is None:
             rnd = torch.rand((n, L.RESET_RND), device=dev)
-        if getattr(self, "_real_dev", None) is None and f.real_path:
-            self._real_dev = torch.from_numpy(self.real_rows()).to(dev).contiguous()
+        if getattr(self, "_real_dev", None) is None and (f.real_path or pred):
+            self._real_dev = torch.from_numpy(self.pred_rows() if pred else self.real_rows()).to(dev).contiguous()
+        if pred and real_pick is None:
+            real_pick = torch.as_tensor(self._sample_pred_rows(n), dtype=torch.int32)
+        table = getattr(self, "_real_dev", None)
+        if pred:
+            self._note_pred_rows(env_ids, real_pick.cpu().tolist())
+            root = init_pos[:, :3].float().to(dev)
+            table = self._real_dev[real_pick.to(dev).long()]                       # (n, num_verts, 3), a copy
+            table[..., 0:2] = table[..., 0:2] - (table[..., 0, 0:2] - root[..., 0:2])[:, None]      # :174, the reference's order
+            table = table.contiguous()
+            real_pick = torch.arange(n, dtype=torch.int32, device=dev)
+            init_pos = torch.cat([table[:, 0, 0:2], root[:, 2:3]], dim=1)
         if getattr(self, "_inverted_u8", None) is None:
             self._inverted_u8 = torch.zeros(self.get_num_envs(), dtype=torch.uint8, device=dev)
         self._inverted_u8.copy_(self.inverted.to(torch.uint8))
         b = L.ResetBufs()
         fl = (L.RESET_INIT_HEADING if f.init_heading else 0) | (L.RESET_ADJUST_ROOT_VEL if f.adjust_root_vel else 0)
         fl |= L.RESET_HEADING_INVERSION if (f.init_heading and f.heading_inversion) else 0
-        fl |= L.RESET_REAL_PATH if f.real_path else 0
-        if f.fixed_path or f.slow or f.add_noise or getattr(f, "pred_path", False):
-            raise NotImplementedError("reset_on_device: fixed_path / slow / add_noise / pred_path stay on the host path (reset)")
-        b.flags, b.n_real = fl, (int(self._real_dev.shape[0]) if f.real_path else 0)
+        fl |= L.RESET_REAL_PATH if (f.real_path or pred) else 0
+        if pred:
+            fl &= ~L.RESET_ADJUST_ROOT_VEL
+        b.flags, b.n_real = fl, (int(table.shape[0]) if (f.real_path or pred) else 0)
         b.vert_dt, b.dtheta_max, b.speed_min, b.speed_max = self._dt, self._dtheta_max, self._speed_min, self._speed_max
-        b.accel_max, b.sharp_prob, b.hybrid_prob = self._accel_max, self._sharp_turn_prob, self._hybrid_init_prob
-        b.real_traj = self._real_dev.data_ptr() if f.real_path else None
+        b.accel_max, b.sharp_prob, b.hybrid_prob = self._accel_max, self._sharp_turn_prob, (-1.0 if pred else self._hybrid_init_prob)
+        b.real_traj = table.data_ptr() if (f.real_path or pred) else None
         b.traj_verts, b.inverted = self._verts.data_ptr(), self._inverted_u8.data_ptr()
         keep = [rnd.contiguous(), env_ids.to(dev).to(torch.int32).contiguous(), init_pos[:, :3].float().contiguous(),
-                root_vel[:, :3].float().contiguous()]
+                root_vel[:, :3].float().contiguous(), table]
         if real_pick is not None:
             keep.append(real_pick.to(dev).to(torch.int32).contiguous())
             b.real_pick = keep[-1].data_ptr()

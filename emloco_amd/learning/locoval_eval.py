@@ -212,6 +212,11 @@ class LocoValEvaluator:
             "inverted", "n_full")], *[p(self._input(k)) for k in self._inputs], p(b["traj13"]), p(b["pose"]), p(b["vel"]), p(b["row_mask"]))
         self.steps_run = 0
         self.started = False
+        # --pred_path: the host reset knows which row of the predicted-path table every game walks; logged from the first reset on
+        tg = getattr(task, "_traj_gen", None)
+        self._pred_log = None
+        if tg is not None and getattr(tg, "traj_pred_data", None) is not None:
+            self._pred_log = tg.pred_row_log = []
 
     def _input(self, name):
         """The task's LocoVal inputs the kernel reads by address (15 x 3 waypoints, 24 x 3 joints, 2 velocity components per env)."""
@@ -390,6 +395,20 @@ class LocoValEvaluator:
             return out if net is None else out[0]
         assert net in (None, 0)
         return self._records_of(self._records.cpu().numpy().view(RECORD_DTYPE).reshape(E, G), self._b["games"].cpu().numpy())
+
+    def pred_rows(self, records):
+        """Under --pred_path: per record the row of the predicted-path table (position in its key order) the game walked -- game g of
+        an env follows that env's g-th reset since the evaluation began -- or None when the run walks no predicted paths."""
+        if self._pred_log is None:
+            return None
+        G = self.games_per_env
+        table = np.full((self.num_envs, G), -1, np.int64)
+        seen = np.zeros(self.num_envs, np.int64)
+        for ids, rows in self._pred_log:
+            keep = seen[ids] < G
+            table[ids[keep], seen[ids[keep]]] = rows[keep]
+            seen[ids] += 1
+        return table[records["env"], records["game"]]
 
     @staticmethod
     def _records_of(raw, games):

@@ -13,7 +13,13 @@ same inputs (each can be switched off):
   * `reference_inplace_pose`: `ValuePoseNet._rotate_normalization` rotates the caller's pose in place
     (value_pose_net.py:98), so within one sample the pose handed to call c is already rotated by the heading angles
     of all earlier calls (order: pred mode 0, gt, pred mode 1, gt, ...).
-Plots / pickles of the reference are out of scope.
+Plots of the reference are out of scope.
+
+`--save_pred_trajs FILE` keeps the predictions in the form the rollout walks (`run.py --pred_path --pred_traj_file FILE`,
+traj_generator.py:163-175): per stored (sample, mode) the last observed point and the 12 predicted points of the primary person, in
+world coordinates, through the natural cubic spline of load_jta_traj.py:93-95 to 101 vertices (`env/util/traj_densify.py`; on the
+device when the predictions are there).  `--save_pred_modes best` (default) stores per sample the mode the run keeps -- the LocoVal
+arg-max with `--valueloss`, the min-ADE mode without -- and `all` every mode.
 """
 import math
 
@@ -147,6 +153,7 @@ class EvalAccumulator:
         self.s["fde_max"] += float(fde.max(1)[0].sum())
         self.des += des.mean(2).sum(0).cpu().numpy()
         self.n["sample"] += B
+        self.last = {"pred": pred, "ade": ade, "value": None, "valid": None}      # this batch, for PredTrajCollector
         for k, v in motion_primitives(gt).items():
             self.gt_prim[k].append(v.reshape(-1))
         for k, v in motion_primitives(pred.permute(0, 2, 1, 3)).items():
@@ -185,6 +192,7 @@ class EvalAccumulator:
         values = valuenet(safe_calls, safe_pose if reads_pose else None, vel_c if reads_vel else None).reshape(B, M, 2).double()
         valuenet.inplace_pose = was_inplace
         v_pred, v_gt = values[..., 0], values[..., 1]
+        self.last.update(value=v_pred, valid=valid)
         nv = int(valid.sum())
         self.n["values"] += nv
         self.s["value"] += float((v_pred * valid).sum())
@@ -271,8 +279,64 @@ class EvalAccumulator:
         return out
 
 
+class PredTrajCollector:
+    """The predictions of an evaluation as the table `--pred_path` walks: {key: {'coord_dense': (101, 3) float64, 'sample': i, 'mode': m,
+    'ade': ..., 'locoval': ... or None}}, `coord_dense` being the key traj_generator.py:170 reads.  modes = "best": one entry per sample
+    (key i), the mode of the highest LocoVal value among the scored ones, or of the lowest ADE when no LocoVal network scores the run;
+    "all": every mode (key i * M + m).  A track with a non-finite point is left out, as load_jta_traj.py:87-89 leaves such tracks out."""
+
+    def __init__(self, modes="best"):
+        if modes not in ("best", "all"):
+            raise ValueError("--save_pred_modes is best or all")
+        self.modes, self.entries = modes, {}
+
+    @torch.no_grad()
+    def add(self, first_sample, last_observed, last):
+        """One batch: `last_observed` (B, 3) world position of the primary person at the last observed frame, `last` = what
+        EvalAccumulator.update kept of the batch (pred (B, 12, M, 2) relative to that position, ade (B, M), value / valid (B, M) or None)."""
+        from ..env.util.traj_densify import densify
+        pred, ade, value, valid = last["pred"], last["ade"], last["value"], last["valid"]
+        B, _, M, _ = pred.shape
+        org = last_observed.to(pred.device).to(pred.dtype)
+        if self.modes == "best":
+            if value is not None:
+                pick = torch.where(valid, value, torch.full_like(value, -1e30)).argmax(1)
+            else:
+                pick = torch.nan_to_num(ade, nan=1e30).argmin(1)
+            mode = pick[:, None]                                                  # (B, 1)
+        else:
+            mode = torch.arange(M, device=pred.device)[None, :].expand(B, M)
+        K = mode.shape[1]
+        sel = pred.permute(0, 2, 1, 3).gather(1, mode[:, :, None, None].expand(B, K, 12, 2))       # (B, K, 12, 2)
+        way = torch.zeros(B, K, 13, 3, device=pred.device, dtype=pred.dtype)
+        way[:, :, :, :] = org[:, None, None, :]
+        way[:, :, 1:, :2] += sel
+        dense, ok = densify(way.reshape(B * K, 13, 3), origin=False)
+        dense, ok = dense.double().cpu().numpy().reshape(B, K, -1, 3), ok.cpu().numpy().reshape(B, K)
+        ade_k = ade.gather(1, mode).cpu().numpy()
+        val_k = None if value is None else value.gather(1, mode).cpu().numpy()
+        mode = mode.cpu().numpy()
+        for b in range(B):
+            for k in range(K):
+                if not ok[b, k]:
+                    continue
+                i, m = first_sample + b, int(mode[b, k])
+                self.entries[i if self.modes == "best" else i * M + m] = {
+                    "coord_dense": dense[b, k].copy(), "sample": i, "mode": m, "ade": float(ade_k[b, k]),
+                    "locoval": None if val_k is None else float(val_k[b, k])}
+
+    def save(self, path):
+        import os
+        import pickle
+        if os.path.dirname(path):
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, "wb") as f:
+            pickle.dump(self.entries, f)
+        return path
+
+
 def evaluate_ade_fde(model, valuenet, split, modality_selection, dataloader, bs, config, logger=None, exp_name="", return_all=False,
-                     visualize=False, limit_obs=False, dataset="jta", random_ids=None, shard=None, **acc_kw):
+                     visualize=False, limit_obs=False, dataset="jta", random_ids=None, shard=None, pred_trajs=None, **acc_kw):
     """Same arguments as the reference; additionally returns the summary dict (the reference only logs it).
     Data-parallel (configs[4]): with a process group of W ranks, rank r evaluates batches r, r+W, ... (`shard=(r, W)`,
     default from torch.distributed) and the summary is all-reduced -- no tensor data crosses ranks."""
@@ -297,6 +361,8 @@ def evaluate_ade_fde(model, valuenet, split, modality_selection, dataloader, bs,
         ids = None if random_ids is None else random_ids[off:off + B]
         off += B
         acc.update(in_joints, out_joints, pred_joints, primary_init_pose, valuenet, ids, dataset)
+        if pred_trajs is not None:                                                # (a PredTrajCollector)
+            pred_trajs.add(off - B, joints[:, 0, config["TRAIN"]["input_track_size"] - 1, 0, :3], acc.last)
     res = acc.summary()
     if logger is not None:
         logger.info(f"Total samples: {res['samples']}")
@@ -340,6 +406,8 @@ def build_arg_parser():
     p.add_argument("--data_root", type=str, default="data", help="root of <dataset>/preprocess_smpl/<split>/part_*.pkl")
     p.add_argument("--out_root", type=str, default="experiments", help="root of the experiment directories")
     p.add_argument("--dataset", type=str, default="jta", choices=["jta", "jrdb"], help="evaluate_jta.py | evaluate_jrdb.py")
+    p.add_argument("--save_pred_trajs", type=str, default="", help="write the predictions as a --pred_path table (101-vertex paths) to this pickle")
+    p.add_argument("--save_pred_modes", type=str, default="best", choices=["best", "all"], help="the mode the run keeps per sample | every mode")
     return p
 
 
@@ -400,8 +468,15 @@ def run(args, logger=None):
     for obs_i in ([1, 2, 3, 4, 5, 6, 7, 8, 0] if args.all_frames else [args.limit_obs]):
         if logger is not None:
             logger.info(f"Evaluating with {9 if obs_i == 0 else obs_i} frames")
+        collector = PredTrajCollector(args.save_pred_modes) if getattr(args, "save_pred_trajs", "") else None
         out[obs_i] = evaluate_ade_fde(model, valuenet, args.split, args.modality, loader, bs, config, logger, args.exp_name, return_all=True,
-                                      limit_obs=obs_i, dataset=args.dataset)
+                                      limit_obs=obs_i, dataset=args.dataset, pred_trajs=collector)
+        if collector is not None:                                                 # (--all_frames: the last pass, all 9 frames, stays)
+            import torch.distributed as dist
+            rank = dist.get_rank() if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1 else None
+            path = collector.save(args.save_pred_trajs + ("" if rank is None else f".rank{rank}"))      # a rank holds its own batches
+            if logger is not None:
+                logger.info(f"Saved {len(collector.entries)} predicted paths to {path}")
     return out
 
 

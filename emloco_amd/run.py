@@ -9,10 +9,14 @@ frozen random-init policy, and prints the reference's `fps_step` counter (common
 
     python -m emloco_amd.run --test --num_envs 4096 --policy_checkpoint policy.pth --valuenet_path LocoVal.pth \
         [--games_num N] [--eval_out report.json] [--eval_records games.npz] [--compare_valuenet Other.pth ...]
+        [--pred_path [--pred_traj_file preds.pkl]]
 
 is the reference's `pacer/run.py --test --valuenet_path ...` (AMPPlayerContinuousValue.run): the frozen policy plays
 deterministically and LocoVal is scored against the discounted returns of the games (`learning/locoval_eval.py`).  Every `--compare_valuenet` adds a network (its input configuration read off its fc1 width) that is
-scored on the very same games, played once: the input ablation on one set of trajectories.
+scored on the very same games, played once: the input ablation on one set of trajectories.  `--pred_path` makes the humanoid walk the
+predictor's output (traj_generator.py:53-54,163-175): the table `evaluate_jta --save_pred_trajs` writes, named by `--pred_traj_file`
+(default data/traj/traj_pred_data.pkl); `--eval_records` then carries the table row of every game as `pred_row`.  `--real_path JTA`
+takes its tables (`python -m emloco_amd.predictor.export_trajs`) from `--real_traj_file a.pkl[,b.pkl]`.
 """
 import random
 import sys
@@ -176,6 +180,13 @@ def main(argv=None):
         args.num_envs = shard_range(int(args.num_envs), rank, world)[1]
     cfg, cfg_train, _ = load_cfg(args)
     fill_flags(args)
+    if flags.pred_path:                                  # a missing table stops the run here, by name, before the simulator is built
+        from .env.util.traj_generator import PRED_TRAJ_FILE
+        import os
+        pred_file = cfg["env"].get("pred_traj_data", None) or PRED_TRAJ_FILE
+        if isinstance(pred_file, str) and not os.path.isfile(pred_file):
+            raise SystemExit(f"run.py --pred_path: the predicted-path table {pred_file} does not exist (--pred_traj_file PATH names it; "
+                             "`python -m emloco_amd.predictor.evaluate_jta --save_pred_trajs PATH` writes one)")
     env = RLGPUEnv(create_rlgpu_env(args, cfg, cfg_train, rank=rank))
     say = print if rank == 0 else (lambda *a, **k: None)
     if args.test:
@@ -255,6 +266,10 @@ def _run_test(args, env, policy_ckpt, games_num, max_steps, eval_out, eval_recor
     rep["seconds"] = time.time() - t0
     say(f"{rep['steps']} steps of {ev.envs_total} envs in {rep['seconds']:.2f} s")
     recs = ev.records()
+    pred_row = ev.pred_rows(recs)
+    if pred_row is not None:                 # --pred_path: the table row every game walked joins a record to its sample / mode
+        from numpy.lib import recfunctions
+        recs = recfunctions.append_fields(recs, "pred_row", pred_row, dtypes="<i8", usemask=False)
     if eval_records:
         # per-game records of every rank (what the reference draws as scatter plots): gathered on rank 0
         parts = [recs]
@@ -306,6 +321,9 @@ def _run_compare(args, env, bundle, valuenet, compare, games_num, max_steps, gam
     say(f"{ev.steps_run} steps of {ev.envs_total} envs in {seconds:.2f} s, {len(nets)} networks on the same games")
     if eval_records:
         parts = [compare_columns(ev.records())]
+        pred_row = ev.pred_rows(ev.records(0))
+        if pred_row is not None:
+            parts[0]["pred_row"] = pred_row
         if world > 1:
             gathered = [None] * world
             torch.distributed.all_gather_object(gathered, parts[0])

@@ -46,6 +46,8 @@ def get_args(argv=None):
         {"name": "--follow", "action": "store_true", "default": False},
         {"name": "--server_mode", "action": "store_true", "default": False},
         {"name": "--pred_path", "action": "store_true", "default": False},
+        {"name": "--pred_traj_file", "type": str, "default": ""},       # the table --pred_path walks (default: cfg env.pred_traj_data, then data/traj/traj_pred_data.pkl)
+        {"name": "--real_traj_file", "type": str, "default": ""},       # the tables --real_path walks, comma-separated (default: cfg env.traj_data)
         {"name": "--no_virtual_display", "action": "store_true", "default": True},
         {"name": "--show_sensors", "action": "store_true", "default": False},
         {"name": "--add_proj", "action": "store_true", "default": False},
@@ -66,6 +68,10 @@ def load_cfg(args):
     cfg["name"] = args.task
     cfg["headless"] = args.headless
     cfg["env"]["motion_file"] = args.motion_file
+    if getattr(args, "pred_traj_file", ""):
+        cfg["env"]["pred_traj_data"] = args.pred_traj_file
+    if getattr(args, "real_traj_file", ""):
+        cfg["env"]["traj_data"] = [p for p in args.real_traj_file.split(",") if p]
     cfg["args"] = args
     cfg_train = {"params": {"config": {"player": {"use_pose": args.input_init_pose, "use_vel": args.input_init_vel}}},
                  "seed": args.seed}

@@ -286,6 +286,26 @@ int emloco_task_reset_obs_pooled(struct EmlocoSim *sim, const EmlocoResetBufs *r
  * copies them to host16 (may be NULL).  Synchronises the device. */
 int emloco_task_chain_profile(long long *host16);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Waypoint tracks to dense path vertices: scipy.interpolate.CubicSpline(knot_t, way, axis=0, bc_type='natural')(query_t) for every
+ * track of a batch, which is how social-transmotion/load_jta_traj.py:93-95 turns 13 waypoints at 0.4 s into the 101 vertices that
+ * TrajGenerator follows (second derivative zero at both end knots; a query outside the knots is evaluated with the nearest end piece).
+ *   knot_t   [n_knots]   HOST array, shared by the batch, strictly increasing, 4..16 knots
+ *   dev_way  [n_traj][n_knots][3]   device
+ *   query_t  [n_query]   HOST array, shared, 1..128 entries in any order, inside or outside the knots
+ *   dev_out  [n_traj][n_query][3]   device
+ *   dev_valid [n_traj] bytes, device, or NULL: 0 for a track with a non-finite waypoint (its output rows are zeros; load_jta_traj.py:87-89
+ *            skips such tracks), 1 for every other
+ * Knots and queries are read when the call is made and travel with the launch (no copy, no synchronisation).  The solve runs in
+ * coordinates shifted by the track's first waypoint (x and y; fp32 at +-100 m world coordinates loses a digit otherwise):
+ * EMLOCO_DENSIFY_ORIGIN leaves the output shifted (the form TrajGenerator wants), without it the origin is added back.
+ * Bad sizes, non-finite or non-increasing knots: -1 and nothing is launched. */
+#define EMLOCO_DENSIFY_ORIGIN 1
+#define EMLOCO_DENSIFY_MAX_KNOTS 16
+#define EMLOCO_DENSIFY_MAX_QUERY 128
+int emloco_traj_densify(const float *knot_t, int n_knots, const float *dev_way, int64_t n_traj, const float *query_t, int n_query,
+                        float *dev_out, uint8_t *dev_valid, int flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
