@@ -162,6 +162,18 @@ class LocoValNets(C.Structure):
     _fields_ = [("n_nets", C.c_int32), ("_pad", C.c_int32), ("net", LocoValNet * EVAL_MAX_NETS)]
 
 
+TRACK_SAMPLES = 16          # EMLOCO_TRACK_SAMPLES
+TRACK_MOMENTS = 12          # EMLOCO_TRACK_MOMENTS
+
+
+class LocoValTrack(C.Structure):
+    """EmlocoLocoValTrack (include/emloco_predictor.h): the path tracking of the evaluation's games (emloco_locoval_eval_track)."""
+    _fields_ = [("stride", C.c_int32), ("root_stride", C.c_int32), ("dt", C.c_float), ("traj_dur", C.c_float),
+                ("root_pos", C.c_void_p), ("traj_verts", C.c_void_p), ("progress_buf", C.c_void_p),
+                ("sum_dev", C.c_void_p), ("sum_sample_dev", C.c_void_p), ("path_len", C.c_void_p), ("max_dev", C.c_void_p),
+                ("prev_xy", C.c_void_p), ("last_sample_dev", C.c_void_p), ("n_samples", C.c_void_p), ("dev_now", C.c_void_p)]
+
+
 def default_sim_params(**kw):
     """Engine parameters of pacer.yaml:93-104 / config.py:143-163 mapped onto EmlocoSimParams."""
     p = dict(n_sub=2, n_iter=4, h=(1.0 / 60.0) / 2, gravity_z=-9.81, contact_offset=0.02, erp=0.2,

@@ -1,5 +1,6 @@
 // eval_capi.hip -- C ABI of the LocoVal evaluation kernels (include/emloco_predictor.h: emloco_locoval_eval_*).
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstdio>
 #include "eval_kernels.hip"
 
@@ -18,6 +19,7 @@ int efail(int code, const char *what, hipError_t e = hipSuccess) {
     } while (0)
 
 static_assert(sizeof(EmlocoLocoValRecord) == 48, "EmlocoLocoValRecord is 48 bytes (the numpy dtype of learning/locoval_eval.py)");
+static_assert(sizeof(EmlocoLocoValTrackRecord) == 32, "EmlocoLocoValTrackRecord is 32 bytes (TRACK_DTYPE of learning/locoval_eval.py)");
 
 extern "C" {
 
@@ -61,6 +63,30 @@ int emloco_locoval_eval_reduce(int n_env, int games_per_env, const EmlocoLocoVal
     if (n_env < 1 || games_per_env < 1 || !records || !games || !moments) return efail(-1, "emloco_locoval_eval_reduce: bad argument");
     hipLaunchKernelGGL(emloco::locoval_eval_reduce_kernel, dim3(1), dim3(emloco::kEvalReduceThreads), 0, (hipStream_t)stream, n_env,
                        games_per_env, records, games, moments);
+    EHIPCHK(hipGetLastError());
+    return 0;
+}
+
+int emloco_locoval_eval_track(const EmlocoLocoValEval *s, const EmlocoLocoValTrack *t, EmlocoLocoValTrackRecord *records, float *samples,
+                              void *stream) {
+    if (!s || !t || !records || !samples || s->n_env < 1 || s->games_per_env < 1 || !s->steps || !s->games || !s->done)
+        return efail(-1, "emloco_locoval_eval_track: bad argument");
+    if (t->stride < 1 || t->root_stride < 2 || !(t->dt > 0.0f) || !(t->traj_dur > 0.0f) || !std::isfinite(t->dt) || !std::isfinite(t->traj_dur))
+        return efail(-1, "emloco_locoval_eval_track: stride < 1, root_stride < 2, or dt / traj_dur not finite and positive");
+    if (!t->root_pos || !t->traj_verts || !t->progress_buf || !t->sum_dev || !t->sum_sample_dev || !t->path_len || !t->max_dev || !t->prev_xy ||
+        !t->last_sample_dev || !t->n_samples)
+        return efail(-1, "emloco_locoval_eval_track: a NULL tensor in EmlocoLocoValTrack");
+    hipLaunchKernelGGL(emloco::locoval_eval_track_kernel, dim3((unsigned)((s->n_env + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *s, *t,
+                       records, samples);
+    EHIPCHK(hipGetLastError());
+    return 0;
+}
+
+int emloco_locoval_track_reduce(int n_env, int games_per_env, const EmlocoLocoValTrackRecord *records, const int32_t *games, float fail_dist,
+                                double *moments, void *stream) {
+    if (n_env < 1 || games_per_env < 1 || !records || !games || !moments) return efail(-1, "emloco_locoval_track_reduce: bad argument");
+    hipLaunchKernelGGL(emloco::locoval_track_reduce_kernel, dim3(1), dim3(emloco::kEvalReduceThreads), 0, (hipStream_t)stream, n_env,
+                       games_per_env, records, games, fail_dist, moments);
     EHIPCHK(hipGetLastError());
     return 0;
 }

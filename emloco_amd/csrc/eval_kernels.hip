@@ -9,6 +9,7 @@
 #include <stdint.h>
 #include "../../include/emloco_predictor.h"
 #include "locoval_returns_device.h"
+#include "task_device.h"          // calc_pos: the target of the reward, for the path tracking
 
 namespace emloco {
 
@@ -178,6 +179,120 @@ locoval_eval_reduce_kernel(int n_env, int games_per_env, const EmlocoLocoValReco
         __syncthreads();
     }
     if (tid < EMLOCO_EVAL_MOMENTS) moments[tid] = sm[tid][0];
+}
+
+// ---------------------------------------------------------------------------------------------------------------- path tracking
+// (`--eval_tracks`; include/emloco_predictor.h: EmlocoLocoValTrack).  One thread per env, between locoval_eval_step_kernel and the finish
+// kernels: s.done[e] is this step's flag, s.steps[e] the game's step count including this step, s.games[e] the slot of the game in
+// progress.  One calc_pos, two vertex reads and a dozen flops per env; the sums are doubles added in step order, nothing is atomic.
+__global__ void __launch_bounds__(256)
+locoval_eval_track_kernel(EmlocoLocoValEval s, EmlocoLocoValTrack t, EmlocoLocoValTrackRecord *records, float *samples) {
+#ifndef EMLOCO_EMU
+#pragma clang fp contract(off)
+#endif
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= s.n_env) return;
+    const float *verts = t.traj_verts + (long)e * EMLOCO_TRAJ_VERTS * 3;
+    const int64_t prog = t.progress_buf[e];
+    float tar[3];
+    calc_pos(verts, (float)prog * t.dt, t.traj_dur, tar);        // task_device.h:181-183, sample 0: the reward's target
+    const float *root = t.root_pos + (long)e * t.root_stride;
+    const float rx = root[0], ry = root[1];
+    const float dx = tar[0] - rx, dy = tar[1] - ry;               // task_device.h:279-280
+    const float dev = sqrtf(dx * dx + dy * dy);
+    if (t.dev_now) t.dev_now[e] = dev;
+    const int g = s.games[e];
+    if (g >= s.games_per_env) return;                             // the quota is met: the env keeps stepping and records nothing
+    const int n = s.steps[e];                                     // >= 1: this step is the game's n-th
+    const bool first = n <= 1;
+    double sum_dev = first ? 0.0 : t.sum_dev[e];
+    double sum_sample = first ? 0.0 : t.sum_sample_dev[e];
+    double path_len = first ? 0.0 : t.path_len[e];
+    float max_dev = first ? 0.0f : t.max_dev[e];
+    float last_sample = first ? 0.0f : t.last_sample_dev[e];
+    int n_samples = first ? 0 : t.n_samples[e];
+    sum_dev += (double)dev;
+    max_dev = dev > max_dev ? dev : max_dev;
+    if (!first) {                                                 // prev_xy is the root of this game's step before
+        const float sx = rx - t.prev_xy[2 * (long)e], sy = ry - t.prev_xy[2 * (long)e + 1];
+        path_len += (double)sqrtf(sx * sx + sy * sy);
+    }
+    const long slot = (long)e * s.games_per_env + g;
+    if (prog % t.stride == 0 && n_samples < EMLOCO_TRACK_SAMPLES) {
+        float *o = samples + (slot * EMLOCO_TRACK_SAMPLES + n_samples) * 4;
+        o[0] = rx - verts[0];
+        o[1] = ry - verts[1];
+        o[2] = tar[0] - verts[0];
+        o[3] = tar[1] - verts[1];
+        sum_sample += (double)dev;
+        last_sample = dev;
+        n_samples += 1;
+    }
+    const bool done = s.done[e] != 0;
+    if (done) {
+        EmlocoLocoValTrackRecord r;
+        r.ade = n_samples > 0 ? (float)(sum_sample / (double)n_samples) : 0.0f;
+        r.fde = n_samples > 0 ? last_sample : 0.0f;
+        r.mean_dev = (float)(sum_dev / (double)(n > 1 ? n : 1));
+        r.max_dev = max_dev;
+        r.final_dev = dev;
+        r.path_len = (float)path_len;
+        r.n_samples = n_samples;
+        r._pad = 0;
+        records[slot] = r;
+    }
+    // the accumulators start over with the game
+    t.sum_dev[e] = done ? 0.0 : sum_dev;
+    t.sum_sample_dev[e] = done ? 0.0 : sum_sample;
+    t.path_len[e] = done ? 0.0 : path_len;
+    t.max_dev[e] = done ? 0.0f : max_dev;
+    t.last_sample_dev[e] = done ? 0.0f : last_sample;
+    t.n_samples[e] = done ? 0 : n_samples;
+    t.prev_xy[2 * (long)e] = rx;
+    t.prev_xy[2 * (long)e + 1] = ry;
+}
+
+// One workgroup, as locoval_eval_reduce_kernel: thread t sums a contiguous run of slots (the recorded games only), then a pairwise tree in
+// LDS in a fixed order.
+__global__ void __launch_bounds__(kEvalReduceThreads)
+locoval_track_reduce_kernel(int n_env, int games_per_env, const EmlocoLocoValTrackRecord *records, const int32_t *games, float fail_dist,
+                            double *moments) {
+    __shared__ double sm[EMLOCO_TRACK_MOMENTS][kEvalReduceThreads];
+    const int tid = threadIdx.x;
+    const long total = (long)n_env * games_per_env;
+    const long c = (total + kEvalReduceThreads - 1) / kEvalReduceThreads;
+    const long lo = tid * c, hi = (lo + c < total) ? lo + c : total;
+    double m[EMLOCO_TRACK_MOMENTS];
+    for (int k = 0; k < EMLOCO_TRACK_MOMENTS; ++k) m[k] = 0.0;
+    for (long i = lo; i < hi; ++i) {
+        const long e = i / games_per_env;
+        const int g = (int)(i - e * games_per_env);
+        if (g >= games[e]) continue;
+        const EmlocoLocoValTrackRecord r = records[i];
+        const double ade = r.ade, fde = r.fde, md = r.mean_dev;
+        m[0] += 1.0;
+        if (r.n_samples > 0) {
+            m[1] += 1.0;
+            m[2] += ade;
+            m[3] += ade * ade;
+            m[4] += fde;
+            m[5] += fde * fde;
+        }
+        m[6] += md;
+        m[7] += md * md;
+        m[8] += r.final_dev;
+        m[9] += r.path_len;
+        m[10] += r.n_samples;
+        m[11] += r.max_dev > fail_dist ? 1.0 : 0.0;
+    }
+    for (int k = 0; k < EMLOCO_TRACK_MOMENTS; ++k) sm[k][tid] = m[k];
+    __syncthreads();
+    for (int off = kEvalReduceThreads / 2; off > 0; off >>= 1) {
+        if (tid < off)
+            for (int k = 0; k < EMLOCO_TRACK_MOMENTS; ++k) sm[k][tid] += sm[k][tid + off];
+        __syncthreads();
+    }
+    if (tid < EMLOCO_TRACK_MOMENTS) moments[tid] = sm[tid][0];
 }
 
 }  // namespace emloco

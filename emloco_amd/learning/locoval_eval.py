@@ -21,6 +21,14 @@ those games.  What the bookkeeping keeps per game does not depend on the network
 per row and every network of the table evaluated on them, each game recorded once per network), the records are N planes that differ
 in `value` and `sq_err` alone and equal bit for bit what N single-network runs on the same games record, and `paired_from_records`
 compares the networks game by game.
+
+Path tracking (`track=True`; `run.py --eval_tracks`): one more launch per step between the first and the last of the three
+(emloco_locoval_eval_track, once per step however many networks) records per game how far the root was from the path's target -- at
+every step and at the predictor's frames, every `round(sample_dt / dt)` steps: an ADE / FDE of the walk against the path -- how far it
+walked, and the walked and target xy at those frames in the origin-relative frame of the LocoVal inputs.  The reference's player keeps
+`real_traj` / `ideal_traj` for its video (amp_value_players.py:105,126,239) and computes no number from them: these metrics are this
+project's.  Their moments are reduced and all-reduced on their own (`track_moments_from_records` / `tracking_from_moments`); the report
+gains a `tracking` block, nothing else in it changes, and without `track` there is no launch, no buffer and no block.
 """
 import math
 
@@ -129,6 +137,95 @@ def paired_from_records(recs):
     return dict(games=int(n), mse=mse, corr_total=corr, pairs=pairs)
 
 
+# EmlocoLocoValTrackRecord (include/emloco_predictor.h), 32 bytes
+TRACK_DTYPE = np.dtype({"names": ["ade", "fde", "mean_dev", "max_dev", "final_dev", "path_len", "n_samples"],
+                        "formats": ["<f4"] * 6 + ["<i4"], "offsets": [0, 4, 8, 12, 16, 20, 24], "itemsize": 32})
+TRACK_WORDS = TRACK_DTYPE.itemsize // 4
+TRACK_SAMPLES = 16          # EMLOCO_TRACK_SAMPLES
+FAIL_DIST = 4.0             # humanoid_traj.py: the distance from the target at which the task ends a game
+# the moment vector of emloco_locoval_track_reduce (EMLOCO_TRACK_MOMENTS doubles)
+TRACK_MOMENT_NAMES = ("games", "games_sampled", "sum_ade", "sum_ade2", "sum_fde", "sum_fde2", "sum_mean_dev", "sum_mean_dev2",
+                      "sum_final_dev", "sum_path_len", "sum_samples", "failed")
+
+
+class TrackRefusal(ValueError):
+    """The path tracking cannot sample this task at the path's own frames (`track_stride`)."""
+
+
+def track_stride(sample_dt, dt, episode_length):
+    """Control steps between two sample instants, round(sample_dt / dt); a TrackRefusal (a ValueError) where the frames of the predictor do
+    not fall on control steps or a full game has more of them than a game's EMLOCO_TRACK_SAMPLES slots."""
+    sample_dt, dt = float(sample_dt), float(dt)
+    if not (dt > 0.0 and sample_dt > 0.0):
+        raise TrackRefusal(f"path tracking: sample_dt {sample_dt} and dt {dt} must be positive")
+    stride = int(round(sample_dt / dt))
+    if stride < 1 or abs(stride * dt - sample_dt) > 1e-6:
+        raise TrackRefusal(f"path tracking: the sample interval {sample_dt} s is no whole number of control steps of {dt} s "
+                         f"({stride} steps are {stride * dt} s): the walk cannot be sampled at the path's own frames")
+    if -(-int(episode_length) // stride) > TRACK_SAMPLES:
+        raise TrackRefusal(f"path tracking: a game of {int(episode_length)} steps has {-(-int(episode_length) // stride)} sample instants "
+                         f"{stride} steps apart, a game's record holds {TRACK_SAMPLES}")
+    return stride
+
+
+def track_moments_from_records(rec, fail_dist=FAIL_DIST):
+    """The moment vector of a structured array of track records (the TRACK_DTYPE columns), in float64, summed in record order -- what
+    emloco_locoval_track_reduce computes on the device (there in a fixed tree order).  Sums only: the moments of two shards add up to
+    the moments of their union."""
+    m = np.zeros(len(TRACK_MOMENT_NAMES), np.float64)
+    col = lambda k, sel=slice(None): rec[k][sel].astype(np.float64)
+    sampled = rec["n_samples"] > 0
+    m[0], m[1] = len(rec), int(np.count_nonzero(sampled))
+    for i, k in ((2, "ade"), (4, "fde")):
+        y = col(k, sampled)
+        m[i], m[i + 1] = float(np.add.reduce(y)), float(np.add.reduce(y * y))
+    y = col("mean_dev")
+    m[6], m[7] = float(np.add.reduce(y)), float(np.add.reduce(y * y))
+    m[8], m[9], m[10] = float(np.add.reduce(col("final_dev"))), float(np.add.reduce(col("path_len"))), float(np.add.reduce(col("n_samples")))
+    m[11] = float(np.count_nonzero(rec["max_dev"] > np.float32(fail_dist)))
+    return m
+
+
+def tracking_from_moments(m):
+    """The `tracking` block of the report from a track moment vector: a dict of the numbers and `lines`.  ade / fde are averaged over the
+    games that reached a sample instant (`games_sampled`), everything else over all games.  The moments hold no sum of final_dev^2:
+    `std_final_dev` is not in this block; the evaluator's report takes it, like the correlations, from `tracking_from_records`."""
+    m = [float(x) for x in m]
+    n, ns = m[0], m[1]
+    if n < 1:
+        return {"games": 0, "lines": ["tracking: no game finished"]}
+    nan = float("nan")
+    r = {"games": int(round(n)), "games_sampled": int(round(ns))}
+    r["av_ade"], r["std_ade"] = (m[2] / ns, _std(ns, m[2], m[3])) if ns >= 1 else (nan, nan)
+    r["av_fde"], r["std_fde"] = (m[4] / ns, _std(ns, m[4], m[5])) if ns >= 1 else (nan, nan)
+    r["av_mean_dev"], r["std_mean_dev"] = m[6] / n, _std(n, m[6], m[7])
+    r["av_final_dev"], r["av_path_len"], r["av_samples"] = m[8] / n, m[9] / n, m[10] / n
+    r["failed"], r["fail_share"] = int(round(m[11])), m[11] / n
+    r["lines"] = [
+        f"tracking: {r['games']} games, {r['games_sampled']} with a sample instant, av samples: {r['av_samples']:.2f}",
+        f"av_ade: {r['av_ade']:.3f}, std_ade: {r['std_ade']:.3f}, av_fde: {r['av_fde']:.3f}, std_fde: {r['std_fde']:.3f}",
+        f"av_mean_dev: {r['av_mean_dev']:.3f}, std_mean_dev: {r['std_mean_dev']:.3f}, av_final_dev: {r['av_final_dev']:.3f}, "
+        f"av_path_len: {r['av_path_len']:.3f}, beyond fail_dist: {100.0 * r['fail_share']:.1f} %",
+    ]
+    return r
+
+
+def tracking_from_records(values, track):
+    """What the moments do not carry, in float64 from the gathered records (as `paired_from_records`): the std of final_dev, and per
+    network (`values`: one array per network, the games of `track` in its order) Pearson r of `value` against ade and fde over the games
+    that reached a sample instant -- whether LocoVal predicts how well the path is tracked.  NaN where a variance is zero."""
+    sel = track["n_samples"] > 0
+    out = {"std_final_dev": float(np.std(track["final_dev"].astype(np.float64))) if len(track) else float("nan"),
+           "corr_value_ade": [], "corr_value_fde": []}
+    for v in values:
+        v = np.asarray(v)[sel].astype(np.float64)
+        for k in ("ade", "fde"):
+            y = track[k][sel].astype(np.float64)
+            ok = len(v) > 1 and v.std() > 0 and y.std() > 0
+            out["corr_value_" + k].append(float(np.corrcoef(v, y)[0, 1]) if ok else float("nan"))
+    return out
+
+
 class LocoValEvaluator:
     """Plays `games_num` games (all ranks together) of a frozen policy and scores a LocoVal network on them.
 
@@ -138,15 +235,22 @@ class LocoValEvaluator:
     valuenet: a ValuePoseNet on the task's device (the fused HIP forward evaluates it), or a list of 1 .. EVAL_MAX_NETS of them (any
       variants): all are scored on the same games, and `report` / `records` answer per network.
     max_steps: the step cap of the reference's player (rl_games BasePlayer: 27 000); a run whose games never finish stops there and
-      the report states the shortfall."""
+      the report states the shortfall.
+    track: also record per game how closely the root followed its path (module docstring): `report` gains a `tracking` block,
+      `track_records` / `track_samples` answer per game."""
 
-    def __init__(self, vec_env, policy_bundle, valuenet, games_num, max_steps=27000, poll_every=16, gamma=0.99, disc_reward=None):
+    def __init__(self, vec_env, policy_bundle, valuenet, games_num, max_steps=27000, poll_every=16, gamma=0.99, disc_reward=None,
+                 track=False):
         from ..predictor import ops
         from .value_pose_net import ValuePoseNet
         self.vec_env = vec_env
         env = vec_env.env if hasattr(vec_env, "env") else vec_env
         self.env, self.task = env, env.task
         task = self.task
+        self.track = bool(track)
+        if self.track:                            # refused by name before anything is allocated
+            self.track_stride = track_stride(task._traj_sample_timestep, task.dt, task.max_episode_length)
+            self.fail_dist = float(getattr(task, "_fail_dist", FAIL_DIST))
         self.device = torch.device(task.device)
         self.multi = isinstance(valuenet, (list, tuple))
         nets = list(valuenet) if self.multi else [valuenet]
@@ -210,6 +314,14 @@ class LocoValEvaluator:
         self._s = ops.LocoValEval(E, self.step_to_pred, G, 0, self.gamma, *[p(b[k]) for k in (
             "coef", "c_disc", "tp_disc", "cr", "c_loc", "c_pow", "tp_cr", "tp_loc", "tp_pow", "steps", "games", "done", "terminated",
             "inverted", "n_full")], *[p(self._input(k)) for k in self._inputs], p(b["traj13"]), p(b["pose"]), p(b["vel"]), p(b["row_mask"]))
+        if self.track:
+            f64 = lambda *s: torch.zeros(*s, dtype=torch.float64, device=dev)
+            self._tb = tb = dict(sum_dev=f64(E), sum_sample_dev=f64(E), path_len=f64(E), max_dev=f(E), prev_xy=f(E, 2),
+                                 last_sample_dev=f(E), n_samples=i32(E), dev_now=f(E))
+            self._track_records = torch.zeros(E * G * TRACK_WORDS, dtype=torch.int32, device=dev)
+            self._track_samples = f(E, G, ops.TRACK_SAMPLES, 4)
+            self._track_moments = torch.zeros(ops.TRACK_MOMENTS, dtype=torch.float64, device=dev)
+            self._t = ops.LocoValTrack(stride=self.track_stride, **{k: p(v) for k, v in tb.items()})
         self.steps_run = 0
         self.started = False
         # --pred_path: the host reset knows which row of the predicted-path table every game walks; logged from the first reset on
@@ -278,6 +390,9 @@ class LocoValEvaluator:
         ops._chk(lib.emloco_locoval_eval_step(C.byref(self._s), P(reward_raw.contiguous()), P(disc), P(dones.contiguous()),
                                               P(None if terminate is None else terminate.contiguous()),
                                               P(None if inverted is None else inverted.contiguous()), st), "emloco_locoval_eval_step")
+        if self.track:                              # once per step, whatever the number of networks: nothing tracked depends on them
+            ops._chk(lib.emloco_locoval_eval_track(C.byref(self._s), C.byref(self._track_inputs()), P(self._track_records),
+                                                   P(self._track_samples), st), "emloco_locoval_eval_track")
         if self.multi:
             self._check_nets()
             ops._chk(lib.emloco_locoval_eval_fwd_multi(C.byref(self._s), C.byref(self._nets), st), "emloco_locoval_eval_fwd_multi")
@@ -286,6 +401,17 @@ class LocoValEvaluator:
             return
         self._forward(st)
         ops._chk(lib.emloco_locoval_eval_finish(C.byref(self._s), P(self._value), P(self._records), st), "emloco_locoval_eval_finish")
+
+    def _track_inputs(self):
+        """The tracker reads what the task's reward kernel read this step: the addresses and constants of the task's own EmlocoTaskBufs."""
+        from .. import _lib as L
+        pb = getattr(self.task, "_post_bufs", None)
+        if pb is None:
+            raise RuntimeError("LocoValEvaluator(track=True): the task has not launched its post-physics kernel yet (no EmlocoTaskBufs)")
+        t = self._t
+        t.root_pos, t.root_stride, t.traj_verts, t.progress_buf = pb.rb_state, L.NB * 13, pb.traj_verts, pb.progress_buf
+        t.dt, t.traj_dur = pb.dt, pb.traj_dur
+        return t
 
     def _forward(self, st):
         """LocoVal on the rows whose game took its first step (:128-134), into the persistent `value` rows."""
@@ -339,11 +465,70 @@ class LocoValEvaluator:
         D.all_reduce_(m)                            # the one collective of the evaluation
         return m.cpu().numpy()
 
+    def track_moments(self):
+        """The track moment vector of all ranks: one reduction, one all-reduce of its own (the moment vector of `moments` is untouched)."""
+        import ctypes as C
+        from ..predictor import ops
+        from ..sim import current_stream_handle
+        P = lambda t: C.c_void_p(t.data_ptr())
+        ops._chk(ops._lib().emloco_locoval_track_reduce(self.num_envs, self.games_per_env, P(self._track_records), P(self._b["games"]),
+                                                        self.fail_dist, P(self._track_moments), current_stream_handle(self.device)),
+                 "emloco_locoval_track_reduce")
+        m = self._track_moments.clone()
+        D.all_reduce_(m)
+        return m.cpu().numpy()
+
+    def track_records(self):
+        """This rank's track records (TRACK_DTYPE columns plus `env` and `game`), in the order of `records`."""
+        E, G = self.num_envs, self.games_per_env
+        raw = self._track_records.cpu().numpy().view(TRACK_DTYPE).reshape(E, G)
+        env, game = self._slots(self._b["games"].cpu().numpy(), G)
+        out = np.zeros(len(env), dtype=[(k, TRACK_DTYPE.fields[k][0]) for k in TRACK_DTYPE.names] + [("env", "<i4"), ("game", "<i4")])
+        for k in TRACK_DTYPE.names:
+            out[k] = raw[k][env, game]
+        out["env"], out["game"] = env, game
+        return out
+
+    def track_samples(self):
+        """(walked, target): [games][TRACK_SAMPLES][2] each, the root's and the target's xy at the sample instants of every recorded game
+        (order of `records`) relative to the path's first vertex; rows past the game's n_samples are zero."""
+        env, game = self._slots(self._b["games"].cpu().numpy(), self.games_per_env)
+        smp = self._track_samples.cpu().numpy()[env, game]
+        return np.ascontiguousarray(smp[:, :, 0:2]), np.ascontiguousarray(smp[:, :, 2:4])
+
+    def _tracking(self, values, say):
+        """The `tracking` block: the all-reduced moments, and from all ranks' records the Pearson r of every network's value."""
+        m = self.track_moments()
+        trk = tracking_from_moments(m)
+        rec = self.track_records()
+        if D.is_distributed():
+            parts = [None] * D.world_size()
+            torch.distributed.all_gather_object(parts, (values, rec))
+            values = [np.concatenate([p[0][k] for p in parts]) for k in range(len(values))]
+            rec = np.concatenate([p[1] for p in parts])
+        assert trk["games"] == len(rec), "the track records and their moments cover the same games"
+        extra = tracking_from_records(values, rec)
+        if not self.multi:
+            extra["corr_value_ade"], extra["corr_value_fde"] = extra["corr_value_ade"][0], extra["corr_value_fde"][0]
+        trk.update(extra, fail_dist=self.fail_dist, stride=self.track_stride, dt=float(self._t.dt), traj_dur=float(self._t.traj_dur),
+                   moments=[float(x) for x in m])
+        if trk["games"] > 0:
+            fmt = lambda c: ", ".join(f"{x:.3f}" for x in (c if self.multi else [c]))
+            trk["lines"] = trk["lines"] + [f"Correlation of value with ade: {fmt(trk['corr_value_ade'])}, with fde: {fmt(trk['corr_value_fde'])}"]
+        if say is not None:
+            for ln in trk["lines"]:
+                say(ln)
+        return trk
+
     def report(self, say=print):
         """One network: the report dict.  A list of networks: {"networks": [the report of each, as a single run of it gives],
-        "paired": paired_from_records of all ranks' records}; the lines of every network are said under a `network k` heading."""
+        "paired": paired_from_records of all ranks' records}; the lines of every network are said under a `network k` heading.
+        With `track` the dict also holds `tracking` (its lines are said last and kept in the block, not in the report's `lines`)."""
         if not self.multi:
-            return self._report(self.moments(), say)
+            rep = self._report(self.moments(), say)
+            if self.track:
+                rep["tracking"] = self._tracking([self.records()["value"]], say)
+            return rep
         reps = []
         for k, m in enumerate(self.moments()):
             if say is not None:
@@ -359,6 +544,8 @@ class LocoValEvaluator:
         if say is not None:
             for pr in paired["pairs"]:
                 say(f"network {pr['b']} - network {pr['a']}: MSE {pr['d_mse']:+.6f}, Pearson r (total) {pr['d_corr_total']:+.4f}")
+        if self.track:
+            return {"networks": reps, "paired": paired, "tracking": self._tracking([r["value"] for r in self.records()], say)}
         return {"networks": reps, "paired": paired}
 
     def _report(self, m, say):
@@ -411,9 +598,14 @@ class LocoValEvaluator:
         return table[records["env"], records["game"]]
 
     @staticmethod
+    def _slots(games, G):
+        """(env, game) of the recorded slots, env-major."""
+        return np.nonzero(np.arange(G)[None, :] < games[:, None])
+
+    @staticmethod
     def _records_of(raw, games):
         G = raw.shape[1]
-        env, game = np.nonzero(np.arange(G)[None, :] < games[:, None])
+        env, game = LocoValEvaluator._slots(games, G)
         rec = raw[env, game]
         out = np.zeros(len(rec), dtype=[(k, RECORD_DTYPE.fields[k][0]) for k in RECORD_DTYPE.names] + [("env", "<i4"), ("game", "<i4")])
         for k in RECORD_DTYPE.names:

@@ -9,7 +9,7 @@ import os
 import torch
 
 from .. import _lib as L
-from .._lib import EVAL_MAX_NETS, LocoValEval, LocoValNet, LocoValNets, LocoValStep  # noqa: F401  (re-exported: callers say ops.LocoValStep)
+from .._lib import EVAL_MAX_NETS, TRACK_MOMENTS, TRACK_SAMPLES, LocoValEval, LocoValNet, LocoValNets, LocoValStep, LocoValTrack  # noqa: F401  (re-exported: callers say ops.LocoValStep)
 from ..sim import current_stream_handle
 
 GEMM_BIAS, GEMM_RELU, GEMM_ACC, GEMM_DROPOUT = 1, 2, 4, 8

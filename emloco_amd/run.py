@@ -9,14 +9,16 @@ frozen random-init policy, and prints the reference's `fps_step` counter (common
 
     python -m emloco_amd.run --test --num_envs 4096 --policy_checkpoint policy.pth --valuenet_path LocoVal.pth \
         [--games_num N] [--eval_out report.json] [--eval_records games.npz] [--compare_valuenet Other.pth ...]
-        [--pred_path [--pred_traj_file preds.pkl]]
+        [--pred_path [--pred_traj_file preds.pkl]] [--eval_tracks]
 
 is the reference's `pacer/run.py --test --valuenet_path ...` (AMPPlayerContinuousValue.run): the frozen policy plays
 deterministically and LocoVal is scored against the discounted returns of the games (`learning/locoval_eval.py`).  Every `--compare_valuenet` adds a network (its input configuration read off its fc1 width) that is
 scored on the very same games, played once: the input ablation on one set of trajectories.  `--pred_path` makes the humanoid walk the
 predictor's output (traj_generator.py:53-54,163-175): the table `evaluate_jta --save_pred_trajs` writes, named by `--pred_traj_file`
 (default data/traj/traj_pred_data.pkl); `--eval_records` then carries the table row of every game as `pred_row`.  `--real_path JTA`
-takes its tables (`python -m emloco_amd.predictor.export_trajs`) from `--real_traj_file a.pkl[,b.pkl]`.
+takes its tables (`python -m emloco_amd.predictor.export_trajs`) from `--real_traj_file a.pkl[,b.pkl]`.  `--eval_tracks` also records how
+closely every game followed its path (learning/locoval_eval.py): a `tracking` block in the report, and in `--eval_records` the per-game
+`track` table and the `walked` / `target` xy at the path's own frames, origin-relative as the rows of the predicted-path table.
 """
 import random
 import sys
@@ -125,16 +127,26 @@ def load_compare_valuenets(paths):
     return out
 
 
+def pop_test_options(argv):
+    """Remove the options of --test from argv (get_args does not know them) and return them; one that is given without --test but means
+    nothing there stops the run."""
+    opt = dict(games_num=_pop_opt(argv, "--games_num"), eval_out=_pop_opt(argv, "--eval_out"), eval_records=_pop_opt(argv, "--eval_records"),
+               max_steps=_pop_opt(argv, "--max_steps"), compare=_pop_all(argv, "--compare_valuenet"), eval_tracks="--eval_tracks" in argv)
+    if opt["eval_tracks"]:
+        argv.remove("--eval_tracks")
+        if "--test" not in argv:
+            raise SystemExit("run.py: --eval_tracks records the path tracking of the games of --test")
+    if opt["compare"] and "--test" not in argv:
+        raise SystemExit("run.py: --compare_valuenet adds networks to the evaluation of --test")
+    return opt
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     # --test (the reference's player, amp_value_players.py): its own options, checked before anything touches a device
-    games_num = _pop_opt(argv, "--games_num")
-    eval_out = _pop_opt(argv, "--eval_out")
-    eval_records = _pop_opt(argv, "--eval_records")
-    max_steps = _pop_opt(argv, "--max_steps")
-    compare = _pop_all(argv, "--compare_valuenet")
-    if compare and "--test" not in argv:
-        raise SystemExit("run.py: --compare_valuenet adds networks to the evaluation of --test")
+    opt = pop_test_options(argv)
+    games_num, eval_out, eval_records, max_steps = opt["games_num"], opt["eval_out"], opt["eval_records"], opt["max_steps"]
+    compare, eval_tracks = opt["compare"], opt["eval_tracks"]
     if "--test" in argv:
         vp = _pop_opt(list(argv), "--valuenet_path", "")
         if not vp:
@@ -190,7 +202,7 @@ def main(argv=None):
     env = RLGPUEnv(create_rlgpu_env(args, cfg, cfg_train, rank=rank))
     say = print if rank == 0 else (lambda *a, **k: None)
     if args.test:
-        _run_test(args, env, policy_ckpt, games_num, max_steps, eval_out, eval_records, rank, world, say, compare)
+        _run_test(args, env, policy_ckpt, games_num, max_steps, eval_out, eval_records, rank, world, say, compare, eval_tracks)
         return
     if train_policy:
         import yaml
@@ -227,12 +239,31 @@ def main(argv=None):
         torch.distributed.destroy_process_group()
 
 
-def _run_test(args, env, policy_ckpt, games_num, max_steps, eval_out, eval_records, rank, world, say, compare=()):
+def _track_columns(ev):
+    """--eval_tracks: the --eval_records columns of this rank's games, in the order of its records."""
+    walked, target = ev.track_samples()
+    trk = ev.track_records()
+    from numpy.lib import recfunctions
+    cols = recfunctions.repack_fields(trk[[k for k in trk.dtype.names if k not in ("env", "game")]])      # env / game are columns already
+    return dict(track=cols, walked=walked, target=target)
+
+
+def _gather_track_columns(ev, world):
+    """The track columns of every rank, concatenated in rank order as the records are (collective)."""
+    parts = [_track_columns(ev)]
+    if world > 1:
+        gathered = [None] * world
+        torch.distributed.all_gather_object(gathered, parts[0])
+        parts = gathered
+    return {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
+
+
+def _run_test(args, env, policy_ckpt, games_num, max_steps, eval_out, eval_records, rank, world, say, compare=(), eval_tracks=False):
     """--test: LocoValEvaluator with the frozen policy (deterministic actions) and the LocoVal network of --valuenet_path."""
     import json
     import yaml
     from .learning.amp_policy import DEFAULT_CFG, AMPPolicyBundle
-    from .learning.locoval_eval import LocoValEvaluator
+    from .learning.locoval_eval import LocoValEvaluator, TrackRefusal
     from .learning.value_pose_net import ValuePoseNet
     cfg_train = yaml.safe_load(open(DEFAULT_CFG))
     config = cfg_train["params"]["config"]
@@ -256,10 +287,14 @@ def _run_test(args, env, policy_ckpt, games_num, max_steps, eval_out, eval_recor
     valuenet.eval()
     if compare:
         _run_compare(args, env, bundle, valuenet, compare, int(games_num) if games_num else int(player.get("games_num", 200)),
-                     int(max_steps) if max_steps else 27000, float(config.get("gamma", 0.99)), eval_out, eval_records, rank, world, say)
+                     int(max_steps) if max_steps else 27000, float(config.get("gamma", 0.99)), eval_out, eval_records, rank, world, say,
+                     eval_tracks)
         return
-    ev = LocoValEvaluator(env, bundle, valuenet, int(games_num) if games_num else int(player.get("games_num", 200)),
-                          max_steps=int(max_steps) if max_steps else 27000, gamma=float(config.get("gamma", 0.99)))
+    try:
+        ev = LocoValEvaluator(env, bundle, valuenet, int(games_num) if games_num else int(player.get("games_num", 200)),
+                              max_steps=int(max_steps) if max_steps else 27000, gamma=float(config.get("gamma", 0.99)), track=eval_tracks)
+    except TrackRefusal as e:                    # --eval_tracks on a task it cannot sample: a message, no traceback
+        raise SystemExit(f"run.py --test: {e}")
     t0 = time.time()
     rep = ev.run(say=say)
     torch.cuda.synchronize()
@@ -277,9 +312,11 @@ def _run_test(args, env, policy_ckpt, games_num, max_steps, eval_out, eval_recor
             gathered = [None] * world
             torch.distributed.all_gather_object(gathered, recs)
             parts = gathered
+        tcols = _gather_track_columns(ev, world) if eval_tracks else {}
         if rank == 0:
             cols = {k: np.concatenate([p[k] for p in parts]) for k in recs.dtype.names}
             cols["rank"] = np.concatenate([np.full(len(p), r, np.int32) for r, p in enumerate(parts)])
+            cols.update(tcols)
             np.savez(eval_records, **cols)
     if eval_out and rank == 0:
         with open(eval_out, "w") as f:
@@ -297,10 +334,11 @@ def compare_columns(recs):
     return cols
 
 
-def _run_compare(args, env, bundle, valuenet, compare, games_num, max_steps, gamma, eval_out, eval_records, rank, world, say):
+def _run_compare(args, env, bundle, valuenet, compare, games_num, max_steps, gamma, eval_out, eval_records, rank, world, say,
+                 eval_tracks=False):
     """--test with --compare_valuenet: the network of --valuenet_path and the added ones on the same games, played once."""
     import json
-    from .learning.locoval_eval import LocoValEvaluator
+    from .learning.locoval_eval import LocoValEvaluator, TrackRefusal
     from .learning.value_pose_net import ValuePoseNet
     task = env.env.task
     nets, paths = [valuenet], [args.valuenet_path]
@@ -313,7 +351,10 @@ def _run_compare(args, env, bundle, valuenet, compare, games_num, max_steps, gam
             raise SystemExit(f"run.py --test: --compare_valuenet {path} does not load as the network its fc1 width names: {e}")
         nets.append(net.eval())
         paths.append(path)
-    ev = LocoValEvaluator(env, bundle, nets, games_num, max_steps=max_steps, gamma=gamma)
+    try:
+        ev = LocoValEvaluator(env, bundle, nets, games_num, max_steps=max_steps, gamma=gamma, track=eval_tracks)
+    except TrackRefusal as e:                    # --eval_tracks on a task it cannot sample: a message, no traceback
+        raise SystemExit(f"run.py --test: {e}")
     t0 = time.time()
     rep = ev.run(say=say)
     torch.cuda.synchronize()
@@ -328,16 +369,21 @@ def _run_compare(args, env, bundle, valuenet, compare, games_num, max_steps, gam
             gathered = [None] * world
             torch.distributed.all_gather_object(gathered, parts[0])
             parts = gathered
+        tcols = _gather_track_columns(ev, world) if eval_tracks else {}
         if rank == 0:
             cols = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
             cols["rank"] = np.concatenate([np.full(len(p["env"]), r, np.int32) for r, p in enumerate(parts)])
+            cols.update(tcols)
             np.savez(eval_records, **cols)
     if eval_out and rank == 0:
         for r in rep["networks"]:
             r["seconds"] = seconds
         with open(eval_out, "w") as f:
-            json.dump({"networks": [dict(path=p, variant=n.variant, report=r) for p, n, r in zip(paths, nets, rep["networks"])],
-                       "paired": rep["paired"]}, f, indent=1, default=float)
+            out = {"networks": [dict(path=p, variant=n.variant, report=r) for p, n, r in zip(paths, nets, rep["networks"])],
+                   "paired": rep["paired"]}
+            if eval_tracks:
+                out["tracking"] = rep["tracking"]
+            json.dump(out, f, indent=1, default=float)
     if world > 1:
         torch.distributed.destroy_process_group()
 

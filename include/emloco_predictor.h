@@ -451,6 +451,59 @@ int emloco_locoval_eval_fwd_multi(const EmlocoLocoValEval *s, const EmlocoLocoVa
 int emloco_locoval_eval_finish_multi(const EmlocoLocoValEval *s, const EmlocoLocoValNets *nets, EmlocoLocoValRecord *records,
                                      void *stream);
 
+/* Path tracking of the evaluation's games (`run.py --test --eval_tracks`): how far the humanoid walked from the path it was given, and
+ * where it went.  The reference's player keeps the data per game -- real_traj, the root xy after every step (amp_value_players.py:126),
+ * and ideal_traj, the path's vertices (:105) -- and only draws them (:239); it computes no number from them, so the metrics below are
+ * this project's own (only calc_pos, traj_generator.py:278-296, is the reference's).  A fourth launch per step, BETWEEN
+ * emloco_locoval_eval_step (after it s->done[e] is this step's flag, s->steps[e] the game's step count with this step, s->games[e] still the
+ * slot of the game in progress) and emloco_locoval_eval_finish[_multi] (which advances them); nothing it keeps depends on a network, so
+ * it is issued once per step however many networks are scored.  Per env and step:
+ *   target = calc_pos(traj_verts[e], (float)progress_buf[e] * dt, traj_dur)   the call the reward makes (time after the increment,
+ *                                                                             phase clipped to [0, 1])
+ *   dev    = sqrtf(dx * dx + dy * dy), d = target.xy - root.xy                exp(-2 dev^2) is the step's reward_raw[e][0]
+ * While games[e] < games_per_env (an env whose quota is met keeps stepping and writes nothing but dev_now): dev joins the game's sum
+ * (double, step order), maximum and last value; the root's xy step |root_xy(n) - root_xy(n - 1)| joins path_len from the game's
+ * second step on; when progress_buf[e] % stride == 0 the step is sample k = n_samples of the game (k < EMLOCO_TRACK_SAMPLES, later
+ * ones are dropped and not counted): samples[e][games[e]][k] = (walked xy, target xy), both minus the path's first vertex
+ * traj_verts[e][0].xy -- the origin-relative frame of the LocoVal inputs and of the predictor's output, so a walked path compares
+ * directly with the row of the predicted-path table the game walked.  When s->done[e] is set the game's record goes to
+ * records[e][games[e]] and the accumulators start over.  One thread per env, no atomics: the same bytes on every run. */
+#define EMLOCO_TRACK_SAMPLES 16
+typedef struct EmlocoLocoValTrack {     /* caller-owned device memory */
+    int32_t stride;                 /* control steps between samples: round(sample_dt / dt) (12: the predictor's 0.4 s frames) */
+    int32_t root_stride;            /* floats between the root positions of consecutive envs */
+    float dt, traj_dur;             /* as EmlocoTaskBufs */
+    const float *root_pos;          /* the tensor the reward kernel reads the root position from (EmlocoTaskBufs.rb_state: body 0, xyz first) */
+    const float *traj_verts;        /* [n_env][EMLOCO_TRAJ_VERTS = 101][3] */
+    const int64_t *progress_buf;    /* [n_env], after this step's increment */
+    double *sum_dev;                /* [n_env] per-game accumulators: sum of dev over the steps, */
+    double *sum_sample_dev;         /* [n_env] over the sample instants, */
+    double *path_len;               /* [n_env] and of the root's xy steps */
+    float *max_dev;                 /* [n_env] */
+    float *prev_xy;                 /* [n_env][2] the root's xy at the step before (invalid at a game's first step) */
+    float *last_sample_dev;         /* [n_env] */
+    int32_t *n_samples;             /* [n_env] */
+    float *dev_now;                 /* [n_env] or NULL: this step's dev, written at every launch for every env */
+} EmlocoLocoValTrack;
+typedef struct EmlocoLocoValTrackRecord {   /* one game, 32 bytes */
+    float ade, fde;                 /* mean / last dev over the game's sample instants (0 when n_samples == 0) */
+    float mean_dev, max_dev, final_dev;     /* over every step of the game / at its last step */
+    float path_len;                 /* what the root walked in xy (0 for a one-step game) */
+    int32_t n_samples, _pad;
+} EmlocoLocoValTrackRecord;
+/* records [n_env][games_per_env]; samples [n_env][games_per_env][EMLOCO_TRACK_SAMPLES][4] (zeroed by the caller: slots past n_samples
+ * are never written).  -1 and no launch: a NULL argument or required pointer, stride < 1, games_per_env < 1, n_env < 1, root_stride < 2,
+ * dt or traj_dur not finite and positive. */
+int emloco_locoval_eval_track(const EmlocoLocoValEval *s, const EmlocoLocoValTrack *t, EmlocoLocoValTrackRecord *records, float *samples,
+                              void *stream);
+/* moments[EMLOCO_TRACK_MOMENTS] (double, fixed tree order as emloco_locoval_eval_reduce, over the recorded games; sums only, so one
+ * all-reduce(sum) over ranks is correct): [0] games, [1] games with n_samples > 0, [2] sum ade, [3] sum ade^2, [4] sum fde, [5] sum fde^2
+ * (over the games of [1]), [6] sum mean_dev, [7] sum mean_dev^2, [8] sum final_dev, [9] sum path_len, [10] sum n_samples,
+ * [11] games with max_dev > fail_dist (the task's termination distance, 4.0). */
+#define EMLOCO_TRACK_MOMENTS 12
+int emloco_locoval_track_reduce(int n_env, int games_per_env, const EmlocoLocoValTrackRecord *records, const int32_t *games, float fail_dist,
+                                double *moments, void *stream);
+
 /* torch.nn.utils.clip_grad_norm_(params, max_norm) + torch.optim.Adam.step() (train_jta.py:317-318,411; train_jrdb.py likewise) on ONE
  * flat fp32 buffer of n parameters with their gradients, first and second moments laid out alike -- three launches (block sums of
  * squares, the clip coefficient from them in a fixed order, the update) where the foreach implementations issue ~25.  The gradient is
