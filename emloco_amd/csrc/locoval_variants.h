@@ -6,7 +6,7 @@
 //     1 vel     28 / 13 /  6   FOUR samples per wave, one per 16-lane DPP row (h1 <= 13 and the 13 waypoints fit a row):
 //     0 traj    26 / 12 /  6   a 256-thread workgroup serves 16 samples and holds the ~1.8 KB of weights in LDS once
 // Included at the end of predictor_kernels.hip; the dispatch (`locoval_variant_fwd / _bwd`) is shared by the C ABI
-// (predictor_capi.hip) and the CPU emulation's glue (tests/emu_locoval_variants.cpp) through a launcher object, as fold_rows is.
+// (predictor_capi.hip) and the CPU emulation's glue (tests/emu/emu_predictor.cpp) through a launcher object, as fold_rows is.
 #pragma once
 
 namespace emloco {

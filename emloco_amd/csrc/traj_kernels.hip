@@ -17,7 +17,7 @@
 //   3. lanes 0..191 each solve one (track, coordinate): a forward and a back substitution of n - 2 steps;
 //   4. all lanes evaluate the workgroup's contiguous tracks x n_query x 3 outputs, consecutive lanes writing consecutive floats (the
 //      kernel is write-bound: 156 B in, 1 212 B out per track at 13 knots / 101 queries).
-// Plain fp32 arithmetic in a fixed order (the unit is built with -ffp-contract=off), no atomics: tests/emu_traj_densify.cpp runs
+// Plain fp32 arithmetic in a fixed order (the unit is built with -ffp-contract=off), no atomics: tests/emu/emu_task.cpp runs
 // the same source on the CPU.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -30,6 +30,7 @@ walked, and the walked and target xy at those frames in the origin-relative fram
 project's.  Their moments are reduced and all-reduced on their own (`track_moments_from_records` / `tracking_from_moments`); the report
 gains a `tracking` block, nothing else in it changes, and without `track` there is no launch, no buffer and no block.
 """
+import ctypes as C
 import math
 
 import numpy as np
@@ -226,6 +227,43 @@ def tracking_from_records(values, track):
     return out
 
 
+# The per-env buffers of EmlocoLocoValEval and EmlocoLocoValTrack (include/emloco_predictor.h) under the structs' own field names:
+# (name, dtype, shape after the env axis).  All start at zero but `coef`, a game's discount, which starts at one; EmlocoLocoValEval also
+# holds `n_full`, the one int32 counter the host polls.
+EVAL_BUFFERS = (("coef", "float64", ()), ("c_disc", "float64", ()), ("tp_disc", "float64", ()), ("cr", "float32", ()),
+                ("c_loc", "float32", ()), ("c_pow", "float32", ()), ("tp_cr", "float32", ()), ("tp_loc", "float32", ()),
+                ("tp_pow", "float32", ()), ("steps", "int32", ()), ("games", "int32", ()), ("done", "uint8", ()),
+                ("terminated", "uint8", ()), ("inverted", "uint8", ()), ("traj13", "float32", (13, 3)), ("pose", "float32", (24, 3)),
+                ("vel", "float32", (2,)), ("row_mask", "float32", ()))
+EVAL_INPUTS = (("waypoint_traj", (15, 3)), ("init_pose", (24, 3)), ("init_vel", (2,)))      # the task's float32 tensors the step reads by address
+TRACK_BUFFERS = (("sum_dev", "float64", ()), ("sum_sample_dev", "float64", ()), ("path_len", "float64", ()), ("max_dev", "float32", ()),
+                 ("prev_xy", "float32", (2,)), ("last_sample_dev", "float32", ()), ("n_samples", "int32", ()), ("dev_now", "float32", ()))
+
+
+def eval_state(n_env, step_to_pred, games_per_env, gamma, inputs, zeros, ptr):
+    """(EmlocoLocoValEval, {field: buffer}): the game state of `n_env` envs at the start of an evaluation.  inputs: {name: array} for
+    EVAL_INPUTS; zeros(shape, dtype name) allocates a zeroed array and ptr(array) gives its address (torch on the device here; the
+    tests run the same state on host arrays)."""
+    from .._lib import LocoValEval
+    b = {k: zeros((n_env, *shape), dt) for k, dt, shape in EVAL_BUFFERS}
+    b["coef"] += 1
+    b["n_full"] = zeros((1,), "int32")
+    s = LocoValEval(n_env=n_env, step_to_pred=step_to_pred, games_per_env=games_per_env, gamma=gamma,
+                    **{k: ptr(v) for k, v in b.items()}, **{k: ptr(inputs[k]) for k, _ in EVAL_INPUTS})
+    return s, b
+
+
+def track_state(n_env, zeros, ptr, **scalars):
+    """(EmlocoLocoValTrack, {field: buffer}) beside `eval_state`; scalars: the struct's own (stride, root_stride, dt, traj_dur)."""
+    from .._lib import LocoValTrack
+    tb = {k: zeros((n_env, *shape), dt) for k, dt, shape in TRACK_BUFFERS}
+    return LocoValTrack(**scalars, **{k: ptr(v) for k, v in tb.items()}), tb
+
+
+def _p(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
 class LocoValEvaluator:
     """Plays `games_num` games (all ranks together) of a frozen policy and scores a LocoVal network on them.
 
@@ -286,12 +324,10 @@ class LocoValEvaluator:
         self.step_to_pred = int(task.step_to_pred)
         dev = self.device
         f = lambda *s: torch.zeros(*s, device=dev)
-        i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)
-        u8 = lambda *s: torch.zeros(*s, dtype=torch.uint8, device=dev)
-        self._b = b = dict(coef=torch.ones(E, dtype=torch.float64, device=dev), c_disc=torch.zeros(E, dtype=torch.float64, device=dev),
-                           tp_disc=torch.zeros(E, dtype=torch.float64, device=dev), cr=f(E), c_loc=f(E), c_pow=f(E), tp_cr=f(E),
-                           tp_loc=f(E), tp_pow=f(E), steps=i32(E), games=i32(E), done=u8(E), terminated=u8(E), inverted=u8(E),
-                           n_full=i32(1), traj13=f(E, 13, 3), pose=f(E, 24, 3), vel=f(E, 2), row_mask=f(E))
+        zeros = lambda shape, dt: torch.zeros(shape, dtype=getattr(torch, dt), device=dev)
+        self._inputs = tuple(k for k, _ in EVAL_INPUTS)
+        self._s, self._b = eval_state(E, self.step_to_pred, G, self.gamma, {k: self._input(k) for k in self._inputs}, zeros,
+                                      torch.Tensor.data_ptr)
         # the forward's persistent output (a game's prediction stays in its row until the game is recorded) and its scratch rows
         N = len(nets)
         if self.multi:          # a value plane and a record plane per network: the table of emloco_locoval_eval_fwd_multi / _finish_multi
@@ -309,19 +345,11 @@ class LocoValEvaluator:
             self._value, self._x100, self._h1, self._h2, self._ang = f(E), f(E, n_in), f(E, n_h1), f(E, n_h2), f(E)
             self._records = torch.zeros(E * G * RECORD_WORDS, dtype=torch.int32, device=dev)
             self._moments = torch.zeros(ops.EVAL_MOMENTS, dtype=torch.float64, device=dev)
-        self._inputs = ("waypoint_traj", "init_pose", "init_vel")
-        p = lambda t: t.data_ptr()
-        self._s = ops.LocoValEval(E, self.step_to_pred, G, 0, self.gamma, *[p(b[k]) for k in (
-            "coef", "c_disc", "tp_disc", "cr", "c_loc", "c_pow", "tp_cr", "tp_loc", "tp_pow", "steps", "games", "done", "terminated",
-            "inverted", "n_full")], *[p(self._input(k)) for k in self._inputs], p(b["traj13"]), p(b["pose"]), p(b["vel"]), p(b["row_mask"]))
         if self.track:
-            f64 = lambda *s: torch.zeros(*s, dtype=torch.float64, device=dev)
-            self._tb = tb = dict(sum_dev=f64(E), sum_sample_dev=f64(E), path_len=f64(E), max_dev=f(E), prev_xy=f(E, 2),
-                                 last_sample_dev=f(E), n_samples=i32(E), dev_now=f(E))
+            self._t, self._tb = track_state(E, zeros, torch.Tensor.data_ptr, stride=self.track_stride)
             self._track_records = torch.zeros(E * G * TRACK_WORDS, dtype=torch.int32, device=dev)
             self._track_samples = f(E, G, ops.TRACK_SAMPLES, 4)
             self._track_moments = torch.zeros(ops.TRACK_MOMENTS, dtype=torch.float64, device=dev)
-            self._t = ops.LocoValTrack(stride=self.track_stride, **{k: p(v) for k, v in tb.items()})
         self.steps_run = 0
         self.started = False
         # --pred_path: the host reset knows which row of the predicted-path table every game walks; logged from the first reset on
@@ -333,7 +361,7 @@ class LocoValEvaluator:
     def _input(self, name):
         """The task's LocoVal inputs the kernel reads by address (15 x 3 waypoints, 24 x 3 joints, 2 velocity components per env)."""
         t = getattr(self.task, name)
-        want = {"waypoint_traj": (self.num_envs, 15, 3), "init_pose": (self.num_envs, 24, 3), "init_vel": (self.num_envs, 2)}[name]
+        want = (self.num_envs, *dict(EVAL_INPUTS)[name])
         if tuple(t.shape) != want or t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device:
             raise RuntimeError(f"LocoValEvaluator: task.{name} must be a contiguous float32 {want} tensor on {self.device}")
         return t
@@ -376,31 +404,29 @@ class LocoValEvaluator:
 
     def _launch(self, reward_raw, disc, dones, terminate, inverted):
         """The bookkeeping of one step on the current stream (also the entry point of the tests that script the streams)."""
-        import ctypes as C
         from ..predictor import ops
         from ..sim import current_stream_handle
         lib = ops._lib()
         st = current_stream_handle(self.device)
-        P = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         assert reward_raw.dtype == torch.float32 and reward_raw.shape == (self.num_envs, 2) and dones.dtype == torch.int64
         assert terminate is None or terminate.dtype == torch.int64
         if inverted is not None and inverted.dtype == torch.bool:
             inverted = inverted.view(torch.uint8)
         self._check_inputs()
-        ops._chk(lib.emloco_locoval_eval_step(C.byref(self._s), P(reward_raw.contiguous()), P(disc), P(dones.contiguous()),
-                                              P(None if terminate is None else terminate.contiguous()),
-                                              P(None if inverted is None else inverted.contiguous()), st), "emloco_locoval_eval_step")
+        ops._chk(lib.emloco_locoval_eval_step(C.byref(self._s), _p(reward_raw.contiguous()), _p(disc), _p(dones.contiguous()),
+                                              _p(None if terminate is None else terminate.contiguous()),
+                                              _p(None if inverted is None else inverted.contiguous()), st), "emloco_locoval_eval_step")
         if self.track:                              # once per step, whatever the number of networks: nothing tracked depends on them
-            ops._chk(lib.emloco_locoval_eval_track(C.byref(self._s), C.byref(self._track_inputs()), P(self._track_records),
-                                                   P(self._track_samples), st), "emloco_locoval_eval_track")
+            ops._chk(lib.emloco_locoval_eval_track(C.byref(self._s), C.byref(self._track_inputs()), _p(self._track_records),
+                                                   _p(self._track_samples), st), "emloco_locoval_eval_track")
         if self.multi:
             self._check_nets()
             ops._chk(lib.emloco_locoval_eval_fwd_multi(C.byref(self._s), C.byref(self._nets), st), "emloco_locoval_eval_fwd_multi")
-            ops._chk(lib.emloco_locoval_eval_finish_multi(C.byref(self._s), C.byref(self._nets), P(self._records), st),
+            ops._chk(lib.emloco_locoval_eval_finish_multi(C.byref(self._s), C.byref(self._nets), _p(self._records), st),
                      "emloco_locoval_eval_finish_multi")
             return
         self._forward(st)
-        ops._chk(lib.emloco_locoval_eval_finish(C.byref(self._s), P(self._value), P(self._records), st), "emloco_locoval_eval_finish")
+        ops._chk(lib.emloco_locoval_eval_finish(C.byref(self._s), _p(self._value), _p(self._records), st), "emloco_locoval_eval_finish")
 
     def _track_inputs(self):
         """The tracker reads what the task's reward kernel read this step: the addresses and constants of the task's own EmlocoTaskBufs."""
@@ -415,21 +441,16 @@ class LocoValEvaluator:
 
     def _forward(self, st):
         """LocoVal on the rows whose game took its first step (:128-134), into the persistent `value` rows."""
-        import ctypes as C
         from ..predictor import ops
-        P = lambda t: C.c_void_p(t.data_ptr())
-        b, n = self._b, self.valuenet._network
-        w = [n.fc1.weight, n.fc1.bias, n.fc2.weight, n.fc2.bias, n.fc3.weight, n.fc3.bias]
-        for t in w:
-            assert t.dtype == torch.float32 and t.is_contiguous() and t.device == self.device
+        b, w = self._b, self._weights(self.valuenet)
         if self.valuenet.variant == ops.LOCOVAL_FULL:
-            ops._chk(ops._lib().emloco_locoval_fwd_rows(self.num_envs, P(b["traj13"]), 3, P(b["pose"]), P(b["vel"]), *[P(t) for t in w],
-                                                        P(self._value), P(self._x100), P(self._h1), P(self._h2), P(self._ang), P(b["row_mask"]),
+            ops._chk(ops._lib().emloco_locoval_fwd_rows(self.num_envs, _p(b["traj13"]), 3, _p(b["pose"]), _p(b["vel"]), *[_p(t) for t in w],
+                                                        _p(self._value), _p(self._x100), _p(self._h1), _p(self._h2), _p(self._ang), _p(b["row_mask"]),
                                                         st), "emloco_locoval_fwd_rows")
         else:
-            ops._chk(ops._lib().emloco_locoval_variant_fwd_rows(self.valuenet.variant, self.num_envs, P(b["traj13"]), 3, P(b["pose"]), P(b["vel"]),
-                                                                *[P(t) for t in w], P(self._value), P(self._x100), P(self._h1), P(self._h2),
-                                                                P(self._ang), None, P(b["row_mask"]), st), "emloco_locoval_variant_fwd_rows")
+            ops._chk(ops._lib().emloco_locoval_variant_fwd_rows(self.valuenet.variant, self.num_envs, _p(b["traj13"]), 3, _p(b["pose"]), _p(b["vel"]),
+                                                                *[_p(t) for t in w], _p(self._value), _p(self._x100), _p(self._h1), _p(self._h2),
+                                                                _p(self._ang), None, _p(b["row_mask"]), st), "emloco_locoval_variant_fwd_rows")
 
     # ------------------------------------------------------------------ the run
     def envs_full(self):
@@ -446,33 +467,23 @@ class LocoValEvaluator:
         return self.report(say=say)
 
     def moments(self):
-        import ctypes as C
         from ..predictor import ops
         from ..sim import current_stream_handle
-        P = lambda t: C.c_void_p(t.data_ptr())
-        if self.multi:                              # one reduction per record plane -> [N][EVAL_MOMENTS], still one collective
-            rec = self._records.view(len(self.valuenets), -1)
-            for k in range(len(self.valuenets)):
-                ops._chk(ops._lib().emloco_locoval_eval_reduce(self.num_envs, self.games_per_env, P(rec[k]), P(self._b["games"]),
-                                                               P(self._moments[k]), current_stream_handle(self.device)),
-                         "emloco_locoval_eval_reduce")
-            m = self._moments.clone()
-            D.all_reduce_(m)
-            return m.cpu().numpy()
-        ops._chk(ops._lib().emloco_locoval_eval_reduce(self.num_envs, self.games_per_env, P(self._records), P(self._b["games"]),
-                                                       P(self._moments), current_stream_handle(self.device)), "emloco_locoval_eval_reduce")
+        # one reduction per record plane -> [N][EVAL_MOMENTS] (a list of networks) or [EVAL_MOMENTS], and the one collective of the evaluation
+        N = len(self.valuenets)
+        for rec, mom in zip(self._records.view(N, -1), self._moments.view(N, -1)):
+            ops._chk(ops._lib().emloco_locoval_eval_reduce(self.num_envs, self.games_per_env, _p(rec), _p(self._b["games"]), _p(mom),
+                                                           current_stream_handle(self.device)), "emloco_locoval_eval_reduce")
         m = self._moments.clone()
-        D.all_reduce_(m)                            # the one collective of the evaluation
+        D.all_reduce_(m)
         return m.cpu().numpy()
 
     def track_moments(self):
         """The track moment vector of all ranks: one reduction, one all-reduce of its own (the moment vector of `moments` is untouched)."""
-        import ctypes as C
         from ..predictor import ops
         from ..sim import current_stream_handle
-        P = lambda t: C.c_void_p(t.data_ptr())
-        ops._chk(ops._lib().emloco_locoval_track_reduce(self.num_envs, self.games_per_env, P(self._track_records), P(self._b["games"]),
-                                                        self.fail_dist, P(self._track_moments), current_stream_handle(self.device)),
+        ops._chk(ops._lib().emloco_locoval_track_reduce(self.num_envs, self.games_per_env, _p(self._track_records), _p(self._b["games"]),
+                                                        self.fail_dist, _p(self._track_moments), current_stream_handle(self.device)),
                  "emloco_locoval_track_reduce")
         m = self._track_moments.clone()
         D.all_reduce_(m)

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(os.path.dirname(_HERE))
 _EXTRA = os.environ.get("EMLOCO_EMU_EXTRA", "").split()          # e.g. -DEMLOCO_SIM_PAIR=1: the experimental two-envs-per-wave rigid-body kernel
 _SO = os.path.join(_HERE, "_build", "libemu" + ("_" + "".join(c for c in "".join(_EXTRA) if c.isalnum()) if _EXTRA else "") + ".so")
-_SRCS = ["emu_sim.cpp", "emu_task.cpp", "emu_predictor.cpp", "emu_ppo.cpp", "emu_runtime.cpp", "hip/hip_runtime.h"]
+_SRCS = ["emu_sim.cpp", "emu_task.cpp", "emu_predictor.cpp", "emu_ppo.cpp", "emu_eval.cpp", "emu_runtime.cpp", "hip/hip_runtime.h"]
 def build():
     """g++ over the kernel sources; every file under emloco_amd/csrc and include/ is a dependency.  Built under a file lock into a
     temporary name and renamed, so that the workers of a parallel test run neither build twice at once nor load a half-written file."""
@@ -43,6 +43,10 @@ def lib():
     global _lib
     if _lib is None:
         _lib = C.CDLL(build())
+        # the evaluation's records as locoval_eval.py views them (RECORD_DTYPE, TRACK_DTYPE)
+        assert _lib.emu_locoval_record_size() == 48 and _lib.emu_locoval_track_record_size() == 32
+        _lib.emu_locoval_track_reduce.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
+        _lib.emu_traj_densify_error.restype = C.c_char_p
     return _lib
 
 

@@ -1,9 +1,8 @@
-// TEST INFRASTRUCTURE ONLY: runs the path tracking of emloco_amd/csrc/eval_kernels.hip on the CPU through tests/emu/hip/, between the real
-// step and finish kernels (tests/test_locoval_eval_track_cpu.py compiles it with emu/emu_runtime.cpp).  The launch geometry is the C ABI's
+// TEST INFRASTRUCTURE ONLY: runs emloco_amd/csrc/eval_kernels.hip on the CPU through tests/emu/hip/.  The launch geometry is the C ABI's
 // (eval_capi.hip).
 #include <stdint.h>
 #include "hip/hip_runtime.h"
-#include "../emloco_amd/csrc/eval_kernels.hip"
+#include "../../emloco_amd/csrc/eval_kernels.hip"
 
 using namespace emloco;
 
@@ -31,10 +30,25 @@ extern "C" int emu_locoval_eval_finish(const EmlocoLocoValEval *s, const float *
     return 0;
 }
 
+extern "C" int emu_locoval_eval_finish_multi(const EmlocoLocoValEval *s, const EmlocoLocoValNets *nets, EmlocoLocoValRecord *records) {
+    const EmlocoLocoValEval t = *s;
+    const EmlocoLocoValNets n = *nets;
+    emu::launch((unsigned)((t.n_env + 255) / 256), 256, [&] { locoval_eval_finish_multi_kernel(t, n, records); });
+    blockIdx.x = 0;
+    return 0;
+}
+
+extern "C" int emu_locoval_eval_reduce(int n_env, int games_per_env, const EmlocoLocoValRecord *records, const int32_t *games,
+                                       double *moments) {
+    emu::launch(1, kEvalReduceThreads, [&] { locoval_eval_reduce_kernel(n_env, games_per_env, records, games, moments); });
+    return 0;
+}
+
 extern "C" int emu_locoval_track_reduce(int n_env, int games_per_env, const EmlocoLocoValTrackRecord *records, const int32_t *games,
                                         float fail_dist, double *moments) {
     emu::launch(1, kEvalReduceThreads, [&] { locoval_track_reduce_kernel(n_env, games_per_env, records, games, fail_dist, moments); });
     return 0;
 }
 
+extern "C" int emu_locoval_record_size() { return (int)sizeof(EmlocoLocoValRecord); }
 extern "C" int emu_locoval_track_record_size() { return (int)sizeof(EmlocoLocoValTrackRecord); }

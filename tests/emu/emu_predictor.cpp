@@ -199,17 +199,69 @@ extern "C" int emu_adam_clip_flat(long n, float *p, float *g, float *m, float *v
     return 0;
 }
 extern "C" long emu_layernorm_bwd_workspace(int rows, int d) { return fold_workspace((rows + LN_ROWS_PER_BLOCK - 1) / LN_ROWS_PER_BLOCK, 2L * d); }
-extern "C" int emu_locoval_fwd(int B, const float *traj, int ts, const float *pose, const float *vel, const float *w1,
-                               const float *b1, const float *w2, const float *b2, const float *w3, const float *b3,
-                               float *value, float *x100, float *h1, float *h2, float *angle) {
-    emu::launch((unsigned)B, 64, [&] { locoval_fwd_kernel(B, traj, ts, pose, vel, w1, b1, w2, b2, w3, b3, value, x100, h1, h2, angle, (const float *)nullptr); });
+// the full network's kernels as emloco_locoval_fwd / _fwd_rows (row_weight NULL: every row) and emloco_locoval_bwd / _bwd_rows (slot / count
+// NULL: the dense backward) launch them (predictor_capi.hip)
+extern "C" int emu_locoval_fwd(int B, const float *traj, int ts, const float *pose, const float *vel, const float *w1, const float *b1,
+                               const float *w2, const float *b2, const float *w3, const float *b3, float *value, float *x100, float *h1,
+                               float *h2, float *angle, const float *row_weight) {
+    emu::launch((unsigned)B, 64, [&] { locoval_fwd_kernel(B, traj, ts, pose, vel, w1, b1, w2, b2, w3, b3, value, x100, h1, h2, angle, row_weight); });
+    blockIdx.x = 0;
     return 0;
 }
-extern "C" int emu_locoval_bwd(int B, const float *traj, int ts, const float *pose, const float *vel, const float *w1,
-                               const float *w2, const float *w3, const float *value, const float *x100, const float *h1,
-                               const float *h2, const float *angle, const float *dvalue, float *dparams, float *dtraj, float *ws) {
-    emu::launch((unsigned)B, 64, [&] { locoval_bwd_kernel(B, traj, ts, pose, vel, w1, w2, w3, value, x100, h1, h2, angle, dvalue, ws, dtraj, (const int32_t *)nullptr); });
-    emu::launch((unsigned)((LV_NPARAM + 255) / 256), 256, [&] { locoval_reduce_kernel(B, ws, dparams, (const float *)nullptr); });
+extern "C" int emu_locoval_bwd(int B, const float *traj, int ts, const float *pose, const float *vel, const float *w1, const float *w2,
+                               const float *w3, const float *value, const float *x100, const float *h1, const float *h2,
+                               const float *angle, const float *dvalue, const int32_t *slot, const float *count, float *dparams,
+                               float *dtraj, float *ws) {
+    emu::launch((unsigned)B, 64, [&] { locoval_bwd_kernel(B, traj, ts, pose, vel, w1, w2, w3, value, x100, h1, h2, angle, dvalue, ws, dtraj, slot); });
+    emu::launch((unsigned)((LV_NPARAM + 255) / 256), 256, [&] { locoval_reduce_kernel(B, ws, dparams, count); });
+    blockIdx.x = 0;
+    return 0;
+}
+
+// ---- the reduced-input LocoVal networks (locoval_variants.h) through the product's own dispatch (emloco::locoval_variant_fwd / _bwd) with
+// a launcher that runs the kernel on the emulator
+namespace {
+struct EmuLaunch {
+    template <class K, class... A> void operator()(K kernel, unsigned grid, unsigned block, A... args) const {
+        emu::launch(grid, block, [&] { kernel(args...); });
+        blockIdx.x = 0;
+    }
+};
+}  // namespace
+
+extern "C" int emu_locoval_variant_dims(int variant, int32_t *dims4) {
+    LocoValDims d;
+    if (!locoval_dims(variant, &d)) return -1;
+    dims4[0] = d.in; dims4[1] = d.h1; dims4[2] = d.h2; dims4[3] = d.n_param;
+    return 0;
+}
+
+extern "C" int emu_locoval_variant_fwd_rows(int variant, int B, const float *traj, int ts, const float *pose, const float *vel, const float *w1,
+                                            const float *b1, const float *w2, const float *b2, const float *w3, const float *b3, float *value,
+                                            float *x, float *h1, float *h2, float *angle, float *pose_rot, const float *row_weight) {
+    const LocoValFwd a{B, traj, ts, pose, vel, w1, b1, w2, b2, w3, b3, value, x, h1, h2, angle, pose_rot, row_weight};
+    locoval_variant_fwd(EmuLaunch{}, variant, a);
+    return 0;
+}
+
+// slot / count NULL: the dense backward (emloco_locoval_variant_bwd)
+extern "C" int emu_locoval_variant_bwd_rows(int variant, int B, const float *traj, int ts, const float *pose, const float *vel, const float *w1,
+                                            const float *w2, const float *w3, const float *value, const float *x, const float *h1,
+                                            const float *h2, const float *angle, const float *dvalue, const int32_t *slot, const float *count,
+                                            float *dparams, float *dtraj, float *ws) {
+    const LocoValBwd a{B, traj, ts, pose, vel, w1, w2, w3, value, x, h1, h2, angle, dvalue, ws, dparams, dtraj, slot, count};
+    locoval_variant_bwd(EmuLaunch{}, variant, a);
+    return 0;
+}
+
+// several networks on the evaluation's staged rows (locoval_multi.h), launched as emloco_locoval_eval_fwd_multi launches it
+extern "C" int emu_locoval_eval_fwd_multi(const EmlocoLocoValEval *s, const EmlocoLocoValNets *nets) {
+    const EmlocoLocoValEval t = *s;
+    const EmlocoLocoValNets n = *nets;
+    emu::launch((unsigned)t.n_env, 64, [&] {
+        locoval_eval_fwd_multi_kernel(t.n_env, (const float *)t.traj13, (const float *)t.pose, (const float *)t.vel, (const float *)t.row_mask, n);
+    });
+    blockIdx.x = 0;
     return 0;
 }
 

@@ -4,6 +4,7 @@
 #include "../../emloco_amd/csrc/task_kernels.hip"
 #include "../../emloco_amd/csrc/reset_kernels.hip"
 #include "../../emloco_amd/csrc/chain_kernels.hip"
+#include "../../emloco_amd/csrc/traj_kernels.hip"
 
 extern "C" int emu_task_post_physics(const EmlocoTaskBufs *b, int mode, const int32_t *env_ids, int n) {
     const int count = env_ids ? n : b->n_env;
@@ -70,5 +71,25 @@ extern "C" int emu_reset_obs_live(const EmlocoTaskBufs *pb, int live_mode, const
 extern "C" int emu_task_post_physics_returns(const EmlocoTaskBufs *b, int mode, const EmlocoLocoValStep *step, const uint8_t *inverted) {
     EmlocoLocoValStep lv = *step;
     emu::launch((unsigned)b->n_env, 64, [&] { emloco::post_physics_returns_kernel(*b, mode, lv, inverted); });
+    return 0;
+}
+
+// traj_densify_kernel with the arguments of emloco_traj_densify (include/emloco_task.h), all arrays on the host; validation and packing
+// are the product's own (emloco::densify_pack), the launch is the emulator's
+static const char *g_densify_why = "";
+
+extern "C" const char *emu_traj_densify_error(void) { return g_densify_why; }
+
+extern "C" int emu_traj_densify(const float *knot_t, int n_knots, const float *way, int64_t n_traj, const float *query_t, int n_query,
+                                float *out, uint8_t *valid, int flags) {
+    emloco::DensifyArgs a;
+    const char *why = emloco::densify_pack(knot_t, n_knots, (long long)n_traj, query_t, n_query, flags, &a);
+    g_densify_why = why ? why : "";
+    if (why) return -1;
+    if (n_traj == 0) return 0;
+    if (!way || !out) return -1;
+    emu::launch((unsigned)((n_traj + emloco::DENSIFY_TPB - 1) / emloco::DENSIFY_TPB), emloco::DENSIFY_THREADS,
+                [&] { emloco::traj_densify_kernel(a, way, out, valid); });
+    blockIdx.x = 0;
     return 0;
 }

@@ -661,7 +661,8 @@ def test_locoval_kernels_match_reference_golden(golden):
                               g["_network_fc2_bias"], g["_network_fc3_weight"], g["_network_fc3_bias"])
     value, x100 = np.zeros(B, np.float32), np.zeros((B, 100), np.float32)
     h1, h2, ang = np.zeros((B, 49), np.float32), np.zeros((B, 24), np.float32), np.zeros(B, np.float32)
-    lib.emu_locoval_fwd(B, P(traj), 3, P(pose), P(vel), P(w1), P(b1), P(w2), P(b2), P(w3), P(b3), P(value), P(x100), P(h1), P(h2), P(ang))
+    lib.emu_locoval_fwd(B, P(traj), 3, P(pose), P(vel), P(w1), P(b1), P(w2), P(b2), P(w3), P(b3), P(value), P(x100), P(h1), P(h2), P(ang),
+                        None)
     np.testing.assert_allclose(value, g["value"][:, 0], rtol=1e-5, atol=1e-6)
     # the reference mutates the caller's pose in place (rotation + hidden joints): our x100 carries that result
     np.testing.assert_allclose(x100[:, 26:98].reshape(B, 24, 3), g["pose_after_inplace"], rtol=1e-5, atol=1e-6)
@@ -671,7 +672,7 @@ def test_locoval_kernels_match_reference_golden(golden):
     dparams, dtraj = np.zeros(6174, np.float32), np.zeros_like(traj)
     ws = np.zeros(B * 6174, np.float32)
     lib.emu_locoval_bwd(B, P(traj), 3, P(pose), P(vel), P(w1), P(w2), P(w3), P(value), P(x100), P(h1), P(h2), P(ang),
-                        P(dvalue), P(dparams), P(dtraj), P(ws))
+                        P(dvalue), None, None, P(dparams), P(dtraj), P(ws))
     np.testing.assert_allclose(dtraj, g["grad_traj"], rtol=2e-4, atol=1e-7)
     o = 0
     for name, shape in (("fc1_weight", (49, 100)), ("fc1_bias", (49,)), ("fc2_weight", (24, 49)), ("fc2_bias", (24,)),

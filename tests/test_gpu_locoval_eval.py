@@ -47,6 +47,7 @@ def test_eval_kernels_match_the_reference_player_for_257_shifted_envs():
     import ctypes as C
     from emloco_amd.learning.locoval_eval import RECORD_DTYPE, RECORD_WORDS, moments_from_records
     from emloco_amd.predictor import ops
+    from locoval_harness import _ptr as P, eval_state
     from test_locoval_eval_cpu import assert_records_equal_fixture, fixture, run_restatement, shifted_script
     fx = fixture()
     E, K = 257, len(fx["lengths"])
@@ -57,21 +58,10 @@ def test_eval_kernels_match_the_reference_player_for_257_shifted_envs():
     assert_records_equal_fixture(want, fx, order)
     g = torch.Generator().manual_seed(5)
     wp, ip, iv = (torch.randn(*sh, generator=g).to(dev) for sh in ((E, 15, 3), (E, 24, 3), (E, 2)))
-    f64 = lambda: torch.zeros(E, dtype=torch.float64, device=dev)
-    b = dict(coef=torch.ones(E, dtype=torch.float64, device=dev), c_disc=f64(), tp_disc=f64(),
-             **{k: torch.zeros(E, device=dev) for k in ("cr", "c_loc", "c_pow", "tp_cr", "tp_loc", "tp_pow", "row_mask")},
-             steps=torch.zeros(E, dtype=torch.int32, device=dev), games=torch.zeros(E, dtype=torch.int32, device=dev),
-             **{k: torch.zeros(E, dtype=torch.uint8, device=dev) for k in ("done", "terminated", "inverted")},
-             n_full=torch.zeros(1, dtype=torch.int32, device=dev), traj13=torch.zeros(E, 13, 3, device=dev),
-             pose=torch.zeros(E, 24, 3, device=dev), vel=torch.zeros(E, 2, device=dev))
-    st = ops.LocoValEval(E, int(fx["step_to_pred"]), K, 0, float(fx["gamma"]), *[b[k].data_ptr() for k in (
-        "coef", "c_disc", "tp_disc", "cr", "c_loc", "c_pow", "tp_cr", "tp_loc", "tp_pow", "steps", "games", "done", "terminated",
-        "inverted", "n_full")], wp.data_ptr(), ip.data_ptr(), iv.data_ptr(), b["traj13"].data_ptr(), b["pose"].data_ptr(),
-        b["vel"].data_ptr(), b["row_mask"].data_ptr())
+    st, b = eval_state(E, K, int(fx["step_to_pred"]), float(fx["gamma"]), device=dev, waypoint_traj=wp, init_pose=ip, init_vel=iv)
     lib = ops._lib()
     value = torch.zeros(E, device=dev)
     records = torch.zeros(E * K * RECORD_WORDS, dtype=torch.int32, device=dev)
-    P = lambda t: C.c_void_p(t.data_ptr())
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     rr_all = up(np.stack([s["r_loc"], s["r_pow"]], axis=2))
     disc_all, dones_all, term_all, inv_all = up(s["disc"]), up(s["dones"]), up(s["terminate"]), up(s["inverted"].astype(np.uint8))

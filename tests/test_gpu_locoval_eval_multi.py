@@ -21,13 +21,13 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
+from locoval_harness import DIMS, _ptr as P, eval_state  # noqa: E402
 from test_gpu_locoval_variants import TorchVariantNet, _embed_in_full, _net  # noqa: E402
-from test_locoval_variants_cpu import DIMS, VARIANTS  # noqa: E402
+from test_locoval_variants_cpu import VARIANTS  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENV_ARGS = ["--random_heading", "--init_heading", "--heading_inversion", "--adjust_root_vel"]
 DEV = "cuda:0"
-P = lambda t: None if t is None else C.c_void_p(t.data_ptr())
 
 
 def _weights(net):
@@ -200,17 +200,7 @@ def _time_step(rounds=60, warmup=8, E=4096, period=32):
     nets = [_net(name, dev, seed=5 + v) for name, v in VARIANTS.items()]
 
     def state():
-        z = lambda dt: torch.zeros(E, dtype=dt, device=dev)
-        b = dict(coef=torch.ones(E, dtype=torch.float64, device=dev), c_disc=z(torch.float64), tp_disc=z(torch.float64),
-                 **{k: z(torch.float32) for k in ("cr", "c_loc", "c_pow", "tp_cr", "tp_loc", "tp_pow", "row_mask")}, steps=z(torch.int32),
-                 games=z(torch.int32), done=z(torch.uint8), terminated=z(torch.uint8), inverted=z(torch.uint8),
-                 n_full=torch.zeros(1, dtype=torch.int32, device=dev), traj13=torch.zeros(E, 13, 3, device=dev),
-                 pose=torch.zeros(E, 24, 3, device=dev), vel=torch.zeros(E, 2, device=dev))
-        s = ops.LocoValEval(E, 5, G, 0, 0.99, *[b[k].data_ptr() for k in (
-            "coef", "c_disc", "tp_disc", "cr", "c_loc", "c_pow", "tp_cr", "tp_loc", "tp_pow", "steps", "games", "done", "terminated",
-            "inverted", "n_full")], wp.data_ptr(), ip.data_ptr(), iv.data_ptr(), b["traj13"].data_ptr(), b["pose"].data_ptr(),
-            b["vel"].data_ptr(), b["row_mask"].data_ptr())
-        return s, b
+        return eval_state(E, G, 5, 0.99, device=dev, waypoint_traj=wp, init_pose=ip, init_vel=iv)
 
     N = len(nets)
     ms, mb = state()

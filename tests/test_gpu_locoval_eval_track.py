@@ -27,6 +27,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 import track_cases as TC  # noqa: E402
+from locoval_harness import _ptr as P, eval_state, track_state  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENV_ARGS = ["--random_heading", "--init_heading", "--heading_inversion", "--adjust_root_vel"]
@@ -40,23 +41,12 @@ def run_device(case):
     dev = torch.device("cuda:0")
     lib = ops._lib()
     z = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device=dev)
-    b = dict(coef=torch.ones(E, dtype=torch.float64, device=dev), c_disc=z(E, dt=torch.float64), tp_disc=z(E, dt=torch.float64),
-             **{k: z(E) for k in ("cr", "c_loc", "c_pow", "tp_cr", "tp_loc", "tp_pow", "row_mask")},
-             steps=z(E, dt=torch.int32), games=z(E, dt=torch.int32), **{k: z(E, dt=torch.uint8) for k in ("done", "terminated", "inverted")},
-             n_full=z(1, dt=torch.int32))
-    io = [z(*s) for s in ((E, 15, 3), (E, 24, 3), (E, 2), (E, 13, 3), (E, 24, 3), (E, 2))]
-    st = ops.LocoValEval(E, 144, G, 0, 0.99, *[b[k].data_ptr() for k in (
-        "coef", "c_disc", "tp_disc", "cr", "c_loc", "c_pow", "tp_cr", "tp_loc", "tp_pow", "steps", "games", "done", "terminated",
-        "inverted", "n_full")], *[a.data_ptr() for a in io], b["row_mask"].data_ptr())
-    tb = dict(sum_dev=z(E, dt=torch.float64), sum_sample_dev=z(E, dt=torch.float64), path_len=z(E, dt=torch.float64), max_dev=z(E),
-              prev_xy=z(E, 2), last_sample_dev=z(E), n_samples=z(E, dt=torch.int32))
-    t = ops.LocoValTrack(stride=case["stride"], root_stride=TC.ROOT_STRIDE, dt=float(case["dt"]), traj_dur=float(case["traj_dur"]),
-                         **{k: v.data_ptr() for k, v in tb.items()})
+    st, b = eval_state(E, G, device=dev)
+    t, _tb = track_state(case, device=dev)
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     verts, root, prog, dones = up(case["verts"][:T]), up(case["root"][:T]), up(case["progress"][:T]), up(case["dones"][:T])
     records, track = z(E * G * RECORD_WORDS, dt=torch.int32), z(E * G * TRACK_WORDS, dt=torch.int32)
     samples, value, rr, dev_now = z(E, G, TC.TRACK_SAMPLES, 4), z(E), torch.ones(E, 2, device=dev), z(T, E)
-    P = lambda x: C.c_void_p(x.data_ptr())
     for k in range(T):
         t.root_pos, t.traj_verts, t.progress_buf, t.dev_now = root[k].data_ptr(), verts[k].data_ptr(), prog[k].data_ptr(), dev_now[k].data_ptr()
         assert lib.emloco_locoval_eval_step(C.byref(st), P(rr), None, P(dones[k]), None, None, None) == 0

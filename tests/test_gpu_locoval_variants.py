@@ -21,7 +21,8 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-from test_locoval_variants_cpu import DIMS, GRAD_TOL, VALUE_TOL, VARIANTS, fixture, restate  # noqa: E402
+from locoval_harness import DIMS  # noqa: E402
+from test_locoval_variants_cpu import GRAD_TOL, VALUE_TOL, VARIANTS, fixture, restate  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENV_ARGS = ["--random_heading", "--init_heading", "--heading_inversion", "--adjust_root_vel"]

@@ -15,8 +15,10 @@ import subprocess
 import sys
 
 import numpy as np
-import pytest
 import torch
+
+import emu
+from locoval_harness import _ptr, eval_state
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURE = os.path.join(ROOT, "tests", "golden", "locoval_player.npz")
@@ -208,24 +210,9 @@ def test_report_of_no_games_and_of_constant_values():
 
 
 # ------------------------------------------------------------------------------------------------------------ the kernels, emulated
-@pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("emu_eval") / "libemu_eval.so")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-x", "c++", "-ffp-contract=off", "-DEMLOCO_EMU", "-Wno-psabi",
-                           "-I", os.path.join(ROOT, "tests", "emu"), "-o", so, os.path.join(ROOT, "tests", "emu_locoval_eval.cpp"),
-                           os.path.join(ROOT, "tests", "emu", "emu_runtime.cpp"), "-lpthread"], timeout=300)
-    lib = C.CDLL(so)
-    assert lib.emu_locoval_record_size() == 48
-    return lib
-
-
-def _ptr(a):
-    return C.c_void_p(a.ctypes.data) if a is not None else None
-
-
-def test_emulated_kernels_equal_the_restatement_bit_for_bit(emu):
-    from emloco_amd.predictor.ops import LocoValEval
+def test_emulated_kernels_equal_the_restatement_bit_for_bit():
     from emloco_amd.learning.locoval_eval import RECORD_DTYPE, RECORD_WORDS, moments_from_records
+    lib = emu.lib()
     fx = fixture()
     E, K = 67, len(fx["lengths"])
     R, s, order = run_restatement(fx, E)
@@ -234,14 +221,7 @@ def test_emulated_kernels_equal_the_restatement_bit_for_bit(emu):
     wp = rng.standard_normal((E, 15, 3)).astype(np.float32)
     ip = rng.standard_normal((E, 24, 3)).astype(np.float32)
     iv = rng.standard_normal((E, 2)).astype(np.float32)
-    b = dict(coef=np.ones(E), c_disc=np.zeros(E), tp_disc=np.zeros(E), **{k: np.zeros(E, np.float32) for k in
-             ("cr", "c_loc", "c_pow", "tp_cr", "tp_loc", "tp_pow", "row_mask")}, steps=np.zeros(E, np.int32), games=np.zeros(E, np.int32),
-             done=np.zeros(E, np.uint8), terminated=np.zeros(E, np.uint8), inverted=np.zeros(E, np.uint8), n_full=np.zeros(1, np.int32),
-             traj13=np.zeros((E, 13, 3), np.float32), pose=np.zeros((E, 24, 3), np.float32), vel=np.zeros((E, 2), np.float32))
-    st = LocoValEval(E, int(fx["step_to_pred"]), K, 0, float(fx["gamma"]), *[b[k].ctypes.data for k in (
-        "coef", "c_disc", "tp_disc", "cr", "c_loc", "c_pow", "tp_cr", "tp_loc", "tp_pow", "steps", "games", "done", "terminated",
-        "inverted", "n_full")], wp.ctypes.data, ip.ctypes.data, iv.ctypes.data, b["traj13"].ctypes.data, b["pose"].ctypes.data,
-        b["vel"].ctypes.data, b["row_mask"].ctypes.data)
+    st, b = eval_state(E, K, int(fx["step_to_pred"]), float(fx["gamma"]), waypoint_traj=wp, init_pose=ip, init_vel=iv)
     value = np.zeros(E, np.float32)
     records = np.zeros(E * K * RECORD_WORDS, np.int32)
     T = s["r_loc"].shape[0]
@@ -249,14 +229,14 @@ def test_emulated_kernels_equal_the_restatement_bit_for_bit(emu):
         rr = np.ascontiguousarray(np.stack([s["r_loc"][t], s["r_pow"][t]], axis=1))
         disc, dones, term = [np.ascontiguousarray(s[k][t]) for k in ("disc", "dones", "terminate")]
         inv = np.ascontiguousarray(s["inverted"][t].astype(np.uint8))
-        assert emu.emu_locoval_eval_step(C.byref(st), _ptr(rr), _ptr(disc), _ptr(dones), _ptr(term), _ptr(inv)) == 0
+        assert lib.emu_locoval_eval_step(C.byref(st), _ptr(rr), _ptr(disc), _ptr(dones), _ptr(term), _ptr(inv)) == 0
         first = b["row_mask"] != 0
         if first.any():                                           # the LocoVal inputs of the game's first step, origin-relative
             assert np.array_equal(b["traj13"][first], (wp[:, :13] - wp[:, :1])[first])
             assert np.array_equal(b["pose"][first], (ip - ip[:, :1])[first])
             assert np.array_equal(b["vel"][first], iv[first])
         value[first] = fx["values"][s["gid"][t]][first]          # stands where emloco_locoval_fwd_rows writes the masked rows
-        assert emu.emu_locoval_eval_finish(C.byref(st), _ptr(value), _ptr(records)) == 0
+        assert lib.emu_locoval_eval_finish(C.byref(st), _ptr(value), _ptr(records)) == 0
     assert np.array_equal(b["games"], np.full(E, K)) and int(b["n_full"][0]) == E
     raw = records.view(RECORD_DTYPE).reshape(E, K)
     got = raw[want["env"], want["game"]]
@@ -264,32 +244,26 @@ def test_emulated_kernels_equal_the_restatement_bit_for_bit(emu):
         assert got[k].tobytes() == want[k].tobytes(), k
     assert_records_equal_fixture(want, fx, order)
     mom = np.zeros(20)
-    assert emu.emu_locoval_eval_reduce(E, K, _ptr(records), _ptr(b["games"]), _ptr(mom)) == 0
+    assert lib.emu_locoval_eval_reduce(E, K, _ptr(records), _ptr(b["games"]), _ptr(mom)) == 0
     ref = moments_from_records(want)
     np.testing.assert_allclose(mom, ref, rtol=1e-12, atol=0)
 
 
-def test_quota_records_only_the_first_games_of_each_env(emu):
+def test_quota_records_only_the_first_games_of_each_env():
     """G = 2: an env records its first two games and nothing after them (no over-sampling of short games)."""
-    from emloco_amd.predictor.ops import LocoValEval
     from emloco_amd.learning.locoval_eval import RECORD_DTYPE, RECORD_WORDS
+    lib = emu.lib()
     E, G, T = 3, 2, 12
     dones = np.zeros((T, E), np.int64)
     for e, ends in enumerate([[0, 1, 2, 3, 4], [5, 11], [11]]):      # env 0: five one-step games, env 1: two games, env 2: one
         dones[ends, e] = 1
-    b = dict(coef=np.ones(E), c_disc=np.zeros(E), tp_disc=np.zeros(E), **{k: np.zeros(E, np.float32) for k in
-             ("cr", "c_loc", "c_pow", "tp_cr", "tp_loc", "tp_pow", "row_mask")}, steps=np.zeros(E, np.int32), games=np.zeros(E, np.int32),
-             done=np.zeros(E, np.uint8), terminated=np.zeros(E, np.uint8), inverted=np.zeros(E, np.uint8), n_full=np.zeros(1, np.int32))
-    io = [np.zeros(s, np.float32) for s in ((E, 15, 3), (E, 24, 3), (E, 2), (E, 13, 3), (E, 24, 3), (E, 2))]
-    st = LocoValEval(E, 144, G, 0, 0.99, *[b[k].ctypes.data for k in (
-        "coef", "c_disc", "tp_disc", "cr", "c_loc", "c_pow", "tp_cr", "tp_loc", "tp_pow", "steps", "games", "done", "terminated",
-        "inverted", "n_full")], *[a.ctypes.data for a in io], b["row_mask"].ctypes.data)
+    st, b = eval_state(E, G)
     records = np.zeros(E * G * RECORD_WORDS, np.int32)
     value = np.zeros(E, np.float32)
     rr = np.ones((E, 2), np.float32)
     for t in range(T):
-        emu.emu_locoval_eval_step(C.byref(st), _ptr(rr), None, _ptr(np.ascontiguousarray(dones[t])), None, None)
-        emu.emu_locoval_eval_finish(C.byref(st), _ptr(value), _ptr(records))
+        lib.emu_locoval_eval_step(C.byref(st), _ptr(rr), None, _ptr(np.ascontiguousarray(dones[t])), None, None)
+        lib.emu_locoval_eval_finish(C.byref(st), _ptr(value), _ptr(records))
     assert list(b["games"]) == [2, 2, 1] and int(b["n_full"][0]) == 2
     raw = records.view(RECORD_DTYPE).reshape(E, G)
     assert list(raw["steps"][0]) == [1, 1] and list(raw["steps"][1]) == [6, 6] and raw["steps"][2, 0] == 12

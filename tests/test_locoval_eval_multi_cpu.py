@@ -22,24 +22,12 @@ import numpy as np
 import pytest
 import torch
 
-from test_locoval_variants_cpu import DIMS
+import emu
+from locoval_harness import DIMS, _ptr, eval_state
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E, T, G, STEP_TO_PRED, GAMMA = 8, 40, 5, 5, 0.99
 NETS = (3, 1, 0)                                  # the full, the velocity-only (28) and the trajectory-only (26) network
-
-
-@pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("emu_eval_multi") / "libemu_eval_multi.so")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-x", "c++", "-ffp-contract=off", "-DEMLOCO_EMU", "-Wno-psabi", "-w",
-                           "-I", os.path.join(ROOT, "tests", "emu"), "-o", so, os.path.join(ROOT, "tests", "emu_locoval_eval_multi.cpp"),
-                           os.path.join(ROOT, "tests", "emu", "emu_runtime.cpp"), "-lpthread"], timeout=900)
-    return C.CDLL(so)
-
-
-def _ptr(a):
-    return C.c_void_p(a.ctypes.data) if a is not None else None
 
 
 def params_of(variant, seed):
@@ -65,23 +53,16 @@ def script():
                 ip=(rng.standard_normal((T, E, 24, 3)) * 0.3).astype(np.float32), iv=rng.standard_normal((T, E, 2)).astype(np.float32))
 
 
-def play(lib, nets, multi):
+def play(nets, multi):
     """The scripted evaluation.  nets: [(variant, params)].  multi: the table through the two new entry points; otherwise ONE network
     through the existing three launches.  Returns the record planes [N][E][G], the moments [N][20], the games counters and, per step,
     whether the staged pose was left as the step staged it."""
     from emloco_amd.learning.locoval_eval import RECORD_DTYPE, RECORD_WORDS
-    from emloco_amd.predictor.ops import LocoValEval, LocoValNet, LocoValNets
-    s, N = script(), len(nets)
+    from emloco_amd.predictor.ops import LocoValNet, LocoValNets
+    lib, s, N = emu.lib(), script(), len(nets)
     assert multi or N == 1
-    b = dict(coef=np.ones(E), c_disc=np.zeros(E), tp_disc=np.zeros(E), **{k: np.zeros(E, np.float32) for k in
-             ("cr", "c_loc", "c_pow", "tp_cr", "tp_loc", "tp_pow", "row_mask")}, steps=np.zeros(E, np.int32), games=np.zeros(E, np.int32),
-             done=np.zeros(E, np.uint8), terminated=np.zeros(E, np.uint8), inverted=np.zeros(E, np.uint8), n_full=np.zeros(1, np.int32),
-             traj13=np.zeros((E, 13, 3), np.float32), pose=np.zeros((E, 24, 3), np.float32), vel=np.zeros((E, 2), np.float32))
-    wp, ip, iv = np.zeros((E, 15, 3), np.float32), np.zeros((E, 24, 3), np.float32), np.zeros((E, 2), np.float32)
-    st = LocoValEval(E, STEP_TO_PRED, G, 0, GAMMA, *[b[k].ctypes.data for k in (
-        "coef", "c_disc", "tp_disc", "cr", "c_loc", "c_pow", "tp_cr", "tp_loc", "tp_pow", "steps", "games", "done", "terminated",
-        "inverted", "n_full")], wp.ctypes.data, ip.ctypes.data, iv.ctypes.data, b["traj13"].ctypes.data, b["pose"].ctypes.data,
-        b["vel"].ctypes.data, b["row_mask"].ctypes.data)
+    st, b = eval_state(E, G, STEP_TO_PRED, GAMMA)
+    wp, ip, iv = b["waypoint_traj"], b["init_pose"], b["init_vel"]
     values = np.full((N, E), 0.25, np.float32)
     records = np.zeros(N * E * G * RECORD_WORDS, np.int32)
     table = LocoValNets(n_nets=N)
@@ -101,7 +82,7 @@ def play(lib, nets, multi):
             (v, p), (x, h1, h2, ang) = nets[0], scratch[0]
             head = [E, _ptr(b["traj13"]), 3, _ptr(b["pose"]), _ptr(b["vel"]), *[_ptr(a) for a in p], _ptr(values[0]), _ptr(x), _ptr(h1), _ptr(h2), _ptr(ang)]
             if v == 3:                              # as LocoValEvaluator._forward: the full network through its own entry point
-                assert lib.emu_locoval_old_fwd_rows(*head, _ptr(b["row_mask"])) == 0
+                assert lib.emu_locoval_fwd(*head, _ptr(b["row_mask"])) == 0
             else:
                 assert lib.emu_locoval_variant_fwd_rows(v, *head, None, _ptr(b["row_mask"])) == 0
         pose_kept.append(all(np.array_equal(staged[k], b[k]) for k in staged))
@@ -123,13 +104,13 @@ def nets():
 
 
 @pytest.fixture(scope="module")
-def multi_run(emu, nets):
-    return play(emu, nets, multi=True)
+def multi_run(nets):
+    return play(nets, multi=True)
 
 
 @pytest.fixture(scope="module")
-def single_runs(emu, nets):
-    return [play(emu, [n], multi=False) for n in nets]
+def single_runs(nets):
+    return [play([n], multi=False) for n in nets]
 
 
 def test_the_script_covers_the_games_the_issue_names(single_runs):
@@ -164,20 +145,20 @@ def test_planes_differ_in_value_and_sq_err_alone(multi_run):
         assert not np.array_equal(planes[k]["value"], planes[0]["value"])
 
 
-def test_one_network_through_the_new_path_equals_the_existing_path(emu, nets, single_runs):
+def test_one_network_through_the_new_path_equals_the_existing_path(nets, single_runs):
     for n, single in zip(nets, single_runs):
-        one = play(emu, [n], multi=True)
+        one = play([n], multi=True)
         assert one["planes"].tobytes() == single["planes"].tobytes()
         assert np.array_equal(one["moments"], single["moments"]) and np.array_equal(one["games"], single["games"])
         assert np.array_equal(one["values"], single["values"])
 
 
-def test_the_same_variant_twice_with_other_weights_and_all_four_variants(emu):
+def test_the_same_variant_twice_with_other_weights_and_all_four_variants():
     table = [(3, params_of(3, 1)), (2, params_of(2, 2)), (1, params_of(1, 3)), (0, params_of(0, 4)), (2, params_of(2, 5)), (0, params_of(0, 6)),
              (3, params_of(3, 7)), (1, params_of(1, 8))]                                 # EMLOCO_EVAL_MAX_NETS networks
-    got = play(emu, table, multi=True)
+    got = play(table, multi=True)
     for k, n in enumerate(table):
-        single = play(emu, [n], multi=False)
+        single = play([n], multi=False)
         assert got["planes"][k].tobytes() == single["planes"][0].tobytes(), k
         assert np.array_equal(got["moments"][k], single["moments"][0])
 
@@ -189,18 +170,12 @@ def test_the_staged_inputs_are_unchanged_by_the_forward(multi_run, single_runs):
 
 
 # ------------------------------------------------------------------------------------------------------------ the C ABI's refusals
-def _host_state():
-    from emloco_amd.predictor.ops import LocoValEval
-    keep = [np.zeros(4 * 72, np.float64) for _ in range(22)]
-    return LocoValEval(4, 5, 2, 0, 0.99, *[a.ctypes.data for a in keep]), keep
-
-
 def test_the_entry_points_refuse_no_network_too_many_and_a_bad_variant(capfd):
     """The argument checks come before any launch: they answer without a device."""
     from emloco_amd import _lib as L
     from emloco_amd.predictor.ops import EVAL_MAX_NETS, LocoValNet, LocoValNets
     lib = L.load()
-    st, keep = _host_state()
+    st, _keep = eval_state(4, 2, step_to_pred=5)
     w = np.zeros(8, np.float32)
     records = np.zeros(4 * 2 * 12 * (EVAL_MAX_NETS + 1), np.int32)
     ok = lambda v: LocoValNet(v, 0, *[w.ctypes.data] * 7)

@@ -14,7 +14,6 @@ half an ulp of the value.  Cap case (C = 54.8): at most 0.047 for the records, 0
 target half; walked half 6.0e-8 m), target half against the fp32 target 1.00 of half an ulp (a tie).
 """
 import ctypes as C
-import os
 import re
 import shutil
 import subprocess
@@ -23,57 +22,18 @@ import types
 import numpy as np
 import pytest
 
+import emu
 import track_cases as TC
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("emu_track") / "libemu_track.so")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-x", "c++", "-ffp-contract=off", "-DEMLOCO_EMU", "-Wno-psabi",
-                           "-I", os.path.join(ROOT, "tests", "emu"), "-o", so, os.path.join(ROOT, "tests", "emu_locoval_eval_track.cpp"),
-                           os.path.join(ROOT, "tests", "emu", "emu_runtime.cpp"), "-lpthread"], timeout=300)
-    lib = C.CDLL(so)
-    assert lib.emu_locoval_track_record_size() == 32
-    lib.emu_locoval_track_reduce.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
-    return lib
+from locoval_harness import _ptr, eval_state, track_state
 
 
-def _ptr(a):
-    return C.c_void_p(a.ctypes.data) if a is not None else None
-
-
-def _eval_state(E, G):
-    """An EmlocoLocoValEval over host arrays, as tests/test_locoval_eval_cpu.py builds it."""
-    from emloco_amd.predictor.ops import LocoValEval
-    b = dict(coef=np.ones(E), c_disc=np.zeros(E), tp_disc=np.zeros(E), **{k: np.zeros(E, np.float32) for k in
-             ("cr", "c_loc", "c_pow", "tp_cr", "tp_loc", "tp_pow", "row_mask")}, steps=np.zeros(E, np.int32), games=np.zeros(E, np.int32),
-             done=np.zeros(E, np.uint8), terminated=np.zeros(E, np.uint8), inverted=np.zeros(E, np.uint8), n_full=np.zeros(1, np.int32))
-    io = [np.zeros(s, np.float32) for s in ((E, 15, 3), (E, 24, 3), (E, 2), (E, 13, 3), (E, 24, 3), (E, 2))]
-    st = LocoValEval(E, 144, G, 0, 0.99, *[b[k].ctypes.data for k in (
-        "coef", "c_disc", "tp_disc", "cr", "c_loc", "c_pow", "tp_cr", "tp_loc", "tp_pow", "steps", "games", "done", "terminated",
-        "inverted", "n_full")], *[a.ctypes.data for a in io], b["row_mask"].ctypes.data)
-    return st, b, io
-
-
-def _track_state(case):
-    from emloco_amd.predictor.ops import LocoValTrack
-    E = case["E"]
-    tb = dict(sum_dev=np.zeros(E), sum_sample_dev=np.zeros(E), path_len=np.zeros(E), max_dev=np.zeros(E, np.float32),
-              prev_xy=np.zeros((E, 2), np.float32), last_sample_dev=np.zeros(E, np.float32), n_samples=np.zeros(E, np.int32),
-              dev_now=np.zeros(E, np.float32))
-    t = LocoValTrack(stride=case["stride"], root_stride=TC.ROOT_STRIDE, dt=float(case["dt"]), traj_dur=float(case["traj_dur"]),
-                     **{k: v.ctypes.data for k, v in tb.items()})
-    return t, tb
-
-
-def run_emu(emu, case):
+def run_emu(case):
     """The scripted streams through step -> track -> finish; returns what `TC.check` takes."""
     from emloco_amd.learning.locoval_eval import RECORD_WORDS, TRACK_DTYPE, TRACK_WORDS
+    lib = emu.lib()
     E, G, T = case["E"], case["G"], case["T"]
-    st, b, _io = _eval_state(E, G)
-    t, tb = _track_state(case)
+    st, b = eval_state(E, G)
+    t, tb = track_state(case)
     records = np.zeros(E * G * RECORD_WORDS, np.int32)
     track = np.zeros(E * G * TRACK_WORDS, np.int32)
     samples = np.zeros((E, G, TC.TRACK_SAMPLES, 4), np.float32)
@@ -82,18 +42,18 @@ def run_emu(emu, case):
     for k in range(T):
         verts, root, prog, dones = (np.ascontiguousarray(case[n][k]) for n in ("verts", "root", "progress", "dones"))
         t.root_pos, t.traj_verts, t.progress_buf = root.ctypes.data, verts.ctypes.data, prog.ctypes.data
-        assert emu.emu_locoval_eval_step(C.byref(st), _ptr(rr), None, _ptr(dones), None, None) == 0
-        assert emu.emu_locoval_eval_track(C.byref(st), C.byref(t), _ptr(track), _ptr(samples)) == 0
-        assert emu.emu_locoval_eval_finish(C.byref(st), _ptr(value), _ptr(records)) == 0
+        assert lib.emu_locoval_eval_step(C.byref(st), _ptr(rr), None, _ptr(dones), None, None) == 0
+        assert lib.emu_locoval_eval_track(C.byref(st), C.byref(t), _ptr(track), _ptr(samples)) == 0
+        assert lib.emu_locoval_eval_finish(C.byref(st), _ptr(value), _ptr(records)) == 0
         dev_now[k] = tb["dev_now"]
     return dict(track=track.view(TRACK_DTYPE).reshape(E, G), samples=samples, games=b["games"].copy(), dev_now=dev_now,
                 steps=records.view(np.int32).reshape(E, G, RECORD_WORDS)[:, :, 9])
 
 
 @pytest.fixture(scope="module")
-def main_run(emu):
+def main_run():
     case = TC.main_case()
-    return case, TC.restate(case), run_emu(emu, case)
+    return case, TC.restate(case), run_emu(case)
 
 
 # ------------------------------------------------------------------------------------------------------------ the scripted cases
@@ -123,21 +83,21 @@ def test_emulated_tracker_equals_the_float64_restatement(main_run):
     assert got["track"]["path_len"][0, 0] == 0 and got["track"]["n_samples"][0, 0] == 0
 
 
-def test_a_game_after_the_quota_leaves_the_records_and_samples_alone(emu):
+def test_a_game_after_the_quota_leaves_the_records_and_samples_alone():
     """Env 3 plays its third and fourth game after its quota is met: cut the streams where its second game ends, and its slots hold the
     same bytes as after the whole run."""
     case = TC.main_case()
-    full = run_emu(emu, case)
+    full = run_emu(case)
     cut = dict(case, T=int(sum(case["lengths"][3][:2])))
-    part = run_emu(emu, cut)
+    part = run_emu(cut)
     assert part["games"][3] == 2 and full["games"][3] == 2
     assert part["track"][3].tobytes() == full["track"][3].tobytes() and part["samples"][3].tobytes() == full["samples"][3].tobytes()
 
 
-def test_samples_beyond_the_cap_are_dropped(emu):
+def test_samples_beyond_the_cap_are_dropped():
     case = TC.cap_case()
     want = TC.restate(case)
-    got = run_emu(emu, case)
+    got = run_emu(case)
     worst = TC.check(case, want, got["track"], got["samples"], got["games"], got["dev_now"])
     assert max(worst.values()) <= 1.0
     assert list(got["track"]["n_samples"][:, 0]) == [16, 16, 16] and case["lengths"] == [[20], [16], [17]]
@@ -152,13 +112,13 @@ def _records_of(case, got):
     return got["track"][env, game]
 
 
-def test_the_reduction_equals_track_moments_from_records(emu, main_run):
+def test_the_reduction_equals_track_moments_from_records(main_run):
     from emloco_amd.learning.locoval_eval import TRACK_MOMENT_NAMES, track_moments_from_records
     case, _, got = main_run
     mom = np.zeros(len(TRACK_MOMENT_NAMES))
     track = np.ascontiguousarray(got["track"])
     games = got["games"].astype(np.int32)
-    assert emu.emu_locoval_track_reduce(case["E"], case["G"], _ptr(track), _ptr(games), 4.0, _ptr(mom)) == 0
+    assert emu.lib().emu_locoval_track_reduce(case["E"], case["G"], _ptr(track), _ptr(games), 4.0, _ptr(mom)) == 0
     ref = track_moments_from_records(_records_of(case, got))
     assert ref[0] == 9 and ref[1] == 7 and ref[10] == got["track"]["n_samples"].sum() and ref[11] == 1
     np.testing.assert_allclose(mom, ref, rtol=1e-12, atol=0)
@@ -213,8 +173,8 @@ def test_the_entry_points_refuse_bad_arguments(capfd):
     from emloco_amd import _lib as L
     lib = L.load()
     case = dict(E=4, stride=12, dt=1 / 30, traj_dur=5.0)
-    st, _b, _io = _eval_state(4, 2)
-    t, _tb = _track_state(case)
+    st, _b = eval_state(4, 2)
+    t, _tb = track_state(case)
     buf = np.zeros(4 * 2 * 16 * 4, np.float32)
     t.root_pos = t.traj_verts = t.progress_buf = buf.ctypes.data
     call = lambda s_=st, t_=t, r=buf, s=buf: lib.emloco_locoval_eval_track(None if s_ is None else C.byref(s_), None if t_ is None else C.byref(t_),

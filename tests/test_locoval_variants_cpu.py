@@ -5,23 +5,23 @@ Here:
   * `restate`, a plain-torch statement of the network of one variant (test infrastructure; the product runs it as HIP kernels),
     reproduces the fixture;
   * the kernels of emloco_amd/csrc/locoval_variants.h, compiled for the CPU through tests/emu/hip/ and launched through the product's
-    own dispatch (tests/emu_locoval_variants.cpp), give the fixture's values, in-place pose and gradients at the tolerances of the
+    own dispatch (tests/emu/emu_predictor.cpp), give the fixture's values, in-place pose and gradients at the tolerances of the
     full network's device test (tests/test_gpu_predictor.py:90-97);
   * the sparse `row_weight` / `slot` / `count` modes, batches that do not fill a wave, the full network through the variant entry
     points (the old entry points' bits), checkpoints and host-side errors.
 """
-import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import emu
+from locoval_harness import DIMS, _ptr
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURE = os.path.join(ROOT, "tests", "golden", "locoval_variants.npz")
 VARIANTS = {"full": 3, "pose": 2, "vel": 1, "traj": 0}           # (use_pose << 1) | use_vel
-DIMS = {3: (100, 49, 24, 6174), 2: (98, 48, 24, 5953), 1: (28, 13, 6, 468), 0: (26, 12, 6, 409)}      # the issue's table
 PARAM_KEYS = ("_network_fc1_weight", "_network_fc1_bias", "_network_fc2_weight", "_network_fc2_bias", "_network_fc3_weight", "_network_fc3_bias")
 HIDDEN = (4, 8, 9, 10, 11)
 VALUE_TOL = dict(rtol=1e-5, atol=1e-6)          # value and in-place pose
@@ -82,19 +82,6 @@ def test_restatement_reproduces_the_reference(name):
 
 
 # ------------------------------------------------------------------------------------------------------------ the kernels, emulated
-@pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("emu_lv") / "libemu_locoval_variants.so")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-x", "c++", "-ffp-contract=off", "-DEMLOCO_EMU", "-Wno-psabi",
-                           "-I", os.path.join(ROOT, "tests", "emu"), "-o", so, os.path.join(ROOT, "tests", "emu_locoval_variants.cpp"),
-                           os.path.join(ROOT, "tests", "emu", "emu_runtime.cpp"), "-lpthread"], timeout=900)
-    return C.CDLL(so)
-
-
-def _ptr(a):
-    return C.c_void_p(a.ctypes.data) if a is not None else None
-
-
 def _f32(a):
     return None if a is None else np.ascontiguousarray(a, np.float32)
 
@@ -102,8 +89,8 @@ def _f32(a):
 class Run:
     """One forward (+ backward) of a variant through the emulated kernels; `old=True`: the full network's own entry points."""
 
-    def __init__(self, lib, variant, params, traj, pose, vel, row_weight=None, fill=None, pose_rot=False, old=False):
-        self.lib, self.v, self.old = lib, variant, old
+    def __init__(self, variant, params, traj, pose, vel, row_weight=None, fill=None, pose_rot=False, old=False):
+        self.lib, self.v, self.old = emu.lib(), variant, old
         n_in, h1, h2, self.n_param = DIMS[variant]
         self.B, self.ts = traj.shape[0], traj.shape[-1]
         self.params = [_f32(p) for p in params]
@@ -117,8 +104,8 @@ class Run:
         rw = _f32(row_weight)
         out = [_ptr(a) for a in (self.value, self.x, self.h1, self.h2, self.ang)]
         if self.old:
-            rc = self.lib.emu_locoval_old_fwd_rows(self.B, _ptr(self.traj), self.ts, _ptr(self.pose), _ptr(self.vel), *[_ptr(p) for p in self.params],
-                                                   *out, _ptr(rw))
+            rc = self.lib.emu_locoval_fwd(self.B, _ptr(self.traj), self.ts, _ptr(self.pose), _ptr(self.vel), *[_ptr(p) for p in self.params],
+                                          *out, _ptr(rw))
         else:
             rc = self.lib.emu_locoval_variant_fwd_rows(self.v, self.B, _ptr(self.traj), self.ts, _ptr(self.pose), _ptr(self.vel),
                                                        *[_ptr(p) for p in self.params], *out, _ptr(self.pose_rot), _ptr(rw))
@@ -131,7 +118,7 @@ class Run:
         w1, _b1, w2, _b2, w3, _b3 = self.params
         args = [self.B, _ptr(self.traj), self.ts, _ptr(self.pose), _ptr(self.vel), _ptr(w1), _ptr(w2), _ptr(w3), _ptr(self.value), _ptr(self.x),
                 _ptr(self.h1), _ptr(self.h2), _ptr(self.ang), _ptr(dv), _ptr(slot), _ptr(count), _ptr(self.dparams), _ptr(self.dtraj), _ptr(ws)]
-        rc = self.lib.emu_locoval_old_bwd_rows(*args) if self.old else self.lib.emu_locoval_variant_bwd_rows(self.v, *args)
+        rc = self.lib.emu_locoval_bwd(*args) if self.old else self.lib.emu_locoval_variant_bwd_rows(self.v, *args)
         assert rc == 0
         return self
 
@@ -148,29 +135,29 @@ def _inputs(fx, v):
     return fx["traj"], (fx["pose"] if v & 2 else None), (fx["vel"] if v & 1 else None)
 
 
-def test_variant_dims_query(emu):
+def test_variant_dims_query():
     from emloco_amd.predictor.ops import locoval_dims, locoval_variant
     for v, want in DIMS.items():
         d = np.zeros(4, np.int32)
-        assert emu.emu_locoval_variant_dims(v, _ptr(d)) == 0 and tuple(d) == want == locoval_dims(v)
-    assert emu.emu_locoval_variant_dims(4, _ptr(np.zeros(4, np.int32))) != 0
+        assert emu.lib().emu_locoval_variant_dims(v, _ptr(d)) == 0 and tuple(d) == want == locoval_dims(v)
+    assert emu.lib().emu_locoval_variant_dims(4, _ptr(np.zeros(4, np.int32))) != 0
     assert [locoval_variant(p, v) for p, v in ((1, 1), (1, 0), (0, 1), (0, 0))] == [3, 2, 1, 0]
 
 
 @pytest.mark.parametrize("name", list(VARIANTS))
-def test_kernels_match_the_reference(emu, name):
+def test_kernels_match_the_reference(name):
     fx, v = fixture(name), VARIANTS[name]
     params = [fx[k] for k in PARAM_KEYS]
     B = fx["traj"].shape[0]
     assert B % 4 != 0
     # the pose is handed over in every variant: rotated in place where it is not an input, rotated and zeroed where it is
     traj, pose, vel = _inputs(fx, v)
-    r = Run(emu, v, params, traj, fx["pose"], vel, pose_rot=not (v & 2))
+    r = Run(v, params, traj, fx["pose"], vel, pose_rot=not (v & 2))
     np.testing.assert_allclose(r.value.reshape(B, 1), fx["value"], **VALUE_TOL)
     pose_after = r.x[:, 26:98].reshape(B, 24, 3) if v & 2 else r.pose_rot
     np.testing.assert_allclose(pose_after, fx["pose_after_inplace"], **VALUE_TOL)
     if not v & 2:                                               # ... and the value does not depend on it
-        assert np.array_equal(Run(emu, v, params, traj, None, vel).value, r.value)
+        assert np.array_equal(Run(v, params, traj, None, vel).value, r.value)
     # EmLoco loss: MSE to 1, mean over the batch
     r.backward(2.0 * (r.value - 1.0) / B)
     np.testing.assert_allclose(r.dtraj, fx["grad_traj"], **GRAD_TOL)
@@ -193,7 +180,7 @@ def _random_batch(B, seed, ts=3):
 
 
 @pytest.mark.parametrize("name", list(VARIANTS))
-def test_rows_mode_touches_only_the_ranked_rows(emu, name):
+def test_rows_mode_touches_only_the_ranked_rows(name):
     fx, v = fixture(name), VARIANTS[name]
     params = [fx[k] for k in PARAM_KEYS]
     B = 37
@@ -202,14 +189,14 @@ def test_rows_mode_touches_only_the_ranked_rows(emu, name):
     weight = np.zeros(B, np.float32)
     weight[[2, 3, 17, 20, 36]] = 1.0                           # most rows left out; two in one wave, the batch's last row
     on = weight != 0
-    dense = Run(emu, v, params, traj, pose, vel)
-    rows = Run(emu, v, params, traj, pose, vel, row_weight=weight, fill=-7.5)
+    dense = Run(v, params, traj, pose, vel)
+    rows = Run(v, params, traj, pose, vel, row_weight=weight, fill=-7.5)
     for a, b in ((rows.value, dense.value), (rows.x, dense.x), (rows.h1, dense.h1), (rows.h2, dense.h2), (rows.ang, dense.ang)):
         assert np.array_equal(a[on], b[on]) and (a[~on] == -7.5).all()
     # ranks from the product's own fit-gradient kernel, as the rollout's fit takes them
     target = np.linspace(0.1, 0.9, B).astype(np.float32)
     dvalue, tail, slot = np.zeros(B, np.float32), np.zeros(2, np.float32), np.zeros(B, np.int32)
-    assert emu.emu_locoval_fit_grad_rows(B, _ptr(dense.value), _ptr(target), _ptr(weight), _ptr(dvalue), _ptr(tail), _ptr(slot)) == 0
+    assert emu.lib().emu_locoval_fit_grad(B, _ptr(dense.value), _ptr(target), _ptr(weight), _ptr(dvalue), _ptr(tail), _ptr(slot)) == 0
     assert tail[1] == on.sum() and list(slot[on]) == list(range(int(on.sum()))) and (slot[~on] == -1).all() and (dvalue[~on] == 0).all()
     sparse = dense.backward(dvalue, slot=slot, count=tail[1:].copy(), fill=-7.5)
     sp_dparams, sp_dtraj = sparse.dparams.copy(), sparse.dtraj.copy()
@@ -220,7 +207,7 @@ def test_rows_mode_touches_only_the_ranked_rows(emu, name):
 
 
 @pytest.mark.parametrize("mode", ["dense", "rows"])
-def test_full_variant_through_the_new_entry_points_gives_the_old_bits(emu, mode):
+def test_full_variant_through_the_new_entry_points_gives_the_old_bits(mode):
     fx = fixture("full")
     params = [fx[k] for k in PARAM_KEYS]
     B = 21
@@ -229,8 +216,8 @@ def test_full_variant_through_the_new_entry_points_gives_the_old_bits(emu, mode)
     if mode == "rows":
         weight = np.zeros(B, np.float32)
         weight[[0, 5, 6, 20]] = 1.0
-    new = Run(emu, 3, params, traj, pose, vel, row_weight=weight, fill=2.5)
-    old = Run(emu, 3, params, traj, pose, vel, row_weight=weight, fill=2.5, old=True)
+    new = Run(3, params, traj, pose, vel, row_weight=weight, fill=2.5)
+    old = Run(3, params, traj, pose, vel, row_weight=weight, fill=2.5, old=True)
     for k in ("value", "x", "h1", "h2", "ang"):
         assert getattr(new, k).tobytes() == getattr(old, k).tobytes(), k
     dvalue = np.linspace(-1, 1, B).astype(np.float32)
@@ -246,7 +233,7 @@ def test_full_variant_through_the_new_entry_points_gives_the_old_bits(emu, mode)
 
 
 @pytest.mark.parametrize("name", ["vel", "traj", "pose"])
-def test_batches_that_do_not_fill_a_wave(emu, name):
+def test_batches_that_do_not_fill_a_wave(name):
     """Four samples share a wave and sixteen a workgroup in the narrow kernels: a sample's results do not depend on its neighbours, on
     the batch size or on where the batch ends; checked against the float64 restatement as well."""
     fx, v = fixture(name), VARIANTS[name]
@@ -257,7 +244,7 @@ def test_batches_that_do_not_fill_a_wave(emu, name):
     dvalue = np.linspace(-1, 1, Bmax).astype(np.float32)
     sel = lambda a, n: None if a is None else a[:n]
     pose_in, vel_in = (pose if v & 2 else None), (vel if v & 1 else None)
-    big = Run(emu, v, params, traj, pose_in, vel_in).backward(dvalue)
+    big = Run(v, params, traj, pose_in, vel_in).backward(dvalue)
     t64 = lambda a: torch.from_numpy(np.array(a)).double()
     p64 = [t64(p).requires_grad_(True) for p in params]
     tr64 = t64(traj).requires_grad_(True)
@@ -268,7 +255,7 @@ def test_batches_that_do_not_fill_a_wave(emu, name):
     for g, p in zip(big.split(), p64):
         np.testing.assert_allclose(g, p.grad.numpy(), **GRAD_TOL)
     for n in (1, 2, 3, 5, 16, 17, 18):
-        r = Run(emu, v, params, traj[:n], sel(pose_in, n), sel(vel_in, n), fill=9.0).backward(dvalue[:n], fill=9.0)
+        r = Run(v, params, traj[:n], sel(pose_in, n), sel(vel_in, n), fill=9.0).backward(dvalue[:n], fill=9.0)
         for k in ("value", "x", "h1", "h2", "ang", "dtraj"):
             assert getattr(r, k).tobytes() == getattr(big, k)[:n].tobytes(), (k, n)
         assert np.isfinite(r.dparams).all()

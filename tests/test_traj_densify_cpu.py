@@ -7,51 +7,38 @@ origin-shifted output over all cases, the MI355X the same 4.24e-6 m; bar 4 x the
 import ctypes as C
 import os
 import pickle
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 from scipy.interpolate import CubicSpline
 
+import emu
 import traj_densify_cases as TC
 from emloco_amd.env.util.traj_densify import TRAJ_PHASE, densify, densify_host
 from emloco_amd.utils.flags import Flags
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
 
 # ------------------------------------------------------------------------------------------------------------ the kernel, emulated
-@pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("emu_td") / "libemu_traj_densify.so")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-x", "c++", "-ffp-contract=off", "-DEMLOCO_EMU", "-Wno-psabi",
-                           "-I", os.path.join(ROOT, "tests", "emu"), "-o", so, os.path.join(ROOT, "tests", "emu_traj_densify.cpp"),
-                           os.path.join(ROOT, "tests", "emu", "emu_runtime.cpp"), "-lpthread"], timeout=900)
-    lib = C.CDLL(so)
-    lib.emu_traj_densify_error.restype = C.c_char_p
-    return lib
-
-
-def run_emu(lib, way, knot_t, query_t, origin=False, want_valid=True, fill=7.0):
+def run_emu(way, knot_t, query_t, origin=False, want_valid=True, fill=7.0):
     way = np.ascontiguousarray(way, np.float32)
     k, q = np.ascontiguousarray(knot_t, np.float32), np.ascontiguousarray(query_t, np.float32)
     out = np.full((way.shape[0], q.size, 3), fill, np.float32)
     valid = np.full(way.shape[0], 9, np.uint8)
     P = lambda a: C.c_void_p(a.ctypes.data)
-    rc = lib.emu_traj_densify(P(k), int(k.size), P(way), C.c_int64(way.shape[0]), P(q), int(q.size), P(out), P(valid) if want_valid else None,
-                              1 if origin else 0)
+    rc = emu.lib().emu_traj_densify(P(k), int(k.size), P(way), C.c_int64(way.shape[0]), P(q), int(q.size), P(out), P(valid) if want_valid else None,
+                                    1 if origin else 0)
     return rc, out, valid
 
 
 @pytest.mark.parametrize("origin", [True, False])
 @pytest.mark.parametrize("shape", list(TC.SHAPES))
-def test_emulated_kernel_matches_scipy(emu, shape, origin):
+def test_emulated_kernel_matches_scipy(shape, origin):
     knot_t, query_t = TC.SHAPES[shape]
     for n in (TC.N_TRAJ if shape == "shipped" else (65,)):
         for offset in (0.0, 100.0):
             way = TC.tracks(n, knot_t, seed=n + len(shape), offset=offset)
-            rc, out, valid = run_emu(emu, way, knot_t, query_t, origin)
+            rc, out, valid = run_emu(way, knot_t, query_t, origin)
             ref = TC.reference(way, knot_t, query_t, origin)
             err = np.abs(out - ref).max()
             print(f"{shape} n={n} offset={offset} origin={origin}: max |kernel - scipy| = {err:.3e} m, extent {np.abs(ref).max():.1f} m")
@@ -59,10 +46,10 @@ def test_emulated_kernel_matches_scipy(emu, shape, origin):
             assert err <= TC.bar(ref, origin), (shape, n, offset, err)
 
 
-def test_emulated_kernel_extrapolates_the_shipped_tail(emu):
+def test_emulated_kernel_extrapolates_the_shipped_tail():
     """vertices 85..100 of the 101 lie behind the last waypoint (phase 84.87): the last piece, as scipy extrapolates"""
     way = TC.tracks(64, TRAJ_PHASE, seed=3)
-    _, out, _ = run_emu(emu, way, TRAJ_PHASE, TC.QUERY_101, origin=True)
+    _, out, _ = run_emu(way, TRAJ_PHASE, TC.QUERY_101, origin=True)
     ref = TC.reference(way, TRAJ_PHASE, TC.QUERY_101, True)
     assert TRAJ_PHASE[-1] < 85 and np.abs(out[:, 85:] - ref[:, 85:]).max() <= TC.BAR_M
     # ... and the spline passes through its waypoints
@@ -73,27 +60,27 @@ def test_emulated_kernel_extrapolates_the_shipped_tail(emu):
     assert np.abs(out[:, k] - shifted).max() <= 0.5 * slope + TC.BAR_M
 
 
-def test_emulated_kernel_flags_non_finite_tracks(emu):
+def test_emulated_kernel_flags_non_finite_tracks():
     way = TC.tracks(130, TRAJ_PHASE, seed=9, offset=100.0)
     clean = way.copy()
     way[0, 0, 0], way[64, 6, 2], way[129, 12, 1] = np.nan, np.inf, np.nan          # first, a middle and the last waypoint
-    rc, out, valid = run_emu(emu, way, TRAJ_PHASE, TC.QUERY_101)
-    _, out_clean, _ = run_emu(emu, clean, TRAJ_PHASE, TC.QUERY_101)
+    rc, out, valid = run_emu(way, TRAJ_PHASE, TC.QUERY_101)
+    _, out_clean, _ = run_emu(clean, TRAJ_PHASE, TC.QUERY_101)
     bad = np.zeros(130, bool)
     bad[[0, 64, 129]] = True
     assert rc == 0 and (valid == ~bad).all()
     assert (out[bad] == 0).all() and np.array_equal(out[~bad], out_clean[~bad])      # the neighbouring rows are untouched
-    rc, out2, untouched = run_emu(emu, way, TRAJ_PHASE, TC.QUERY_101, want_valid=False)     # valid = NULL
+    rc, out2, untouched = run_emu(way, TRAJ_PHASE, TC.QUERY_101, want_valid=False)     # valid = NULL
     assert rc == 0 and np.array_equal(out2, out) and (untouched == 9).all()
 
 
-def test_emulated_entry_refuses_bad_arguments(emu):
+def test_emulated_entry_refuses_bad_arguments():
     even = np.arange(17.0)
     for knots, query, word in ((even[:3], TC.QUERY_101, "n_knots"), (even, TC.QUERY_101, "n_knots"), (even[:13], np.zeros(0), "n_query"),
                                (even[:13], np.arange(129.0), "n_query"), (np.array([0, 1, 2, 2, 3.0]), TC.QUERY_101, "increasing"),
                                (np.array([0, 1, np.nan, 3, 4.0]), TC.QUERY_101, "finite")):
-        rc, out, _ = run_emu(emu, np.ones((2, len(knots), 3)), knots, query)
-        assert rc == -1 and word in emu.emu_traj_densify_error().decode(), (word, emu.emu_traj_densify_error())
+        rc, out, _ = run_emu(np.ones((2, len(knots), 3)), knots, query)
+        assert rc == -1 and word in emu.lib().emu_traj_densify_error().decode(), (word, emu.lib().emu_traj_densify_error())
         assert (out == 7.0).all()                                     # nothing was launched
 
 

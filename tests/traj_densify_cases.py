@@ -5,7 +5,7 @@ kernel reads and the float64 knots / queries the caller gave (the kernel rounds 
 
 BAR_M, absolute, in metres, on origin-shifted output.  Measured maxima over every case below (walkers of 0..3 m/s, extent up to
 18 m, extrapolation included):
-    kernel emulated on the CPU (tests/emu_traj_densify.cpp)     MEASURED_EMU_M
+    kernel emulated on the CPU (tests/emu/emu_task.cpp)         MEASURED_EMU_M
     kernel on the MI355X                                        MEASURED_DEVICE_M
 The bar is 4 x the larger: the margin covers a different operation order in the device's division and nothing else.  (A float32
 restatement of the solve measured 3.9e-6 m at an extent of 2.9 m before the kernel existed; a bar above 2e-5 m would mean the solve
