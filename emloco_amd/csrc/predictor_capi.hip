@@ -1,10 +1,12 @@
 // predictor_capi.hip -- C ABI (include/emloco_predictor.h) over the predictor / LocoVal kernels.
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstdio>
 #include <string>
 #include <stdlib.h>
 #include <vector>
 #include "predictor_kernels.hip"
+#include "locoval_refine.h"            // the refinement loop (emloco_locoval_refine); not part of the CPU emulation's sources
 #include "../../include/emloco_predictor.h"
 
 namespace {
@@ -511,6 +513,28 @@ int emloco_locoval_variant_bwd(int variant, int B, const float *traj, int traj_s
         return pfail(-1, "emloco_locoval_variant_bwd: bad argument");
     const emloco::LocoValBwd a{B, traj, traj_stride, pose, vel, w1, w2, w3, value, x, h1, h2, angle, dvalue, workspace, dparams, dtraj, nullptr, nullptr};
     emloco::locoval_variant_bwd(KernelLaunch{(hipStream_t)stream}, variant, a);
+    PHIPCHK(hipGetLastError());
+    return 0;
+}
+
+// test-time refinement of trajectories against a LocoVal network (locoval_refine.h): the whole Adam loop in one launch
+int emloco_locoval_refine(int variant, int B, const float *traj, int traj_stride, const float *pose, const float *vel,
+                          const float *w1, const float *b1, const float *w2, const float *b2, const float *w3, const float *b3,
+                          const uint8_t *row_mask, int n_steps, float lr, float beta1, float beta2, float eps,
+                          float grad_scale, float anchor_w,
+                          float *traj_out, float *value_before, float *value_after, float *grad0, void *stream) {
+    if (!locoval_inputs_ok(variant, B, traj, traj_stride, pose, vel) || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !traj_out || !value_before ||
+        !value_after)
+        return pfail(-1, "emloco_locoval_refine: bad argument (variant 0..3, B >= 1, traj_stride >= 2, no NULL among the pointers the variant reads)");
+    if (n_steps < 0 || n_steps > 100000) return pfail(-1, "emloco_locoval_refine: n_steps outside 0 .. 100000");
+    if (!std::isfinite(lr) || !(lr > 0.0f) || !std::isfinite(eps) || !(eps > 0.0f) || !(beta1 >= 0.0f && beta1 < 1.0f) ||
+        !(beta2 >= 0.0f && beta2 < 1.0f) || !std::isfinite(grad_scale) || !std::isfinite(anchor_w))
+        return pfail(-1, "emloco_locoval_refine: lr and eps are finite and positive, the betas in [0, 1), grad_scale and anchor_w finite");
+    const int64_t n = (int64_t)B * 13 * traj_stride;
+    if (traj_out < traj + n && traj < traj_out + n) return pfail(-1, "emloco_locoval_refine: traj_out overlaps traj");
+    const emloco::LocoValRefine a{B, traj, traj_stride, pose, vel, w1, b1, w2, b2, w3, b3, row_mask, n_steps, lr, beta1, beta2, eps,
+                                  grad_scale, anchor_w * (2.0f / 12.0f), traj_out, value_before, value_after, grad0};
+    emloco::locoval_refine(KernelLaunch{(hipStream_t)stream}, variant, a);
     PHIPCHK(hipGetLastError());
     return 0;
 }

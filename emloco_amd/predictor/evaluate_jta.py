@@ -20,6 +20,15 @@ traj_generator.py:163-175): per stored (sample, mode) the last observed point an
 world coordinates, through the natural cubic spline of load_jta_traj.py:93-95 to 101 vertices (`env/util/traj_densify.py`; on the
 device when the predictions are there).  `--save_pred_modes best` (default) stores per sample the mode the run keeps -- the LocoVal
 arg-max with `--valueloss`, the min-ADE mode without -- and `all` every mode.
+
+`--refine_steps N` (with `--valueloss`) nudges every predicted path along the LocoVal value's gradient before it is scored: N Adam steps
+per (sample, mode) on the 12 predicted points (`ValuePoseNet.refine`, one launch per batch; plausibl/test_value_mlp.py:239-274 is the
+reference's loop: 750 steps, lr 1e-4).  Everything downstream -- ADE / FDE, the chi distances, the value statistics, the filter, the
+saved paths -- sees the refined paths; the summary keeps `ade_unrefined`, `fde_unrefined`, `value_mean_unrefined` of the paths as
+predicted and `refine_shift_mean` / `refine_shift_max`, the mean and the largest |change| of a refined coordinate in metres.
+`--refine_modes best` refines per sample only the mode with the highest value.  The refinement reads the pose as given
+(side-effect-free), while the scoring reproduces `reference_inplace_pose` by default: with a pose-reading network the value statistics
+are then those of another pose than the one refined against; `reference_inplace_pose=False` scores what was refined.
 """
 import math
 
@@ -281,7 +290,8 @@ class EvalAccumulator:
 
 class PredTrajCollector:
     """The predictions of an evaluation as the table `--pred_path` walks: {key: {'coord_dense': (101, 3) float64, 'sample': i, 'mode': m,
-    'ade': ..., 'locoval': ... or None}}, `coord_dense` being the key traj_generator.py:170 reads.  modes = "best": one entry per sample
+    'ade': ..., 'locoval': ... or None}} (with --refine_steps also 'locoval_unrefined' and 'refined': True), `coord_dense` being the key
+    traj_generator.py:170 reads.  modes = "best": one entry per sample
     (key i), the mode of the highest LocoVal value among the scored ones, or of the lowest ADE when no LocoVal network scores the run;
     "all": every mode (key i * M + m).  A track with a non-finite point is left out, as load_jta_traj.py:87-89 leaves such tracks out."""
 
@@ -315,6 +325,8 @@ class PredTrajCollector:
         dense, ok = dense.double().cpu().numpy().reshape(B, K, -1, 3), ok.cpu().numpy().reshape(B, K)
         ade_k = ade.gather(1, mode).cpu().numpy()
         val_k = None if value is None else value.gather(1, mode).cpu().numpy()
+        unrefined = last.get("value_unrefined")                                   # (--refine_steps: the value of the path as predicted)
+        unref_k = None if unrefined is None else unrefined.gather(1, mode).cpu().numpy()
         mode = mode.cpu().numpy()
         for b in range(B):
             for k in range(K):
@@ -324,6 +336,8 @@ class PredTrajCollector:
                 self.entries[i if self.modes == "best" else i * M + m] = {
                     "coord_dense": dense[b, k].copy(), "sample": i, "mode": m, "ade": float(ade_k[b, k]),
                     "locoval": None if val_k is None else float(val_k[b, k])}
+                if unref_k is not None:
+                    self.entries[i if self.modes == "best" else i * M + m].update(locoval_unrefined=float(unref_k[b, k]), refined=True)
 
     def save(self, path):
         import os
@@ -335,17 +349,58 @@ class PredTrajCollector:
         return path
 
 
+def refine_predictions(valuenet, in_joints, pred_joints, primary_init_pose, dataset="jta", steps=750, lr=1e-4, anchor_w=0.0, modes="all"):
+    """`pred_joints` (B, 12, M [x] 2) of `inference` with every (sample, mode) path refined against `valuenet` (ValuePoseNet.refine on the
+    LocoVal inputs `EvalAccumulator.update` builds: origin prepended, pose with the dataset's axis negated, velocity from the last two
+    observed frames), in the same shape, and (sum, count, max) of |change| over the coordinates of the refined paths.  modes = "best":
+    per sample only the mode of the highest value is refined.  Paths with a non-finite input are left as they are."""
+    if modes not in ("all", "best"):
+        raise ValueError("--refine_modes is all or best")
+    dev = pred_joints.device
+    B = pred_joints.shape[0]
+    pred = pred_joints.reshape(B, 12, -1, 2).float()
+    M = pred.shape[2]
+    init_pose = primary_init_pose.to(dev).float().clone()
+    if dataset == "jta":
+        init_pose[..., 2] = -init_pose[..., 2]
+    else:
+        init_pose[..., 0] = -init_pose[..., 0]
+    init_vel = ((in_joints[:, 8, 0, :2] - in_joints[:, 7, 0, :2]) * 2.5).to(dev).float()
+    traj = torch.cat([torch.zeros(B, M, 1, 2, device=dev), pred.permute(0, 2, 1, 3)], 2).reshape(B * M, 13, 2).contiguous()
+    pose = init_pose[:, None].expand(B, M, 24, 3).reshape(B * M, 24, 3)
+    vel = init_vel[:, None].expand(B, M, 2).reshape(B * M, 2)
+    mask = None
+    if modes == "best" and M > 1:
+        v0 = valuenet.refine(traj, pose, vel, steps=0)[1].reshape(B, M)
+        mask = torch.zeros(B, M, dtype=torch.bool, device=dev)
+        mask[torch.arange(B, device=dev), torch.nan_to_num(v0, nan=-1e30).argmax(1)] = True
+        mask = mask.reshape(B * M)
+    out, _before, after = valuenet.refine(traj, pose, vel, steps=steps, lr=lr, anchor_w=anchor_w, row_mask=mask)
+    done = torch.isfinite(after)                                                  # the rows that were refined
+    shift = (out[done, 1:] - traj[done, 1:]).abs().double()
+    stats = (float(shift.sum()), int(shift.numel()), float(shift.max()) if shift.numel() else 0.0)
+    refined = out[:, 1:].reshape(B, M, 12, 2).permute(0, 2, 1, 3).reshape(pred_joints.shape).to(pred_joints.dtype)
+    return refined, stats
+
+
 def evaluate_ade_fde(model, valuenet, split, modality_selection, dataloader, bs, config, logger=None, exp_name="", return_all=False,
-                     visualize=False, limit_obs=False, dataset="jta", random_ids=None, shard=None, pred_trajs=None, **acc_kw):
+                     visualize=False, limit_obs=False, dataset="jta", random_ids=None, shard=None, pred_trajs=None,
+                     refine_steps=0, refine_lr=1e-4, refine_anchor=0.0, refine_modes="all", **acc_kw):
     """Same arguments as the reference; additionally returns the summary dict (the reference only logs it).
     Data-parallel (configs[4]): with a process group of W ranks, rank r evaluates batches r, r+W, ... (`shard=(r, W)`,
-    default from torch.distributed) and the summary is all-reduced -- no tensor data crosses ranks."""
+    default from torch.distributed) and the summary is all-reduced -- no tensor data crosses ranks.
+    refine_steps > 0 (`--refine_steps`): every prediction goes through `refine_predictions` between `inference` and the accumulator; a
+    second accumulator scores the paths as predicted for the `*_unrefined` keys.  With 0 nothing of this runs."""
     import torch.distributed as dist
+    if refine_steps > 0 and valuenet is None:
+        raise ValueError("--refine_steps needs a LocoVal network to ascend: pass --valueloss")
     if shard is None:
         shard = (dist.get_rank(), dist.get_world_size()) if dist.is_available() and dist.is_initialized() else (0, 1)
     out_F = config["TRAIN"]["output_track_size"]
     thr = 0.8 if dataset == "jrdb" else config["MODEL"]["value_threshold"]
     acc = EvalAccumulator(thr, **acc_kw)
+    acc0 = EvalAccumulator(thr, **acc_kw) if refine_steps > 0 else None           # the paths as predicted
+    shift_sum, shift_n, shift_max = 0.0, 0, 0.0
     off = 0
     for bi, batch in enumerate(dataloader):
         joints, masks, padding_mask = batch[0], batch[1], batch[2]
@@ -360,10 +415,27 @@ def evaluate_ade_fde(model, valuenet, split, modality_selection, dataloader, bs,
         B = out_joints.shape[0]
         ids = None if random_ids is None else random_ids[off:off + B]
         off += B
+        if acc0 is not None:
+            if ids is None:                                                       # one draw for both accumulators (the one `update` makes)
+                ids = torch.randint(0, pred_joints.reshape(B, 12, -1, 2).shape[2], (B,), device=pred_joints.device)
+            acc0.update(in_joints, out_joints, pred_joints, primary_init_pose, valuenet, ids, dataset)
+            pred_joints, (ds, dn, dm) = refine_predictions(valuenet, in_joints, pred_joints, primary_init_pose, dataset, refine_steps, refine_lr,
+                                                           refine_anchor, refine_modes)
+            shift_sum, shift_n, shift_max = shift_sum + ds, shift_n + dn, max(shift_max, dm)
         acc.update(in_joints, out_joints, pred_joints, primary_init_pose, valuenet, ids, dataset)
+        if acc0 is not None:
+            acc.last["value_unrefined"] = acc0.last["value"]
         if pred_trajs is not None:                                                # (a PredTrajCollector)
             pred_trajs.add(off - B, joints[:, 0, config["TRAIN"]["input_track_size"] - 1, 0, :3], acc.last)
     res = acc.summary()
+    if acc0 is not None:
+        res0 = acc0.summary()
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            shift_sum, shift_n = _dist_reduce("sum", np.array([shift_sum, float(shift_n)]))
+            shift_max = float(_dist_reduce("max", np.array([shift_max]))[0])
+        res.update({"refine_steps": int(refine_steps), "ade_unrefined": res0["ade"], "fde_unrefined": res0["fde"],
+                    "value_mean_unrefined": res0.get("value_mean", float("nan")),
+                    "refine_shift_mean": float(shift_sum) / max(float(shift_n), 1.0), "refine_shift_max": float(shift_max)})
     if logger is not None:
         logger.info(f"Total samples: {res['samples']}")
         for label, key in (("ADE", "ade"), ("FDE", "fde"), ("Min ADE", "min_ade"), ("Min FDE", "min_fde"), ("Worst ADE", "worst_ade"),
@@ -380,6 +452,10 @@ def evaluate_ade_fde(model, valuenet, split, modality_selection, dataloader, bs,
                                ("Min ADE with Value sampling", "minade_value"), ("Min FDE with Value sampling", "minfde_value"),
                                ("ADE of rejected samples", "ade_rejected"), ("FDE of rejected samples", "fde_rejected")):
                 logger.info(f"{label}: {res[key]:.5f}")
+        if acc0 is not None:
+            logger.info(f"Refined with {res['refine_steps']} steps: ADE {res['ade_unrefined']:.5f} -> {res['ade']:.5f}, FDE {res['fde_unrefined']:.5f} -> "
+                        f"{res['fde']:.5f}, value {res['value_mean_unrefined']:.5f} -> {res.get('value_mean', float('nan')):.5f}, "
+                        f"shift mean {res['refine_shift_mean']:.5f} m, max {res['refine_shift_max']:.5f} m")
     return res
 
 
@@ -408,6 +484,10 @@ def build_arg_parser():
     p.add_argument("--dataset", type=str, default="jta", choices=["jta", "jrdb"], help="evaluate_jta.py | evaluate_jrdb.py")
     p.add_argument("--save_pred_trajs", type=str, default="", help="write the predictions as a --pred_path table (101-vertex paths) to this pickle")
     p.add_argument("--save_pred_modes", type=str, default="best", choices=["best", "all"], help="the mode the run keeps per sample | every mode")
+    p.add_argument("--refine_steps", type=int, default=0, help="Adam steps that raise the LocoVal value of every predicted path before it is scored (0: off; needs --valueloss)")
+    p.add_argument("--refine_lr", type=float, default=1e-4, help="learning rate of the refinement (metres per step, about)")
+    p.add_argument("--refine_anchor", type=float, default=0.0, help="weight of the mean squared distance to the predicted path in the refinement's objective")
+    p.add_argument("--refine_modes", type=str, default="all", choices=["all", "best"], help="refine every mode | per sample the mode of the highest value")
     return p
 
 
@@ -433,6 +513,8 @@ def run(args, logger=None):
     from torch.utils.data import DataLoader
     from ..learning.value_pose_net import ValuePoseNet
     from .train_jta import load_checkpoint, load_config
+    if getattr(args, "refine_steps", 0) > 0 and not args.valueloss:
+        raise SystemExit("evaluate_jta --refine_steps: the refinement ascends the LocoVal value, which --valueloss loads; pass --valueloss")
     dev = f"cuda:{torch.cuda.current_device()}"
     ckpt_name = find_checkpoint(args)
     if logger is not None:
@@ -470,7 +552,9 @@ def run(args, logger=None):
             logger.info(f"Evaluating with {9 if obs_i == 0 else obs_i} frames")
         collector = PredTrajCollector(args.save_pred_modes) if getattr(args, "save_pred_trajs", "") else None
         out[obs_i] = evaluate_ade_fde(model, valuenet, args.split, args.modality, loader, bs, config, logger, args.exp_name, return_all=True,
-                                      limit_obs=obs_i, dataset=args.dataset, pred_trajs=collector)
+                                      limit_obs=obs_i, dataset=args.dataset, pred_trajs=collector, refine_steps=getattr(args, "refine_steps", 0),
+                                      refine_lr=getattr(args, "refine_lr", 1e-4), refine_anchor=getattr(args, "refine_anchor", 0.0),
+                                      refine_modes=getattr(args, "refine_modes", "all"))
         if collector is not None:                                                 # (--all_frames: the last pass, all 9 frames, stays)
             import torch.distributed as dist
             rank = dist.get_rank() if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1 else None

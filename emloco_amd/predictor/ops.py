@@ -753,6 +753,32 @@ class LocoValVariantFn(torch.autograd.Function):
         return (None, dtraj, None, None, g[0].view(n_h1, n_in), g[1], g[2].view(n_h2, n_h1), g[3], g[4].view(1, n_h2), g[5], None)
 
 
+def locoval_refine(variant, traj, pose, vel, params, steps, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, anchor_w=0.0, row_mask=None,
+                   want_grad0=False):
+    """`steps` Adam steps on the xy of waypoints 1..12 of every row of traj (B, 13, >= 2) that raise the LocoVal value of `variant`
+    (emloco_locoval_refine: the whole loop of plausibl/test_value_mlp.py:239-274 in one launch; objective per row
+    grad_scale * exp(-V) + anchor_w / 12 * sum |p - p0|^2).  `params` = (w1, b1, w2, b2, w3, b3); `pose` / `vel` may be None where the
+    variant does not read them; `row_mask` (B,) bool: rows with False come back as they went in.  Returns (traj_out, value_before,
+    value_after[, grad0 (B, 12, 2) = the gradient of the first step]); the values are those of the forward kernels on traj and traj_out,
+    NaN in the rows the mask leaves out.  Not an autograd function: nothing flows back to `traj` or the parameters."""
+    locoval_dims(variant)
+    if want_grad0 and steps < 1:
+        raise ValueError("locoval_refine: grad0 is the gradient of the first step; steps >= 1")
+    B, ts, dev = traj.shape[0], traj.shape[-1], traj.device
+    traj_c = traj.detach().contiguous().float()
+    pose_c = pose.detach().contiguous().float() if pose is not None and variant & 2 else None
+    vel_c = vel.detach().contiguous().float() if vel is not None and variant & 1 else None
+    mask_c = row_mask.detach().to(dev).reshape(B).to(torch.uint8).contiguous() if row_mask is not None else None
+    ps = [t.detach().contiguous().float() for t in params]
+    traj_out = torch.empty_like(traj_c)
+    before, after = torch.full((B,), float("nan"), device=dev), torch.full((B,), float("nan"), device=dev)
+    grad0 = torch.zeros(B, 12, 2, device=dev) if want_grad0 else None
+    _chk(_lib().emloco_locoval_refine(variant, B, _p(traj_c), ts, _p(pose_c), _p(vel_c), *[_p(t) for t in ps], _p(mask_c), int(steps), float(lr),
+                                      float(betas[0]), float(betas[1]), float(eps), float(grad_scale), float(anchor_w), _p(traj_out), _p(before),
+                                      _p(after), _p(grad0), _st(traj)), "emloco_locoval_refine")
+    return (traj_out, before, after, grad0) if want_grad0 else (traj_out, before, after)
+
+
 def gemm_timing(enable=None):
     lib = _lib()
     if enable is not None:

@@ -302,6 +302,28 @@ int emloco_locoval_variant_bwd(int variant, int B, const float *traj, int traj_s
 /* bytes of workspace emloco_locoval_variant_bwd / _bwd_rows need for batch B (-1: bad argument) */
 int64_t emloco_locoval_variant_bwd_workspace(int variant, int B);
 
+/* Test-time refinement of trajectories against a LocoVal network: the loop of plausibl/test_value_mlp.py:239-274 (class Opt: the
+ * trajectories as a leaf tensor, Adam on exp(-V)) with V the network of value_pose_net.py:73-159, all n_steps in ONE launch (the
+ * weights in LDS, a row's coordinates, Adam moments and activations on chip; emloco_amd/csrc/locoval_refine.h).  Row i: p = the xy of
+ * waypoints 1..12 of traj [B][13][traj_stride], p0 their input values; waypoint 0 and the columns from 2 on are copied to traj_out
+ * unchanged; pose [B][24][3] and vel [B][2] are constants, read only (NULL where the variant does not read them).  For t = 1 .. n_steps
+ *     L = grad_scale * exp(-V(p)) + anchor_w / 12 * sum_k |p_k - p0_k|^2
+ *     g = dL/dp  through the MLP, the rotation and the yaw angle (what emloco_locoval_variant_bwd gives for dvalue = -grad_scale exp(-V))
+ *     m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g g;  p -= lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+ * which is torch.optim.Adam without amsgrad or weight decay.  The reference's objective exp(-V).mean() over N rows is grad_scale = 1 / N;
+ * with grad_scale = 1 a row's result does not depend on the rows that share its launch (Adam cancels the scale except through eps).
+ * Out: traj_out [B][13][traj_stride] (must not overlap traj), value_before [B] and value_after [B] = the bits emloco_locoval_variant_fwd
+ * gives on traj and on traj_out, grad0 [B][12][2] (optional, NULL: not wanted) = g at t = 1.  row_mask [B] (optional, NULL: every row):
+ * a row with mask 0 gets traj_out = traj and its value entries are left untouched.  n_steps = 0 copies the trajectory and writes the two
+ * values, equal.  -1 without a launch: a NULL required pointer (pose / vel where the variant reads it), variant outside 0..3, B < 1,
+ * traj_stride < 2, n_steps outside 0 .. 100000, lr or eps not finite and positive, a beta outside [0, 1), grad_scale or anchor_w not
+ * finite, traj_out overlapping traj. */
+int emloco_locoval_refine(int variant, int B, const float *traj, int traj_stride, const float *pose, const float *vel,
+                          const float *w1, const float *b1, const float *w2, const float *b2, const float *w3, const float *b3,
+                          const uint8_t *row_mask, int n_steps, float lr, float beta1, float beta2, float eps,
+                          float grad_scale, float anchor_w,
+                          float *traj_out, float *value_before, float *value_after, float *grad0, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * LocoVal training step around the MLP: the per-step body of AMPValueAgent.play_steps after env.step
  * (pacer/pacer/learning/amp_continuous_value.py:63-145; optimiser / normalisation common_agent.py:89-97,154-155), as three small
