@@ -56,6 +56,17 @@ __device__ __forceinline__ int tri_index(int a, int b) {
     return ((hi * (hi + 1)) >> 1) + lo;
 }
 
+// the two layouts of the contact matrix in LDS (sim_step_env, phases 6b / 6c)
+struct ContactMatrixSquare { static constexpr bool square = true; };
+struct ContactMatrixPacked { static constexpr bool square = false; };
+// the three entries (ls, r .. r + 2) of one contact: square layout -- three consecutive words at the lane's running row offset `ao`;
+// packed lower triangle -- tri_index per entry
+template <bool SQ>
+__device__ __forceinline__ void contact_entries3(const float *sh_A, int ao, int ls, int r, float &x0, float &x1, float &x2) {
+    if (SQ) { x0 = sh_A[ao]; x1 = sh_A[ao + 1]; x2 = sh_A[ao + 2]; }
+    else { x0 = sh_A[tri_index(ls, r)]; x1 = sh_A[tri_index(ls, r + 1)]; x2 = sh_A[tri_index(ls, r + 2)]; }
+}
+
 // Hand-over of a split launch (emloco_sim_set_split): 16-byte granules written with `sc1` (write-through) stores and read
 // with `sc1` loads -- coherent across the XCDs' L2s and the CUs' L1s access by access (MI355X_MICROARCH.md, inter-workgroup
 // visibility: "sc1 stores and loads both sides") -- and a flag word (relaxed agent-scope atomic) that goes out once the
@@ -319,6 +330,14 @@ __device__ __forceinline__ void sim_step_env(const EmlocoSimParams &prm, const E
     static_assert(O_R % 4 == 0 && O_W % 4 == 0 && O_IA % 4 == 0 && O_PA % 4 == 0 && O_PQ % 4 == 0, "rows must be 16-byte aligned");
     static_assert(O_V - O_G >= EMLOCO_SC_MAXSEG * 8 + EMLOCO_SC_MAXHITS * 8 + 256, "limb-limb scratch does not fit its overlay");
     static_assert(LDS_WORDS * 4 <= 13312, "LDS per env above 160 KiB / 12 in 512-byte granules (three waves per SIMD, 12 envs per CU)");
+    // The contact matrix has two layouts, chosen per env-substep on the contact count (wave-uniform): up to SQ_MAXC contacts
+    // the full square, entry (s, r) at s * SQ_LD + r, both triangles stored -- a lane walks its own row with one running
+    // address; above, the packed lower triangle (a 60 x 60 square does not fit).  The odd stride keeps the 64 lanes of a column
+    // walk on different banks.  The sweeps read one contact past the last one (never used): three words beyond a row.
+    enum { SQ_MAXC = 14, SQ_ROWS = 3 * SQ_MAXC, SQ_LD = SQ_ROWS + 1 };
+    static_assert(SQ_ROWS * SQ_LD <= LDS_WORDS - O_G && (SQ_ROWS - 1) * SQ_LD + SQ_ROWS + 3 <= LDS_WORDS - O_G,
+                  "the square contact matrix (and the read one contact ahead of its last row) does not fit the matrix region");
+    static_assert(SQ_ROWS > 32 && SQ_ROWS <= 64 && SQ_MAXC <= MAXC, "square layout: at most two tile rows of the Gram build");
     __shared__ __attribute__((aligned(16))) float lds[LDS_WORDS];
     float *sh_root = lds + O_ROOT;                            // p0[3] q0[4] V0[6]
     float *sh_V0 = lds + O_V0;                                // lane 0's hand-over between phases: free root twist [0..5], impulse change [6..11]
@@ -343,7 +362,7 @@ __device__ __forceinline__ void sim_step_env(const EmlocoSimParams &prm, const E
     float (*sh_Aacc)[8] = (float (*)[8])(lds + O_AACC);
     float (*sh_fext)[8] = (float (*)[8])(lds + O_FEXT);      // limb-limb penalty wrench per body (self-collision), about O
     float (*sh_pq)[8] = (float (*)[8])(lds + O_PQ);          // world position [0..2] | world rotation quaternion [4..7]
-    float *sh_A = lds + O_G;                                  // contact matrix, lower triangle: (r, s<=r) at r(r+1)/2 + s
+    float *sh_A = lds + O_G;                                  // contact matrix: square (s, r) at s * SQ_LD + r up to SQ_MAXC contacts, else lower triangle: (r, s<=r) at r(r+1)/2 + s
     constexpr bool hf_on = HF != 0;          // compile time: the plane instantiation carries none of the height-field code
 
     // ---------------------------------------------------------------- per-lane constants
@@ -1268,6 +1287,27 @@ __device__ __forceinline__ void sim_step_env(const EmlocoSimParams &prm, const E
                 }
             }
 #undef GRAM_STEP
+            if (nc <= SQ_MAXC) {
+                // Square layout.  Tile (0,0) holds every (row, column) of the first 32 rows; its upper half is bit-equal to the mirror
+                // image (the products commute, the k order is the same), so the tile goes out whole: one address per lane plus
+                // compile-time row offsets, rows and columns beyond nr included (zeros, inside the matrix region).  Tile (1,0) goes
+                // to (32 + row, column) and, mirrored, to (column, 32 + row).
+                if (nc > 0) {
+                    float *t00 = sh_A + 4 * h * SQ_LD + j31;
+                    for (int r = 0; r < 16; ++r) t00[((r & 3) + 8 * (r >> 2)) * SQ_LD] = acc00[r];
+                    if (big) {
+                        float *t10 = sh_A + (32 + 4 * h) * SQ_LD + j31, *t01 = sh_A + j31 * SQ_LD + 32 + 4 * h;
+                        for (int r = 0; r < 16; ++r) {
+                            const int ro = (r & 3) + 8 * (r >> 2);
+                            if (32 + 4 * h + ro < nr) {
+                                t10[ro * SQ_LD] = acc10[r];
+                                t01[ro] = acc10[r];
+                                if (32 + j31 < nr) t10[ro * SQ_LD + 32] = acc11[r];
+                            }
+                        }
+                    }
+                }
+            } else
             for (int r = 0; r < 16; ++r) {
                 const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
                 if (row < nr && j31 <= row) sh_A[row * (row + 1) / 2 + j31] = acc00[r];
@@ -1285,85 +1325,106 @@ __device__ __forceinline__ void sim_step_env(const EmlocoSimParams &prm, const E
         // Lane s owns row s: its multiplier `lam`, the running residual w_s = rhs_s + sum_r A_sr lam_r and 1/(A_ss (1+cfm)).
         // A row update happens in lane rr alone; its change is broadcast with one v_readlane and every lane folds it into
         // w with one fma through column rr of the symmetric matrix -- no wave reduction in the loop.
-        // The matrix stays in LDS (packed lower triangle): lane s reads entry (s, rr) of its row for the row being updated, one
-        // contact ahead of the sweep.  (Holding each lane's row in 60 registers cost a wave per SIMD in occupancy.)
-        const int ls = lane < nr ? lane : 0;                      // idle lanes shadow lane 0 (their w is never used)
-        const int tri_s = ls * (ls + 1) / 2;
-        const float ainv = (lane < nr) ? 1.0f / (sh_A[tri_s + ls] * (1.0f + prm.cfm)) : 0.0f;
-        // entry (ls, rr) of the symmetric matrix in the packed lower triangle; the sweeps read the three entries of the next
-        // contact while the current one is being resolved (the reads do not depend on the multipliers)
-// (tri_index is branch-free min / max / multiply arithmetic per lane.  Two cheaper-looking forms -- a compare-and-select
-// between the two triangle forms, and the larger index's offset taken from the scalar unit with a per-lane select -- have
-// fewer vector instructions and both measured slower: first sweep 340 -> 430 / 392 ticks)
-#define A_OF(rr) sh_A[tri_index(ls, (rr))]
-        float w = rhs;
-        {                                                          // warm start (matrix entries read one contact ahead)
-            float n0 = 0.0f, n1a = 0.0f, n2a = 0.0f;
-            if (nc > 0) { n0 = A_OF(0); n1a = A_OF(1); n2a = A_OF(2); }
-            for (int c = 0; c < nc; ++c) {
-                const int r0 = 3 * c;
-                const float a0 = n0, a1 = n1a, a2 = n2a;
-                if (c + 1 < nc) { n0 = A_OF(r0 + 3); n1a = A_OF(r0 + 4); n2a = A_OF(r0 + 5); }
-                const float l0 = lane_bcast(lam, r0), l1 = lane_bcast(lam, r0 + 1), l2 = lane_bcast(lam, r0 + 2);
-                const float u0 = fmaf(a0, l0, w);
-                w = (l0 != 0.0f) ? u0 : w;
-                const float u1 = fmaf(a1, l1, w);
-                w = (l1 != 0.0f) ? u1 : w;
-                const float u2 = fmaf(a2, l2, w);
-                w = (l2 != 0.0f) ? u2 : w;
-            }
-        }
-        PSTAMP(11);
-        // The sweeps resolve a contact inside ONE lane, the lane of its normal row (the leader): it holds the three
-        // multipliers of the contact, the reciprocal diagonals and the sub-diagonal of its 3 x 3 block, fetches the residuals
-        // of its two tangent rows (two v_readlane of values that are ready since the previous contact) and walks normal ->
-        // tangent 1 -> tangent 2 -> friction cone on its own, forming the intermediate residuals exactly as the rows'
-        // own lanes will; the three changes (and the two of a cone projection) are then broadcast and every lane folds them
-        // into its w in the same order.  Same operations per value as the row-by-row sweep (the oracle's) with a third of the
-        // cross-lane round trips; branch-free on purpose (an exec-masked leader block was slower than the row-by-row sweep).
-        // A wave issues in order at ~4 cycles per instruction here, so the sweep costs what its instruction count costs:
-        // first sweep of a 3-foot-contact env 380 -> 356 ticks of 10 ns.
-        const int lr0 = ls - (lane < nr ? myd : 0);               // first row of this lane's contact
-        float gl0 = __shfl(lam, lr0), gl1 = __shfl(lam, lr0 + 1), gl2 = __shfl(lam, lr0 + 2);
-        const float gi1 = __shfl(ainv, lr0 + 1), gi2 = __shfl(ainv, lr0 + 2);
-        const float gA10 = sh_A[tri_index(lr0 + 1, lr0)], gA20 = sh_A[tri_index(lr0 + 2, lr0)], gA21 = sh_A[tri_index(lr0 + 2, lr0 + 1)];
-        const bool leader = lane < nr && myd == 0;
-        for (int it = 0; it < prm.n_iter; ++it) {
-            float n0 = 0.0f, n1a = 0.0f, n2a = 0.0f;
-            if (nc > 0) { n0 = A_OF(0); n1a = A_OF(1); n2a = A_OF(2); }
-            for (int c = 0; c < nc; ++c) {
-                const int r0 = 3 * c;
-                const float a0 = n0, a1 = n1a, a2 = n2a;
-                if (c + 1 < nc) { n0 = A_OF(r0 + 3); n1a = A_OF(r0 + 4); n2a = A_OF(r0 + 5); }
-                const float w1s = lane_bcast(w, r0 + 1), w2s = lane_bcast(w, r0 + 2);
-                // branch-free: every lane runs the leader's chain on its own contact's values, only lane r0's results are read
-                float nl0 = fmaf(-w, ainv, gl0);
-                if (nl0 < 0.0f) nl0 = 0.0f;
-                const float d0 = nl0 - gl0;
-                const float w1 = fmaf(gA10, d0, w1s);
-                const float nl1 = fmaf(-w1, gi1, gl1);
-                const float d1 = nl1 - gl1;
-                const float w2 = fmaf(gA21, d1, fmaf(gA20, d0, w2s));
-                const float nl2 = fmaf(-w2, gi2, gl2);
-                const float d2 = nl2 - gl2;
-                const bool me = lane == r0;
-                gl0 = me ? nl0 : gl0; gl1 = me ? nl1 : gl1; gl2 = me ? nl2 : gl2;
-                const float lim = prm.mu * nl0;
-                const float m2 = fmaf(nl1, nl1, nl2 * nl2);
-                w = fmaf(a0, lane_bcast(d0, r0), w);
-                w = fmaf(a1, lane_bcast(d1, r0), w);
-                w = fmaf(a2, lane_bcast(d2, r0), w);
-                if (__builtin_expect(__ballot(me && m2 > lim * lim) != 0ull, 0)) {   // wave-uniform: outside the friction cone
-                    const float sc = lim / sqrtf(m2);
-                    const float n1 = nl1 * sc, n2 = nl2 * sc;
-                    gl1 = me ? n1 : gl1; gl2 = me ? n2 : gl2;
-                    w = fmaf(a1, lane_bcast(n1 - nl1, r0), w);
-                    w = fmaf(a2, lane_bcast(n2 - nl2, r0), w);
+        // The matrix stays in LDS: lane s reads entry (s, rr) of its row for the row being updated, one contact ahead of the
+        // sweep.  (Holding each lane's row in 60 registers cost a wave per SIMD in occupancy.)
+        // Two instantiations of the same text, chosen wave-uniformly on the contact count (the layout 6b wrote):
+        //   square (nc <= SQ_MAXC)  the lane's row is contiguous: one running address, 12 bytes on per contact, the three entries
+        //                           of a contact at immediate offsets; the read ahead of the last contact runs three words past
+        //                           the row (inside the matrix region, never used), so the loop carries no guard -- with fewer
+        //                           than 11 contacts those words may be ones 6b did not write in this substep (stale LDS,
+        //                           uninitialised memory on the CPU emulator): they are loaded and dropped, never computed with;
+        //   packed lower triangle   entry (ls, rr) through tri_index, per entry.
+        // The sweeps read the three entries of the next contact while the current one is being resolved (the reads do not
+        // depend on the multipliers).  Leader chain, broadcasts, cone projection and the order of the fmas into w are one text.
+        float gl0 = 0.0f, gl1 = 0.0f, gl2 = 0.0f;
+        bool leader = false;
+        auto pgs = [&](auto layout) {
+            constexpr bool SQ = decltype(layout)::square;
+            const int ls = lane < nr ? lane : 0;                      // idle lanes shadow lane 0 (their w is never used)
+            const int arow = SQ ? ls * SQ_LD : 0;                     // square layout: word offset of this lane's row
+            const float ainv = (lane < nr) ? 1.0f / (sh_A[SQ ? arow + ls : ls * (ls + 1) / 2 + ls] * (1.0f + prm.cfm)) : 0.0f;
+            // (tri_index is branch-free min / max / multiply arithmetic per lane.  Two cheaper-looking forms -- a compare-and-select
+            // between the two triangle forms, and the larger index's offset taken from the scalar unit with a per-lane select --
+            // have fewer vector instructions and both measured slower: first sweep 340 -> 430 / 392 ticks)
+            float w = rhs;
+            {                                                          // warm start (matrix entries read one contact ahead)
+                float n0 = 0.0f, n1a = 0.0f, n2a = 0.0f;
+                int ao = arow;                                         // square layout: running offset, 3 words on per contact
+                if (nc > 0) contact_entries3<SQ>(sh_A, ao, ls, 0, n0, n1a, n2a);
+                for (int c = 0; c < nc; ++c) {
+                    const int r0 = 3 * c;
+                    const float a0 = n0, a1 = n1a, a2 = n2a;
+                    if (SQ || c + 1 < nc) {
+                        if (SQ) ao += 3;
+                        contact_entries3<SQ>(sh_A, ao, ls, r0 + 3, n0, n1a, n2a);
+                    }
+                    const float l0 = lane_bcast(lam, r0), l1 = lane_bcast(lam, r0 + 1), l2 = lane_bcast(lam, r0 + 2);
+                    const float u0 = fmaf(a0, l0, w);
+                    w = (l0 != 0.0f) ? u0 : w;
+                    const float u1 = fmaf(a1, l1, w);
+                    w = (l1 != 0.0f) ? u1 : w;
+                    const float u2 = fmaf(a2, l2, w);
+                    w = (l2 != 0.0f) ? u2 : w;
                 }
             }
-            if (it == 0) PSTAMP(12);
-        }
-#undef A_OF
+            PSTAMP(11);
+            // The sweeps resolve a contact inside ONE lane, the lane of its normal row (the leader): it holds the three
+            // multipliers of the contact, the reciprocal diagonals and the sub-diagonal of its 3 x 3 block, fetches the residuals
+            // of its two tangent rows (two v_readlane of values that are ready since the previous contact) and walks normal ->
+            // tangent 1 -> tangent 2 -> friction cone on its own, forming the intermediate residuals exactly as the rows'
+            // own lanes will; the three changes (and the two of a cone projection) are then broadcast and every lane folds them
+            // into its w in the same order.  Same operations per value as the row-by-row sweep (the oracle's) with a third of the
+            // cross-lane round trips; branch-free on purpose (an exec-masked leader block was slower than the row-by-row sweep).
+            // A wave issues in order at ~4 cycles per instruction here, so the sweep costs what its instruction count costs:
+            // first sweep of a 3-foot-contact env 380 -> 356 ticks of 10 ns.
+            const int lr0 = ls - (lane < nr ? myd : 0);               // first row of this lane's contact
+            gl0 = __shfl(lam, lr0); gl1 = __shfl(lam, lr0 + 1); gl2 = __shfl(lam, lr0 + 2);
+            const float gi1 = __shfl(ainv, lr0 + 1), gi2 = __shfl(ainv, lr0 + 2);
+            const int ablk = lr0 * SQ_LD + lr0;                      // square layout: the contact's 3 x 3 diagonal block
+            const float gA10 = sh_A[SQ ? ablk + SQ_LD : tri_index(lr0 + 1, lr0)], gA20 = sh_A[SQ ? ablk + 2 * SQ_LD : tri_index(lr0 + 2, lr0)];
+            const float gA21 = sh_A[SQ ? ablk + 2 * SQ_LD + 1 : tri_index(lr0 + 2, lr0 + 1)];
+            leader = lane < nr && myd == 0;
+            for (int it = 0; it < prm.n_iter; ++it) {
+                float n0 = 0.0f, n1a = 0.0f, n2a = 0.0f;
+                int ao = arow;                                         // square layout: running offset, 3 words on per contact
+                if (nc > 0) contact_entries3<SQ>(sh_A, ao, ls, 0, n0, n1a, n2a);
+                for (int c = 0; c < nc; ++c) {
+                    const int r0 = 3 * c;
+                    const float a0 = n0, a1 = n1a, a2 = n2a;
+                    if (SQ || c + 1 < nc) {
+                        if (SQ) ao += 3;
+                        contact_entries3<SQ>(sh_A, ao, ls, r0 + 3, n0, n1a, n2a);
+                    }
+                    const float w1s = lane_bcast(w, r0 + 1), w2s = lane_bcast(w, r0 + 2);
+                    // branch-free: every lane runs the leader's chain on its own contact's values, only lane r0's results are read
+                    float nl0 = fmaf(-w, ainv, gl0);
+                    if (nl0 < 0.0f) nl0 = 0.0f;
+                    const float d0 = nl0 - gl0;
+                    const float w1 = fmaf(gA10, d0, w1s);
+                    const float nl1 = fmaf(-w1, gi1, gl1);
+                    const float d1 = nl1 - gl1;
+                    const float w2 = fmaf(gA21, d1, fmaf(gA20, d0, w2s));
+                    const float nl2 = fmaf(-w2, gi2, gl2);
+                    const float d2 = nl2 - gl2;
+                    const bool me = lane == r0;
+                    gl0 = me ? nl0 : gl0; gl1 = me ? nl1 : gl1; gl2 = me ? nl2 : gl2;
+                    const float lim = prm.mu * nl0;
+                    const float m2 = fmaf(nl1, nl1, nl2 * nl2);
+                    w = fmaf(a0, lane_bcast(d0, r0), w);
+                    w = fmaf(a1, lane_bcast(d1, r0), w);
+                    w = fmaf(a2, lane_bcast(d2, r0), w);
+                    if (__builtin_expect(__ballot(me && m2 > lim * lim) != 0ull, 0)) {   // wave-uniform: outside the friction cone
+                        const float sc = lim / sqrtf(m2);
+                        const float n1 = nl1 * sc, n2 = nl2 * sc;
+                        gl1 = me ? n1 : gl1; gl2 = me ? n2 : gl2;
+                        w = fmaf(a1, lane_bcast(n1 - nl1, r0), w);
+                        w = fmaf(a2, lane_bcast(n2 - nl2, r0), w);
+                    }
+                }
+                if (it == 0) PSTAMP(12);
+            }
+        };
+        if (nc <= SQ_MAXC) pgs(ContactMatrixSquare{}); else pgs(ContactMatrixPacked{});
         if (leader) { sh_lam[lane] = gl0; sh_lam[lane + 1] = gl1; sh_lam[lane + 2] = gl2; }
         else if (lane >= nr && lane < MAXR) sh_lam[lane] = 0.0f;
         __syncthreads();
