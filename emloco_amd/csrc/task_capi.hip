@@ -120,19 +120,27 @@ int emloco_task_amp_rows(int n, const float *root_pos, const float *root_rot, co
     return 0;
 }
 
-int emloco_task_reset(EmlocoSim *sim, const EmlocoResetBufs *b, const int32_t *dev_env_ids, int n, const float *dev_rnd, void *stream) {
-    if (!sim || !b || !dev_env_ids || !dev_rnd) return tfail(-1, "emloco_task_reset: null argument");
-    if (!sim->prepared) return tfail(-3, "emloco_task_reset: sim not prepared");
-    if (n < 0 || n > sim->n_env) return tfail(-1, "emloco_task_reset: bad env count");
-    if (n == 0) return 0;
+// what emloco_task_reset refuses, ahead of every launch (emloco_task_reset_seeded checks the same before it fills the random rows);
+// `who` names the entry point in the message.  0: go on, 1: nothing to do (n == 0), else the error code
+static int reset_refused(const char *who, const EmlocoSim *sim, const EmlocoResetBufs *b, const int32_t *dev_env_ids, int n, const float *dev_rnd) {
+    const auto no = [who](int code, const char *what) { return tfail(code, (std::string(who) + ": " + what).c_str()); };
+    if (!sim || !b || !dev_env_ids || !dev_rnd) return no(-1, "null argument");
+    if (!sim->prepared) return no(-3, "sim not prepared");
+    if (n < 0 || n > sim->n_env) return no(-1, "bad env count");
+    if (n == 0) return 1;
     if (!b->gts || !b->grs || !b->lrs || !b->gvs || !b->gavs || !b->dvs || !b->motion_len || !b->motion_dt || !b->motion_nframes ||
         !b->motion_start || b->n_motions < 1 || !b->heightfield || !b->betas || !b->key_bodies || !b->dof_subset || !b->traj_verts ||
         !b->inverted || !b->progress_buf || !b->reset_buf || !b->terminate_buf || !b->waypoint_traj || !b->init_pose || !b->init_vel ||
         !b->amp_obs_buf || !b->motion_ids || !b->motion_times || !b->ground_h)
-        return tfail(-1, "emloco_task_reset: missing buffers");
-    if (!(b->flags & EMLOCO_RESET_FIXED_LOCATION) && (!b->valid_x || !b->valid_y || b->n_valid < 1))
-        return tfail(-1, "emloco_task_reset: no valid locations");
-    if ((b->flags & EMLOCO_RESET_REAL_PATH) && b->n_real > 0 && !b->real_traj) return tfail(-1, "emloco_task_reset: real_path without data");
+        return no(-1, "missing buffers");
+    if (!(b->flags & EMLOCO_RESET_FIXED_LOCATION) && (!b->valid_x || !b->valid_y || b->n_valid < 1)) return no(-1, "no valid locations");
+    if ((b->flags & EMLOCO_RESET_REAL_PATH) && b->n_real > 0 && !b->real_traj) return no(-1, "real_path without data");
+    return 0;
+}
+
+int emloco_task_reset(EmlocoSim *sim, const EmlocoResetBufs *b, const int32_t *dev_env_ids, int n, const float *dev_rnd, void *stream) {
+    const int refused = reset_refused("emloco_task_reset", sim, b, dev_env_ids, n, dev_rnd);
+    if (refused) return refused == 1 ? 0 : refused;
     hipStream_t st = (hipStream_t)stream;
     const unsigned grid = (unsigned)(n < 256 ? n : 256);        // grid-stride kernels: see reset_kernels.hip
     hipLaunchKernelGGL(emloco::reset_sample_kernel, dim3(grid), dim3(64), 0, st, *b, sim->dev, dev_env_ids, n, dev_rnd);
@@ -162,14 +170,13 @@ int emloco_task_reset_amp_history(const EmlocoResetBufs *b, const int32_t *dev_e
 
 int emloco_task_reset_seeded(EmlocoSim *sim, const EmlocoResetBufs *b, const int32_t *dev_env_ids, int n, uint64_t seed,
                              float *dev_rnd_ws, void *stream) {
-    if (!dev_env_ids || !dev_rnd_ws) return tfail(-1, "emloco_task_reset_seeded: null argument");
-    if (n < 0) return tfail(-1, "emloco_task_reset_seeded: bad env count");
-    if (n == 0) return 0;
+    // everything emloco_task_reset refuses is refused here, before the random rows are written
+    const int refused = reset_refused("emloco_task_reset_seeded", sim, b, dev_env_ids, n, dev_rnd_ws);
+    if (refused) return refused == 1 ? 0 : refused;
     const unsigned grid = (unsigned)(n < 256 ? n : 256);
     hipLaunchKernelGGL(emloco::reset_fill_rnd_kernel, dim3(grid), dim3(64), 0, (hipStream_t)stream, dev_env_ids, n,
                        (unsigned)(seed & 0xffffffffu), (unsigned)(seed >> 32), dev_rnd_ws);
     THIPCHK(hipGetLastError());
-    if (!b) return tfail(-1, "emloco_task_reset_seeded: null argument");
     EmlocoResetBufs keyed = *b;                 // a fresh real-path permutation per call (reset_kernels.hip: real_pick_perm)
     keyed.real_pick = nullptr;
     keyed.real_pick_key = (uint32_t)((seed * 0xD6E8FEB86659FD93ull) >> 32);

@@ -195,7 +195,10 @@ int emloco_task_reset(struct EmlocoSim *sim, const EmlocoResetBufs *bufs, const 
  * workspace) is filled with uniforms in [0, 1) from a stateless hash of (seed, i, k) for the list entries that are present,
  * then emloco_task_reset runs on it.  Pass a fresh seed per call (e.g. base seed + call counter; the reference draws from
  * torch's global generator: humanoid_amp.py:284-379, traj_generator.py:60-237).  With a compacted done-list this avoids
- * generating n_env rows per step when a few dozen envs finish. */
+ * generating n_env rows per step when a few dozen envs finish.
+ * Whatever emloco_task_reset refuses (a NULL simulator, buffer struct, list or workspace, n < 0 or above the simulator's env count,
+ * a missing buffer) is refused here with the same code before anything is written, the workspace included -- also at n == 0, where
+ * a NULL simulator or buffer struct is an error as it is for emloco_task_reset. */
 int emloco_task_reset_seeded(struct EmlocoSim *sim, const EmlocoResetBufs *bufs, const int32_t *dev_env_ids, int n,
                              uint64_t seed, float *dev_rnd_ws, void *stream);
 

@@ -160,3 +160,63 @@ def task_pd_targets(actions, offset, scale, zero_mask):
     fn(actions.shape[0], _vp(actions), _vp(np.ascontiguousarray(offset, np.float32)),
        _vp(np.ascontiguousarray(scale, np.float32)), _vp(np.ascontiguousarray(zero_mask, np.uint8)), _vp(out))
     return out
+
+
+# ------------------------------------------------------------------ reset kernels
+RESET_SAMPLE, RESET_FK, RESET_FINISH, RESET_HISTORY = 1, 2, 4, 8
+RESET_ALL = 15
+
+
+class ResetHost:
+    """Host-memory simulator state, motion cache and reset buffers for running the reset kernels under emulation: `arr` holds the arrays a
+    reset writes (root_state, dof_state, rb_state, contact_force, warm_start, traj_verts, inverted, progress, reset, terminate,
+    waypoint_traj, init_pose, init_vel, amp, motion_ids, motion_times, ground_h), `const` what it reads (the motion cache's arrays,
+    heightfield, valid_x, valid_y, betas, real_traj), `scalars` the scalar fields of EmlocoResetBufs by name."""
+
+    def __init__(self, models, arr, const, scalars):
+        from emloco_amd import _lib as L
+        self.L, self.models, self.arr, self.scalars = L, models, arr, dict(scalars)
+        self.const = {k: np.ascontiguousarray(v) for k, v in const.items()}
+        self.key_bodies = np.asarray([7, 3, 22, 17], np.int32)
+        self.dof_subset = np.concatenate([np.arange(3 * j, 3 * j + 3) for j in range(23) if j not in (3, 7, 17, 22)]).astype(np.int32)
+
+    def bufs(self, **override):
+        b = self.L.ResetBufs()
+        for k, v in {**self.scalars, **override}.items():
+            setattr(b, k, v)
+        a, c = self.arr, self.const
+        for k in ("gts", "grs", "lrs", "gvs", "gavs", "dvs", "motion_len", "motion_dt", "motion_nframes", "motion_start", "heightfield",
+                  "valid_x", "valid_y", "betas"):
+            setattr(b, k, c[k].ctypes.data)
+        b.real_traj = c["real_traj"].ctypes.data if b.n_real > 0 else None
+        b.key_bodies, b.dof_subset = self.key_bodies.ctypes.data, self.dof_subset.ctypes.data
+        for k, f in (("traj_verts", "traj_verts"), ("inverted", "inverted"), ("progress", "progress_buf"), ("reset", "reset_buf"),
+                     ("terminate", "terminate_buf"), ("waypoint_traj", "waypoint_traj"), ("init_pose", "init_pose"), ("init_vel", "init_vel"),
+                     ("amp", "amp_obs_buf"), ("motion_ids", "motion_ids"), ("motion_times", "motion_times"), ("ground_h", "ground_h")):
+            setattr(b, f, a[k].ctypes.data)
+        return b
+
+    def _sim_args(self):
+        a = self.arr
+        self._desc = model_desc(self.models)
+        return [C.byref(self._desc)] + [_vp(a[k]) for k in ("root_state", "dof_state", "rb_state", "contact_force", "warm_start")]
+
+    def fill_rnd(self, ids, n, seed, rnd):
+        fn = lib().emu_reset_fill_rnd
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p]
+        assert fn(_vp(ids), n, seed, _vp(rnd)) == 0
+
+    def stages(self, stages, ids, n, rnd, **override):
+        """the launches of emloco_task_reset chosen by `stages` (RESET_* bits), in the launcher's order"""
+        b = self.bufs(**override)
+        fn = lib().emu_task_reset_stages
+        fn.argtypes = [C.c_int, C.c_void_p, C.c_void_p] + [C.c_void_p] * 5 + [C.c_void_p, C.c_int, C.c_void_p]
+        assert fn(stages, C.byref(b), *self._sim_args(), _vp(ids), n, _vp(rnd)) == 0
+
+    def reset_obs(self, task_host, ids, n, seed=0, rnd_ws=None, rnd=None, **override):
+        """the reset roles of reset_obs_kernel; task_host: a TaskHost whose state arrays are this object's"""
+        b, pb = self.bufs(**override), task_host.bufs()
+        pb.amp_ring = b.amp_ring
+        fn = lib().emu_task_reset_obs
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_void_p] * 5 + [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p]
+        assert fn(C.byref(pb), C.byref(b), *self._sim_args(), _vp(ids), n, seed, _vp(rnd_ws), _vp(rnd)) == 0

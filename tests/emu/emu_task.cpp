@@ -5,6 +5,8 @@
 #include "../../emloco_amd/csrc/reset_kernels.hip"
 #include "../../emloco_amd/csrc/chain_kernels.hip"
 #include "../../emloco_amd/csrc/traj_kernels.hip"
+#include "../../emloco_amd/csrc/topology.h"
+#include "../../emloco_amd/csrc/model_pack.h"
 
 extern "C" int emu_task_post_physics(const EmlocoTaskBufs *b, int mode, const int32_t *env_ids, int n) {
     const int count = env_ids ? n : b->n_env;
@@ -91,5 +93,90 @@ extern "C" int emu_traj_densify(const float *knot_t, int n_knots, const float *w
     emu::launch((unsigned)((n_traj + emloco::DENSIFY_TPB - 1) / emloco::DENSIFY_TPB), emloco::DENSIFY_THREADS,
                 [&] { emloco::traj_densify_kernel(a, way, out, valid); });
     blockIdx.x = 0;
+    return 0;
+}
+
+// ---- the reset kernels (reset_kernels.hip) and the reset roles of reset_obs_kernel, launched with the launcher's own grid rule
+// (task_capi.hip: min(n, 256) workgroups; (grid, 14) for the AMP history).  The simulator block is built as emu_sim_fk builds it:
+// emloco::pack_models, the topology block, host arrays.
+namespace {
+struct EmuSimDev {
+    EmlocoSimDev d{};
+    std::vector<int32_t> topo;
+    std::vector<float> mdl;
+    bool build(const EmlocoModelDesc *m, float *root, float *dof, float *rb, float *contact, float *lambda_ws) {
+        emloco::Topology t;
+        if (!t.build(m->parent, m->geom_type)) return false;
+        d.n_env = m->n_env; d.n_cand = t.n_cand; d.max_depth = t.max_depth;
+        topo = emloco::pack_topology(t, nullptr, 0);
+        mdl = emloco::pack_models(m->n_env, m->joint_off, m->mass, m->com, m->inertia, m->geom_a, m->geom_b, m->geom_r, m->kp, m->kd,
+                                  m->armature, m->effort, nullptr, nullptr, nullptr);
+        d.topo = topo.data(); d.model = mdl.data();
+        d.root_state = root; d.dof_state = dof; d.rb_state = rb; d.contact_force = contact; d.lambda_ws = lambda_ws;
+        return true;
+    }
+};
+unsigned reset_grid(int n) { return (unsigned)(n < 256 ? n : 256); }
+}  // namespace
+
+extern "C" int emu_reset_fill_rnd(const int32_t *ids, int n, uint64_t seed, float *rnd) {
+    if (n < 1) return 0;
+    emu::launch(reset_grid(n), 64, [&] { emloco::reset_fill_rnd_kernel(ids, n, (unsigned)(seed & 0xffffffffu), (unsigned)(seed >> 32), rnd); });
+    return 0;
+}
+
+enum { EMU_RESET_SAMPLE = 1, EMU_RESET_FK = 2, EMU_RESET_FINISH = 4, EMU_RESET_HISTORY = 8 };
+
+// the launches of emloco_task_reset one by one (stages: EMU_RESET_* bits, in the launcher's order)
+extern "C" int emu_task_reset_stages(int stages, const EmlocoResetBufs *b, const EmlocoModelDesc *m, float *root, float *dof, float *rb,
+                                     float *contact, float *lambda_ws, const int32_t *ids, int n, const float *rnd) {
+    EmuSimDev s;
+    if (!s.build(m, root, dof, rb, contact, lambda_ws)) return -1;
+    if (n < 1) return 0;
+    const EmlocoResetBufs t = *b;
+    const EmlocoSimDev d = s.d;
+    const unsigned grid = reset_grid(n);
+    if (stages & EMU_RESET_SAMPLE) emu::launch(grid, 64, [&] { emloco::reset_sample_kernel(t, d, ids, n, rnd); });
+    if (stages & EMU_RESET_FK)
+        emu::launch(grid, 64, [&] {
+            for (int bi = (int)blockIdx.x; bi < n; bi += (int)gridDim.x) {
+                const int env = ids[bi];
+                if (env < 0) break;
+                __shared__ float sm[FK_SM_FLOATS];
+                emloco::fk_env(d, env, (int)threadIdx.x, sm);
+                __syncthreads();
+            }
+        });
+    if (stages & EMU_RESET_FINISH) emu::launch(grid, 64, [&] { emloco::reset_finish_kernel(t, d, ids, n, rnd); });
+    if (stages & EMU_RESET_HISTORY) {
+        gridDim.y = EMLOCO_AMP_STEPS - 1;
+        for (unsigned y = 0; y < EMLOCO_AMP_STEPS - 1; ++y) {
+            blockIdx.y = y;
+            emu::launch(grid, 64, [&] { emloco::reset_amp_history_kernel(t, ids, n); });
+        }
+        blockIdx.y = 0; gridDim.y = 1;
+    }
+    return 0;
+}
+
+// the reset roles of reset_obs_kernel (no live role, no pool): the reset chain of every list entry and, unless the flags say
+// EMLOCO_RESET_NO_AMP_HISTORY, its 14 history rows; random rows supplied (rnd) or made from the seed into rnd_ws (rnd = NULL)
+extern "C" int emu_task_reset_obs(const EmlocoTaskBufs *pb, const EmlocoResetBufs *b, const EmlocoModelDesc *m, float *root, float *dof, float *rb,
+                                  float *contact, float *lambda_ws, const int32_t *ids, int n, uint64_t seed, float *rnd_ws, const float *rnd) {
+    EmuSimDev s;
+    if (!s.build(m, root, dof, rb, contact, lambda_ws)) return -1;
+    if (n < 1) return 0;
+    emloco::ChainArgs a; memset(&a, 0, sizeof(a));
+    a.n = n; a.n_slots = (int)reset_grid(n); a.h_slots = a.n_slots;
+    a.n_hist = (b->flags & EMLOCO_RESET_NO_AMP_HISTORY) ? 0 : EMLOCO_AMP_STEPS - 1;
+    a.live_mode = 0; a.reset_mode = EMLOCO_POST_OBS | EMLOCO_POST_AMP_ROW;
+    a.seeded = rnd ? 0 : 1;
+    a.seed_lo = (unsigned)(seed & 0xffffffffu); a.seed_hi = (unsigned)(seed >> 32);
+    a.ids = ids; a.rnd_in = rnd; a.rnd_ws = rnd_ws;
+    EmlocoResetBufs keyed = *b;
+    if (a.seeded) { keyed.real_pick = nullptr; keyed.real_pick_key = (uint32_t)((seed * 0xD6E8FEB86659FD93ull) >> 32); }
+    const EmlocoTaskBufs p = *pb;
+    const EmlocoSimDev d = s.d;
+    emu::launch((unsigned)(a.n_slots + a.h_slots * a.n_hist), 64, [&] { emloco::reset_obs_kernel(p, keyed, d, a); });
     return 0;
 }

@@ -814,3 +814,192 @@ def task_map(rows=520, cols=610, seed=3):
     coarse = torch.randint(-800, 800, (rows // 8 + 1, cols // 8 + 1), generator=g)[i // 8, j // 8]
     fine = torch.randint(-3, 4, (rows, cols), generator=g)
     return (coarse + fine).to(torch.int16)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the reset path (include/emloco_task.h: "Fused reset of finished envs"): every formula restated from the definitions the header
+# cites (motion_lib_smpl.py:485-606, torch_utils.py slerp / quat_to_exp_map, humanoid_pedestrain_terrain.py:526-631,
+# humanoid_amp.py:321-379), in the dtype given
+
+GEOM_SPHERE, GEOM_CAPSULE, GEOM_BOX = 0, 1, 2
+SLERP_C_STAR = math.sqrt(1.0 - 1e-6)         # the cosine at which slerp's sin(half angle) crosses 1e-3
+
+
+def quat_apply(q, v):
+    """quat_apply: v + w t + q_v x t with t = 2 q_v x v"""
+    qv, w = q[..., :3], q[..., 3:4]
+    qv, v = torch.broadcast_tensors(qv, v)
+    t = torch.cross(qv, v, dim=-1) * 2.0
+    return v + w * t + torch.cross(qv, t, dim=-1)
+
+
+def frame_blend(time, length, dt, nframes, dtype=F64):
+    """_calc_frame_blend: phase = clip(time / len, 0, 1); time = max(time, 0) AFTER the phase; i0 = trunc(phase (nf - 1)),
+    i1 = min(i0 + 1, nf - 1); blend = (time - i0 dt) / dt, not clamped.  -> i0, i1 (int64), blend"""
+    time, length, dt = _c(time, dtype), _c(length, dtype), _c(dt, dtype)
+    nf = torch.as_tensor(nframes).to("cpu").long()
+    phase = torch.clamp(time / length, 0.0, 1.0)
+    time = torch.clamp_min(time, 0.0)
+    i0 = (phase * (nf - 1).to(dtype)).long()
+    i1 = torch.minimum(i0 + 1, nf - 1)
+    return i0, i1, (time - i0.to(dtype) * dt) / dt
+
+
+def slerp(q0, q1, t, dtype=F64):
+    """torch_utils.slerp: q1 is flipped where the cosine is negative; the midpoint where |sin(half angle)| < 1e-3; q0 where
+    |cos| >= 1; t broadcasts over the leading dimensions ([...] or [..., 1])"""
+    q0, q1, t = _c(q0, dtype), _c(q1, dtype), _c(t, dtype)
+    if t.dim() < q0.dim():
+        t = t[..., None]
+    c = (q0 * q1).sum(-1, keepdim=True)
+    q1 = torch.where(c < 0, -q1, q1)
+    c = c.abs()
+    half = torch.acos(c)
+    s = torch.sqrt(1.0 - c * c)
+    out = (torch.sin((1.0 - t) * half) / s) * q0 + (torch.sin(t * half) / s) * q1
+    out = torch.where(s.abs() < 0.001, 0.5 * q0 + 0.5 * q1, out)
+    return torch.where(c.abs() >= 1.0, q0.expand_as(out), out)
+
+
+def slerp_branch_distances(q0, q1):
+    """float64 cosine of two frames and its distances to slerp's branch points: the sign flip (c = 0) and the midpoint / q0 branches
+    (c = sqrt(1 - 1e-6) .. 1: one band, the two lie 5e-7 apart).  Frames that are equal or antipodal are on no branch: every branch
+    returns q0 there."""
+    q0, q1 = _c(q0, F64), _c(q1, F64)
+    c = (q0 * q1).sum(-1)
+    same = (q0 == q1).all(-1) | (q0 == -q1).all(-1)
+    big = torch.full_like(c, 1e30)
+    return torch.where(same, big, c.abs()), torch.where(same, big, (c.abs() - SLERP_C_STAR).abs().minimum((c.abs() - 1.0).abs()))
+
+
+def quat_to_exp_map(q, dtype=F64):
+    """torch_utils.quat_to_exp_map: sin = sqrt(1 - w^2), angle = 2 acos(w) wrapped through atan2(sin, cos); angle x q_v / sin where
+    |sin| > 1e-5, zero elsewhere"""
+    q = _c(q, dtype)
+    w = q[..., 3:4]
+    sin_theta = torch.sqrt(1.0 - w * w)
+    angle = 2.0 * torch.acos(w)
+    angle = torch.atan2(torch.sin(angle), torch.cos(angle))
+    e = angle * (q[..., :3] / sin_theta)
+    return torch.where(sin_theta.abs() > 1e-5, e, torch.zeros_like(e))
+
+
+def motion_state(cache, mid, time, key_bodies=KEY_BODIES, dtype=F64):
+    """get_motion_state_smpl on a motion cache (dict of gts / grs / lrs / gvs / gavs [F][24][.], dvs [F][69], motion_len / motion_dt /
+    motion_nframes / motion_start [M]) for clip ids `mid` [n] at `time` [n] -> dict: root_pos / root_rot / root_vel / root_ang_vel,
+    dof_pos / dof_vel [n][69], key_pos [n][4][3], local_rot [n][24][4] (the blended joint quaternions), f0 / f1 / blend"""
+    mid = torch.as_tensor(mid).to("cpu").long()
+    g = lambda k: torch.as_tensor(cache[k]).to("cpu")
+    i0, i1, w = frame_blend(time, g("motion_len")[mid], g("motion_dt")[mid], g("motion_nframes")[mid], dtype=dtype)
+    f0, f1 = i0 + g("motion_start")[mid].long(), i1 + g("motion_start")[mid].long()
+    lerp = lambda a, wt: (1.0 - wt) * _c(a[f0], dtype) + wt * _c(a[f1], dtype)
+    gts = lerp(g("gts"), w[:, None, None])
+    lq = slerp(g("lrs")[f0], g("lrs")[f1], w[:, None], dtype=dtype)
+    return dict(root_pos=gts[:, 0], root_rot=slerp(g("grs")[f0, 0], g("grs")[f1, 0], w, dtype=dtype),
+                root_vel=lerp(g("gvs")[:, 0], w[:, None]), root_ang_vel=lerp(g("gavs")[:, 0], w[:, None]),
+                dof_pos=quat_to_exp_map(lq[:, 1:], dtype=dtype).reshape(-1, 69), dof_vel=lerp(g("dvs"), w[:, None]),
+                key_pos=gts[:, list(key_bodies)], local_rot=lq, f0=f0, f1=f1, blend=w)
+
+
+def reset_pick(u, n):
+    """min(trunc(u n), n - 1) with u n as the float32 product the launch forms (u and n are float32 numbers)"""
+    u = torch.as_tensor(u).to("cpu").float()
+    return torch.clamp((u * float(n)).long(), max=n - 1)
+
+
+def reset_root(state, u_yaw, u_speed, random_heading, place_xy, dtype=F64):
+    """the root of a reset from a motion_state: with random_heading the turn yaw = pi (2 u - 1) about z (hq x rot, hq applied to the angular
+    velocity) and the forward speed 0.5 u + 1 in place of the x velocity, turned by the NEW heading; x, y are the placement
+    -> xy [n][2], rot, vel, ang_vel"""
+    rot, vel, ang = (_c(state[k], dtype).clone() for k in ("root_rot", "root_vel", "root_ang_vel"))
+    if random_heading:
+        yaw = math.pi * (2.0 * _c(u_yaw, dtype) - 1.0)
+        hq = quat_about_z(yaw)
+        rot = quat_mul(hq, rot)
+        ang = quat_apply(hq, ang)
+        vel = torch.cat([(_c(u_speed, dtype) * 0.5 + 1.0)[:, None], vel[:, 1:]], dim=1)
+        vel = quat_apply(quat_about_z(calc_heading(rot)), vel)
+    return _c(place_xy, dtype), rot, vel, ang
+
+
+def rotvec_to_quat(e):
+    """rotation vector -> unit quaternion (the simulator's joint convention: no wrap, no threshold beyond 0 / 0)"""
+    a = e.norm(dim=-1, keepdim=True)
+    k = torch.where(a > 1e-12, torch.sin(a / 2.0) / a.clamp_min(1e-300), torch.full_like(a, 0.5))
+    return torch.cat([e * k, torch.cos(a / 2.0)], dim=-1)
+
+
+def forward_kinematics(root_state, dof_pos, parent, joint_off, dtype=F64):
+    """body positions [E][24][3] and rotations [E][24][4] of a tree (parent [24], joint_off [E][24][3]) from the root pose and the
+    joints' rotation vectors [E][69]: p_b = p_parent + R_parent off_b, q_b = q_parent x q_joint"""
+    rs, dp, off = _c(root_state, dtype), _c(dof_pos, dtype).reshape(-1, 23, 3), _c(joint_off, dtype)
+    qj = rotvec_to_quat(dp)
+    pos, rot = [rs[:, 0:3]], [rs[:, 3:7] / rs[:, 3:7].norm(dim=-1, keepdim=True)]
+    for b in range(1, 24):
+        p = int(parent[b])
+        pos.append(pos[p] + quat_rotate(rot[p], off[:, b]))
+        q = quat_mul(rot[p], qj[:, b - 1])
+        rot.append(q / q.norm(dim=-1, keepdim=True))
+    return torch.stack(pos, dim=1), torch.stack(rot, dim=1)
+
+
+def lowest_collision_point(body_pos, body_rot, geom_type, geom_a, geom_b, geom_r, dtype=F64):
+    """the lowest z over the simulator's ground-contact candidates: a sphere's centre (geom_a), a capsule's two ends (geom_a, geom_b), a
+    box's eight corners (centre geom_a, half extents geom_b), in the body frame, each minus the body's radius geom_r -> [E]"""
+    p, q, ga, gb, gr = (_c(t, dtype) for t in (body_pos, body_rot, geom_a, geom_b, geom_r))
+    low = torch.full((p.shape[0],), float("inf"), dtype=dtype)
+    for b in range(p.shape[1]):
+        gt = int(geom_type[b])
+        if gt == GEOM_SPHERE:
+            pts = [ga[:, b]]
+        elif gt == GEOM_CAPSULE:
+            pts = [ga[:, b], gb[:, b]]
+        else:
+            sg = lambda k, bit: 1.0 if k & bit else -1.0
+            pts = [ga[:, b] + gb[:, b] * torch.tensor([sg(k, 1), sg(k, 2), sg(k, 4)], dtype=dtype) for k in range(8)]
+        for lp in pts:
+            low = torch.minimum(low, p[:, b, 2] + quat_rotate(q[:, b], lp)[:, 2] - gr[:, b])
+    return low
+
+
+def _fmix32(x):
+    x &= 0xFFFFFFFF
+    x ^= x >> 16
+    x = (x * 0x85EBCA6B) & 0xFFFFFFFF
+    x ^= x >> 13
+    x = (x * 0xC2B2AE35) & 0xFFFFFFFF
+    return x ^ (x >> 16)
+
+
+def reset_rnd_row(seed, bi, n=512):
+    """row bi of the device's random rows for a 64-bit seed, exact (Python integers): per row fmix32(seed_lo ^ bi 0x9E3779B1) + seed_hi,
+    per entry k two rounds of the murmur3 finaliser around + 0x165667B1; the top 24 bits over 2^24 (exact in float32)"""
+    lo, hi = seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF
+    row = (_fmix32(lo ^ ((bi * 0x9E3779B1) & 0xFFFFFFFF)) + hi) & 0xFFFFFFFF
+    out = []
+    for k in range(n):
+        x = _fmix32((_fmix32(row ^ ((k * 0x27D4EB2F) & 0xFFFFFFFF)) + 0x165667B1) & 0xFFFFFFFF)
+        out.append((x >> 8) / 16777216.0)
+    return torch.tensor(out, dtype=F64).float()
+
+
+def real_pick_perm(x, n, key):
+    """the keyed bijection of [0, n) that picks a real path: 4-round Feistel network over the next even power of two >= n (at least 4),
+    halves swapped each round with F = fmix32(r 0x9E3779B1 + key + round 0x85EBCA6B), cycle-walked until the value is below n"""
+    bits = 2
+    while (1 << bits) < n:
+        bits += 2
+    half = bits >> 1
+    mask = (1 << half) - 1
+    while True:
+        l, r = x >> half, x & mask
+        for rnd in range(4):
+            l, r = r, l ^ (_fmix32((r * 0x9E3779B1 + key + rnd * 0x85EBCA6B) & 0xFFFFFFFF) & mask)
+        x = (l << half) | r
+        if x < n:
+            return x
+
+
+def seeded_real_key(seed):
+    """the permutation key a seeded reset derives from its seed: the high word of seed x 0xD6E8FEB86659FD93 (mod 2^64)"""
+    return ((seed * 0xD6E8FEB86659FD93) & 0xFFFFFFFFFFFFFFFF) >> 32
