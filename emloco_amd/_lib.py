@@ -164,6 +164,9 @@ class LocoValNets(C.Structure):
 
 TRACK_SAMPLES = 16          # EMLOCO_TRACK_SAMPLES
 TRACK_MOMENTS = 12          # EMLOCO_TRACK_MOMENTS
+EPISODE_RUNNING = 4         # EMLOCO_EPISODE_RUNNING
+EPISODE_MOMENTS = 15        # EMLOCO_EPISODE_MOMENTS
+EPISODE_GAME_OUT = 8        # EMLOCO_EPISODE_GAME_OUT
 
 
 class LocoValTrack(C.Structure):

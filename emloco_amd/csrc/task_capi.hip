@@ -6,6 +6,7 @@
 #include "reset_kernels.hip"
 #include "chain_kernels.hip"
 #include "traj_kernels.hip"
+#include "episode_stats_kernels.hip"
 #include "sim_state.h"
 #include "../../include/emloco_predictor.h"
 
@@ -345,6 +346,43 @@ int emloco_traj_densify(const float *knot_t, int n_knots, const float *dev_way, 
     if (!dev_way || !dev_out) return tfail(-1, "emloco_traj_densify: null waypoints or output");
     const unsigned grid = (unsigned)((n_traj + emloco::DENSIFY_TPB - 1) / emloco::DENSIFY_TPB);
     hipLaunchKernelGGL(emloco::traj_densify_kernel, dim3(grid), dim3(emloco::DENSIFY_THREADS), 0, (hipStream_t)stream, a, dev_way, dev_out, dev_valid);
+    THIPCHK(hipGetLastError());
+    return 0;
+}
+
+int emloco_episode_stats_step(int n_envs, const float *dev_rew_buf, const float *dev_reward_raw, const int64_t *dev_reset_buf,
+                              const int64_t *dev_terminate_buf, const int64_t *dev_progress_buf, const float *dev_rb_state,
+                              const float *dev_traj_verts, const uint8_t *dev_inverted, float inversion_scale, float dt, float traj_dur,
+                              float fail_dist, float *dev_running, double *dev_totals, float *dev_game_out, void *stream) {
+    static_assert(EMLOCO_EPM_TIMEOUT == EMLOCO_EPM_GAMES + EMLOCO_EPISODE_TIMEOUT && EMLOCO_EPM_FAR == EMLOCO_EPM_GAMES + EMLOCO_EPISODE_FAR &&
+                  EMLOCO_EPM_FALLEN == EMLOCO_EPM_GAMES + EMLOCO_EPISODE_FALLEN, "the cause counters follow the game counter");
+    if (!dev_rew_buf || !dev_reward_raw || !dev_reset_buf || !dev_terminate_buf || !dev_progress_buf || !dev_rb_state || !dev_traj_verts ||
+        !dev_running || !dev_totals)
+        return tfail(-1, "emloco_episode_stats_step: null buffer");
+    if (n_envs <= 0) return tfail(-1, "emloco_episode_stats_step: bad env count");
+    const auto positive = [](float x) { return x > 0.0f && x <= 3.402823466e38f; };
+    if (!positive(fail_dist) || !positive(dt) || !positive(traj_dur))
+        return tfail(-1, "emloco_episode_stats_step: fail_dist, dt and traj_dur must be positive and finite");
+    if (dev_inverted && !(fabsf(inversion_scale) <= 3.402823466e38f)) return tfail(-1, "emloco_episode_stats_step: bad inversion scale");
+    emloco::EpisodeStatsArgs a;
+    a.n_env = n_envs;
+    a.rew_buf = dev_rew_buf; a.reward_raw = dev_reward_raw;
+    a.reset_buf = dev_reset_buf; a.terminate_buf = dev_terminate_buf; a.progress_buf = dev_progress_buf;
+    a.rb_state = dev_rb_state; a.traj_verts = dev_traj_verts;
+    a.inverted = dev_inverted; a.neg_scale = -inversion_scale;
+    a.dt = dt; a.traj_dur = traj_dur; a.fail_dist = fail_dist;
+    a.running = dev_running; a.totals = dev_totals; a.game_out = dev_game_out;
+    const unsigned grid = (unsigned)((n_envs + emloco::kStatsWaves - 1) / emloco::kStatsWaves);
+    hipLaunchKernelGGL(emloco::episode_stats_step_kernel, dim3(grid), dim3(64 * emloco::kStatsWaves), 0, (hipStream_t)stream, a);
+    THIPCHK(hipGetLastError());
+    return 0;
+}
+
+int emloco_episode_stats_reduce(int n_envs, double *dev_totals, double *dev_moments, void *stream) {
+    if (!dev_totals || !dev_moments) return tfail(-1, "emloco_episode_stats_reduce: null buffer");
+    if (n_envs <= 0) return tfail(-1, "emloco_episode_stats_reduce: bad env count");
+    hipLaunchKernelGGL(emloco::episode_stats_reduce_kernel, dim3(1), dim3(emloco::kStatsReduceThreads), 0, (hipStream_t)stream, n_envs,
+                       dev_totals, dev_moments);
     THIPCHK(hipGetLastError());
     return 0;
 }

@@ -201,6 +201,18 @@ def all_reduce_mean_scalar(x):
     return float(t.item()) / dist.get_world_size()
 
 
+def all_gather_vector(t):
+    """Every rank's copy of a small vector, as a list of numpy arrays in rank order: one device read, and one collective when there are
+    several ranks (a vector whose entries fold differently -- sums, minima, maxima -- is merged by the caller from the parts)."""
+    if not is_distributed():
+        return [t.detach().cpu().numpy()]
+    if dist.get_backend() == "gloo":
+        t = t.detach().cpu()
+    parts = [torch.empty_like(t) for _ in range(dist.get_world_size())]
+    dist.all_gather(parts, t.detach().contiguous())
+    return [p.cpu().numpy() for p in parts]
+
+
 def sync_running_mean_std(*rms_modules):
     """hvd.sync_stats (common_agent.py:179-180): once per epoch every rank's observation statistics become the statistics
     of the pooled samples.  Each RunningMeanStd holds (count, mean, var) of what its rank saw; with weights w_r = count_r /

@@ -300,6 +300,7 @@ class AMPAgent:
         self.done_indices = torch.arange(E, device=self.device)
         self._idx_buf = torch.randperm(self.batch_size)
         self.epoch_num, self.frame = 0, 0
+        self.episode_stats = None                             # learning/episode_stats.py: set by the driver (run.py --experiment / --stats)
         self.train_result = {}
         self._init_amp_demo_buf()
 
@@ -375,6 +376,8 @@ class AMPAgent:
                 for k in ("neglogpacs", "values", "actions", "mus", "sigmas"):
                     buf[k][n] = res[k]
                 obs, rewards, dones, infos = self.vec_env.step(torch.clamp(res["actions"], -1.0, 1.0))
+                if self.episode_stats is not None:
+                    self.episode_stats.step()                     # behind the step's flags, ahead of the next reset
                 buf["rewards"][n] = rewards.unsqueeze(-1) if rewards.dim() == 1 else rewards
                 buf["next_obses"][n] = obs
                 buf["dones"][n] = dones.to(torch.uint8)

@@ -119,6 +119,10 @@ class LocoValRollout:
         if hasattr(self.task, "attach_returns"):
             self.task.attach_returns(None)
         self._disc_halves = None
+        # game statistics (learning/episode_stats.py): off unless attach_episode_stats() is called -- no launch, no allocation
+        self.episode_stats = None
+        self._epoch_fit = None
+        self.epoch_num = 0
         if self.fused:
             self._init_fused()
 
@@ -402,6 +406,13 @@ class LocoValRollout:
         ops._chk(lib.emloco_adamw_gated(self._n_param, P(self._flat_params), P(self.bucket.grads), P(z["m"]), P(z["v"]), P(a), P(b), P(self.bucket.tail),
                                         float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
                                         P(self._stats), st), "emloco_adamw_gated")
+        if self._epoch_fit is not None:
+            # the epoch's vnet_pred / combine_rwd (common_agent.py:206-207): sums of the network's output and of the normalised return over
+            # the fitted episodes, added on the device on the fit's stream -- only with the game statistics on
+            # (weight is 1 for a fitted episode and 0 elsewhere: two dot products and one add, three small launches off the main stream)
+            torch.dot(z["value"], z["weight"], out=self._step_fit[0])
+            torch.dot(z["target"], z["weight"], out=self._step_fit[1])
+            self._epoch_fit += self._step_fit
 
     # counters of the fit, read from the device on demand (a host synchronisation each)
     @property
@@ -420,6 +431,39 @@ class LocoValRollout:
     def vnet_fits(self):
         self._sync_fit()
         return int(round(self._stats[4].item()))
+
+    def attach_episode_stats(self, stats):
+        """Turn the game statistics on (an `EpisodeStats` of this loop's task) or off (None).  On: one more launch per step behind
+        `env.step`, and the sums behind `vnet_pred` / `combine_rwd` on the fit's stream; nothing the loop computes changes.  With
+        `overlap_reset` the reset chain is forked from the caller's stream by an event that `reset_done()` records behind the
+        statistics launch, so the chain is ordered behind it as it is in the one-stream schedule."""
+        self._sync_fit()
+        self.episode_stats = stats
+        self._epoch_fit = None if stats is None else torch.zeros(2, device=self.device, dtype=torch.float64)
+        self._step_fit = None if stats is None else torch.zeros(2, device=self.device)
+        self._epoch_base = None if stats is None else self._stats.detach().cpu().numpy().copy()
+
+    def epoch_report(self):
+        """After end_epoch(), with the statistics on: the game report of the epoch and the loop's own numbers of the per-epoch line
+        (common_agent.py:205-207,236): `vnet_loss` = the epoch's loss sum / fitted episodes, `vnet_pred` / `combine_rwd` = the means of
+        the network's output / the normalised return over them.  One read of the device for the lot."""
+        if self.episode_stats is None:
+            raise RuntimeError("LocoValRollout.epoch_report: attach_episode_stats() first")
+        self._sync_fit()
+        from ..dist import world_size
+        # [pred sum, target sum] are this rank's and are summed over the ranks; the loss / episode counters are global already (the
+        # bucket's tail is all-reduced ahead of every AdamW launch): they ride along divided by the world size
+        extra = torch.cat([self._epoch_fit, self._stats[2:5] / float(world_size())])
+        rep = self.episode_stats.end_epoch(extra=extra)
+        self._epoch_fit.zero_()
+        pred, target, loss, episodes, fits = (float(x) for x in self.episode_stats.last_extra)
+        base = self._epoch_base
+        d_loss, d_eps, d_fits = loss - base[2], episodes - base[3], fits - base[4]
+        base[2:5] = loss, episodes, fits
+        n = float(max(d_eps, 0.0))
+        own = dict(fitted_episodes=int(round(n)), vnet_fits=int(round(d_fits)), vnet_loss=float(d_loss) / n if n > 0 else 0.0,
+                   vnet_pred=pred / n if n > 0 else 0.0, combine_rwd=target / n if n > 0 else 0.0)
+        return rep, own
 
     def _reset_finished(self):
         """env_reset(done_indices) of :46 -- every env on the first call, afterwards the envs whose reset flag is set."""
@@ -445,6 +489,8 @@ class LocoValRollout:
             obs, rewards, dones, infos = self.vec_env.step(actions)
             inverted = task.inverted
             self.frames += self.num_actors
+            if self.episode_stats is not None:
+                self.episode_stats.step()                         # behind the step's flags, ahead of the next reset_done()
             if self._disc_halves is not None and getattr(task, "_returns_in_flags", False):
                 self._deferred_disc_step(infos["amp_obs"])
                 return
@@ -557,6 +603,7 @@ class LocoValRollout:
             # to the reference's class, tests/golden/locoval_lr_schedule.npz)
             self.vnet_optimizer._opt_called = True
             self.vnet_scheduler.step()
+        self.epoch_num += 1
 
     def play_steps(self):
         for n in range(self.horizon_length):
@@ -576,6 +623,43 @@ class LocoValRollout:
     def restore(self, path):
         self._sync_fit()
         self.valuenet.load_state_dict(torch.load(path, map_location=self.device))
+
+    def save_state(self, model_output_file):
+        """`<file>_valuenet_state.pth`, the sidecar of `<file>_valuenet.pth`: what a run needs beside the network to carry on -- the
+        AdamW moments and step counters, the position of the learning-rate schedule, the epoch and the frame count."""
+        if not self.fused:
+            raise RuntimeError("LocoValRollout.save_state: the fused loop only")
+        self._sync_fit()
+        z = self._fz
+        g = self.vnet_optimizer.param_groups[0]
+        state = {"adamw_m": z["m"].detach().cpu(), "adamw_v": z["v"].detach().cpu(), "adamw_step": z["steps"][self._flip].detach().cpu(),
+                 "lr": float(g["lr"]), "scheduler": self.vnet_scheduler.state_dict(), "sched_live": bool(getattr(self, "_sched_live", False)),
+                 "epoch": int(self.epoch_num), "frame": int(self.frames), "stats": self._stats.detach().cpu(), "variant": int(self._variant)}
+        path = model_output_file + "_valuenet_state.pth"
+        torch.save(state, path)
+        return path
+
+    def restore_state(self, model_output_file):
+        """`<file>_valuenet.pth` and its sidecar: network, AdamW state, schedule, epoch and frames carry on where save / save_state left
+        them.  The simulator's state and the random streams are not part of a checkpoint."""
+        if not self.fused:
+            raise RuntimeError("LocoValRollout.restore_state: the fused loop only")
+        state = torch.load(model_output_file + "_valuenet_state.pth", map_location="cpu")
+        if int(state["variant"]) != int(self._variant):
+            raise RuntimeError(f"LocoValRollout.restore_state: the checkpoint is of network variant {state['variant']}, this loop's is {self._variant}")
+        self.restore(model_output_file + "_valuenet.pth")
+        z = self._fz
+        z["m"].copy_(state["adamw_m"])
+        z["v"].copy_(state["adamw_v"])
+        for t in z["steps"]:                                  # the gated AdamW reads one counter and writes the other: both start equal
+            t.copy_(state["adamw_step"])
+        self._stats.copy_(state["stats"])
+        self.vnet_scheduler.load_state_dict(state["scheduler"])
+        self.vnet_optimizer.param_groups[0]["lr"] = float(state["lr"])
+        self._sched_live = bool(state["sched_live"])
+        self.epoch_num, self.frames = int(state["epoch"]), int(state["frame"])
+        if self._epoch_fit is not None:
+            self._epoch_base = self._stats.detach().cpu().numpy().copy()
 
     def train(self, max_epochs, model_output_file=None, save_freq=200, save_intermediate=True):
         """The finetune loop of CommonAgent.train: one epoch = one play_steps horizon."""

@@ -19,7 +19,19 @@ predictor's output (traj_generator.py:53-54,163-175): the table `evaluate_jta --
 takes its tables (`python -m emloco_amd.predictor.export_trajs`) from `--real_traj_file a.pkl[,b.pkl]`.  `--eval_tracks` also records how
 closely every game followed its path (learning/locoval_eval.py): a `tracking` block in the report, and in `--eval_records` the per-game
 `track` table and the `walked` / `target` xy at the path's own frames, origin-relative as the rows of the predicted-path table.
+
+    python -m emloco_amd.run ... --experiment NAME [--network_path DIR] [--max_iterations N | --steps N] [--save_freq K] [--resume] [--stats]
+
+is what CommonAgent.train does around train_epoch (common_agent.py:151-273), for the LocoVal fit and for `--train_policy` alike: per epoch
+the reference's line (`Ep: .. rwd: .. fps_step: .. eps_len: ..`, :236-238) from game statistics kept on the device
+(learning/episode_stats.py), one JSON object in DIR/NAME_log.jsonl, and checkpoints under the reference's names (:248-265) --
+`NAME_valuenet.pth` (+ `NAME_valuenet_state.pth`, the optimiser / schedule / epoch sidecar) and `NAME_valuenet_<epoch:08d>.pth` for the
+LocoVal fit, `NAME.pth` and `NAME_<epoch:08d>.pth` for the policy -- every --save_freq epochs, every fifth of those also as an
+intermediate, and at the end.  `--resume` carries an experiment on from them (not the simulator's state nor the random streams: a
+valid continuation, not a bit-identical one).  `--stats` alone: the statistics and the line, nothing on disk.
 """
+import json
+import os
 import random
 import sys
 import time
@@ -141,8 +153,209 @@ def pop_test_options(argv):
     return opt
 
 
+# ---------------------------------------------------------------------------------------------------------------- the training driver
+def train_options(argv, args=None):
+    """What the driver needs of the command line, checked before anything touches a device: `--steps N` is taken out of argv (get_args
+    does not know it), the driver's own flags are read from `args` (utils/config.py) or, ahead of get_args, straight from argv."""
+    steps = None
+    if "--steps" in argv:
+        i = argv.index("--steps")
+        if i + 1 >= len(argv):
+            raise SystemExit("run.py: --steps needs a value")
+        steps = int(argv[i + 1])
+        del argv[i:i + 2]
+    flag = lambda name: (name in argv) if args is None else bool(getattr(args, name[2:]))
+    val = lambda name, default, conv: (conv(_pop_opt(list(argv), name, default)) if args is None else conv(getattr(args, name[2:])))
+    opt = dict(steps=steps, experiment=val("--experiment", "", str), network_path=val("--network_path", "output/", str),
+               max_iterations=val("--max_iterations", 0, int), save_freq=val("--save_freq", 200, int), resume=flag("--resume"),
+               stats=flag("--stats"))
+    if steps is not None and opt["max_iterations"] > 0:
+        raise SystemExit("run.py: --steps and --max_iterations both say how long to train: give one of them")
+    if opt["max_iterations"] < 0 or (steps is not None and steps < 0):
+        raise SystemExit("run.py: --steps / --max_iterations must not be negative")
+    if opt["resume"] and not opt["experiment"]:
+        raise SystemExit("run.py: --resume continues an experiment: name it with --experiment NAME")
+    if "--test" in argv and (opt["experiment"] or opt["resume"] or opt["stats"] or opt["max_iterations"]):
+        raise SystemExit("run.py: --experiment / --max_iterations / --resume / --stats belong to training, not to --test")
+    opt["stats"] = opt["stats"] or bool(opt["experiment"])
+    opt["driver"] = bool(opt["experiment"] or opt["stats"] or opt["max_iterations"])
+    opt["model_output_file"] = os.path.join(opt["network_path"], opt["experiment"]) if opt["experiment"] else None
+    return opt
+
+
+def epoch_line(kind, epoch, frame, info):
+    """The reference's per-epoch line (common_agent.py:236-238): the long variant for the LocoVal fit, the short one for the policy
+    trainer.  An epoch without a finished game prints 0 for the means of the games."""
+    g = info.get("games") or {}
+    rwd, eps_len = g.get("ret_mean", 0.0), g.get("len_mean", 0.0)
+    head = f"Ep: {epoch}\trwd: {rwd:.2f}" if kind == "locoval" else f"Ep: {epoch}\trwd: {rwd:.1f}"
+    if kind == "locoval":
+        head += f"\tvnet_pred: {info['vnet_pred']:.2f}\tcombine_rwd: {info['combine_rwd']:.2f}\tvnet_loss: {info['vnet_loss']:.3f}"
+    return head + (f"\tfps_step: {info['fps_step']:.1f}\tfps_total: {info['fps_total']:.1f}\tep_time:{info['ep_time']:.1f}"
+                   f"\tframe: {frame}\teps_len: {eps_len:.1f}")
+
+
+def run_training(trainee, opt, say=print, rank=0):
+    """CommonAgent.train around `trainee.run_epoch()` (common_agent.py:151-273).  `trainee` (LocoValTrainee / PolicyTrainee below, a stub
+    in the tests) has `kind`, `horizon_length`, `epoch_num`, `frame`, `run_epoch() -> dict`, `save(model_output_file, epoch=None)`,
+    `resume(model_output_file)` and `final_line(steps, seconds)`.  Returns the number of epochs it ran."""
+    mof, K = opt["model_output_file"], int(opt["save_freq"])
+    log = None
+    if mof:
+        if rank == 0:
+            os.makedirs(os.path.dirname(mof) or ".", exist_ok=True)
+        if opt["resume"]:
+            trainee.resume(mof)
+            say(f"resumed {mof} at epoch {trainee.epoch_num}, frame {trainee.frame}")
+        if rank == 0:
+            log = open(mof + "_log.jsonl", "a" if opt["resume"] else "w")
+    # --max_iterations counts the experiment's epochs in total, as the reference's max_epochs does (a resumed run trains the rest);
+    # --steps (default 100) asks for that many more env steps, in whole epochs
+    if opt["max_iterations"] > 0:
+        todo = max(opt["max_iterations"] - trainee.epoch_num, 0)
+    else:
+        steps = 100 if opt["steps"] is None else opt["steps"]
+        todo = -(-steps // trainee.horizon_length)
+    t0 = time.time()
+    ran = 0
+    try:
+        for _ in range(todo):
+            info = trainee.run_epoch()
+            ran += 1
+            epoch, frame = trainee.epoch_num, trainee.frame
+            if opt["stats"]:
+                say(epoch_line(trainee.kind, epoch, frame, info) + info.get("tail", ""))
+            if log is not None:
+                rec = dict(epoch=epoch, frame=frame, wall_time=time.time(), **{k: v for k, v in info.items() if k != "tail"})
+                log.write(json.dumps(rec, default=float) + "\n")
+                log.flush()
+            if mof and K > 0 and epoch % K == 0:
+                trainee.save(mof)
+                say("latest model saved")
+                if epoch % (5 * K) == 0:
+                    trainee.save(mof, epoch)
+                    say("intermediate model saved")
+        if mof:
+            trainee.save(mof)
+    finally:
+        if log is not None:
+            log.close()
+    line = trainee.final_line(ran * trainee.horizon_length, time.time() - t0)
+    if line:
+        say(line)
+    return ran
+
+
+def _locoval_final_line(agent, num_envs, world, n, dt):
+    return (f"fps_step: {num_envs * world * n / dt:,.0f} env-steps/s ({n} steps of {num_envs} envs x {world} ranks), "
+            f"LocoVal loss {agent.vnet_loss:.4f}, {agent.fitted_episodes} episodes fitted")
+
+
+def _policy_epoch_tail(info):
+    return (f"fps_step {info['fps_step']:,.0f} fps_total {info['fps_total']:,.0f} "
+            f"a_loss {info['actor_loss']:.4f} c_loss {info['critic_loss']:.4f} disc_loss {info['disc_loss']:.4f} kl {info['kl']:.5f}")
+
+
+def locoval_loop(agent, num_envs, world, steps, say=print):
+    """The entry point's LocoVal loop without the driver's flags: `steps` env steps in whole horizons, one line at the very end."""
+    t0 = time.time()
+    n = 0
+    while n < steps:
+        agent.play_steps()
+        n += agent.horizon_length
+    torch.cuda.synchronize()
+    say(_locoval_final_line(agent, num_envs, world, n, time.time() - t0))
+
+
+def policy_loop(agent, steps, say=print):
+    """The entry point's PPO + AMP loop without the driver's flags: one line per epoch with the losses."""
+    n = 0
+    while n < steps:
+        info = agent.train_epoch()
+        n += agent.horizon_length
+        say(f"epoch {agent.epoch_num}: " + _policy_epoch_tail(info))
+
+
+class LocoValTrainee:
+    """The LocoVal fit under run_training: an epoch is one horizon of `LocoValRollout.step_once` and `end_epoch`."""
+    kind = "locoval"
+
+    def __init__(self, agent, world=1, rank=0, stats=None):
+        self.agent, self.world, self.rank, self.stats = agent, world, rank, stats
+        self.horizon_length = agent.horizon_length
+        if stats is not None:
+            agent.attach_episode_stats(stats)
+
+    epoch_num = property(lambda self: self.agent.epoch_num)
+    frame = property(lambda self: self.agent.frames * self.world)
+
+    def run_epoch(self):
+        a = self.agent
+        t0 = time.time()
+        for _ in range(a.horizon_length):
+            a.step_once()
+        a.end_epoch()
+        info = {}
+        if self.stats is not None:
+            games, own = a.epoch_report()                # (waits for the epoch's launches: the one read of the device)
+            info.update(games=games, **own)
+        else:
+            torch.cuda.synchronize()
+        dt = max(time.time() - t0, 1e-9)
+        frames = a.num_actors * self.world * a.horizon_length
+        info.update(fps_step=frames / dt, fps_total=frames / dt, ep_time=dt)     # the fit runs beside the rollout: one clock for both
+        return info
+
+    def save(self, mof, epoch=None):
+        if self.rank != 0:
+            return
+        self.agent.save(mof, epoch)
+        if epoch is None:
+            self.agent.save_state(mof)
+
+    def resume(self, mof):
+        self.agent.restore_state(mof)
+
+    def final_line(self, n, dt):
+        return _locoval_final_line(self.agent, self.agent.num_actors, self.world, n, max(dt, 1e-9))
+
+
+class PolicyTrainee:
+    """PPO + AMP under run_training: an epoch is one `AMPAgent.train_epoch`."""
+    kind = "policy"
+
+    def __init__(self, agent, world=1, rank=0, stats=None):
+        self.agent, self.world, self.rank, self.stats = agent, world, rank, stats
+        self.horizon_length = agent.horizon_length
+        agent.episode_stats = stats
+
+    epoch_num = property(lambda self: self.agent.epoch_num)
+    frame = property(lambda self: self.agent.frame * self.world)
+
+    def run_epoch(self):
+        info = self.agent.train_epoch()
+        out = {k: info[k] for k in ("actor_loss", "critic_loss", "disc_loss", "kl", "reward_raw") if k in info}
+        out.update(fps_step=info["fps_step"] * self.world, fps_total=info["fps_total"] * self.world, ep_time=info["total_time"])
+        if self.stats is not None:
+            out["games"] = self.stats.end_epoch()
+        out["tail"] = (f"\ta_loss {info['actor_loss']:.4f} c_loss {info['critic_loss']:.4f} disc_loss {info['disc_loss']:.4f} "
+                       f"kl {info['kl']:.5f}")
+        return out
+
+    def save(self, mof, epoch=None):
+        if self.rank == 0:
+            self.agent.save(mof if epoch is None else mof + "_" + str(epoch).zfill(8))
+
+    def resume(self, mof):
+        self.agent.restore(mof + ".pth")
+
+    def final_line(self, n, dt):
+        return None
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
+    train_opt = train_options(argv)                      # (--steps leaves argv; a bad combination stops the run before any device call)
     # --test (the reference's player, amp_value_players.py): its own options, checked before anything touches a device
     opt = pop_test_options(argv)
     games_num, eval_out, eval_records, max_steps = opt["games_num"], opt["eval_out"], opt["eval_records"], opt["max_steps"]
@@ -159,11 +372,7 @@ def main(argv=None):
         compare = load_compare_valuenets(compare)
     from . import configure_runtime
     configure_runtime()                                  # entry point: 16 hardware queues, ahead of the first GPU call (emloco_amd/__init__.py)
-    steps = 100
-    if "--steps" in argv:
-        i = argv.index("--steps")
-        steps = int(argv[i + 1])
-        del argv[i:i + 2]
+    steps = 100 if train_opt["steps"] is None else train_opt["steps"]
     policy_ckpt, use_policy = None, False
     if "--policy_checkpoint" in argv:            # rl_games-layout checkpoint of the frozen PACER policy (config 3)
         i = argv.index("--policy_checkpoint")
@@ -211,12 +420,12 @@ def main(argv=None):
         agent = AMPAgent(env, yaml.safe_load(open(DEFAULT_CFG)))
         if policy_ckpt:
             agent.restore(policy_ckpt)
-        n = 0
-        while n < steps:
-            info = agent.train_epoch()
-            n += agent.horizon_length
-            say(f"epoch {agent.epoch_num}: fps_step {info['fps_step']:,.0f} fps_total {info['fps_total']:,.0f} "
-                  f"a_loss {info['actor_loss']:.4f} c_loss {info['critic_loss']:.4f} disc_loss {info['disc_loss']:.4f} kl {info['kl']:.5f}")
+        if train_opt["driver"]:
+            from .learning.episode_stats import EpisodeStats
+            stats = EpisodeStats(env.env.task) if train_opt["stats"] else None           # the policy trainer's rewards carry no penalty
+            run_training(PolicyTrainee(agent, world, rank, stats), train_opt, say, rank)
+        else:
+            policy_loop(agent, steps, say)
         return
     from .learning.locoval_rollout import LocoValRollout
     kw = {}
@@ -226,15 +435,14 @@ def main(argv=None):
         kw = dict(policy=bundle.policy, disc_reward=bundle.disc_reward,
                   inversion_penalty_scale=float(bundle.config.get("inversion_penalty_scale", 0.3)))
     agent = LocoValRollout(env, use_pose=args.input_init_pose, use_vel=args.input_init_vel, **kw)
-    t0 = time.time()
-    n = 0
-    while n < steps:
-        agent.play_steps()
-        n += agent.horizon_length
-    torch.cuda.synchronize()
-    dt = time.time() - t0
-    say(f"fps_step: {env.env.num_envs * world * n / dt:,.0f} env-steps/s ({n} steps of {env.env.num_envs} envs x {world} ranks), "
-        f"LocoVal loss {agent.vnet_loss:.4f}, {agent.fitted_episodes} episodes fitted")
+    if train_opt["driver"]:
+        stats = None
+        if train_opt["stats"]:
+            from .learning.episode_stats import EpisodeStats
+            stats = EpisodeStats(env.env.task, inverted_penalty=agent.inversion_penalty_scale)
+        run_training(LocoValTrainee(agent, world, rank, stats), train_opt, say, rank)
+    else:
+        locoval_loop(agent, env.env.num_envs, world, steps, say)
     if world > 1:
         torch.distributed.destroy_process_group()
 

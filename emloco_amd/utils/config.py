@@ -51,6 +51,16 @@ def get_args(argv=None):
         {"name": "--no_virtual_display", "action": "store_true", "default": True},
         {"name": "--show_sensors", "action": "store_true", "default": False},
         {"name": "--add_proj", "action": "store_true", "default": False},
+        # the training driver (run.py; CommonAgent.train, common_agent.py:151-273)
+        {"name": "--experiment", "type": str, "default": "",
+         "help": "name of the run: checkpoints and NAME_log.jsonl go to --network_path/NAME (turns the game statistics on)"},
+        {"name": "--max_iterations", "type": int, "default": 0, "help": "number of training epochs (instead of --steps)"},
+        {"name": "--save_freq", "type": int, "default": 200, "help": "a checkpoint every K epochs, an intermediate one every 5 K"},
+        {"name": "--resume", "action": "store_true", "default": False,
+         "help": "continue --experiment from its checkpoint: network, optimiser state, learning-rate schedule, epoch and frame numbering "
+                 "carry on and the log is appended.  The simulator's state and the random streams are not restored: a valid continuation "
+                 "of the run, not a bit-identical one"},
+        {"name": "--stats", "action": "store_true", "default": False, "help": "game statistics and the per-epoch line without --experiment"},
     ]
     args = gymutil.parse_arguments(description="EmLoco rollout on MI355X", custom_parameters=custom_parameters, argv=argv)
     args.device_id = args.compute_device_id

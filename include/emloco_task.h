@@ -309,6 +309,53 @@ int emloco_task_chain_profile(long long *host16);
 int emloco_traj_densify(const float *knot_t, int n_knots, const float *dev_way, int64_t n_traj, const float *query_t, int n_query,
                         float *dev_out, uint8_t *dev_valid, int flags, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Game statistics of a training run, kept on the device: what rl_games' game_rewards / game_lengths meters and the per-epoch line of
+ * CommonAgent.train report, without the host reading anything between epochs.
+ *
+ * Per env the step kernel keeps EMLOCO_EPISODE_RUNNING float32 running values of the game in progress -- [0] return, [1] its location
+ * part, [2] its power part (the two reward_raw columns), [3] length -- added in step order, and EMLOCO_EPISODE_MOMENTS doubles of epoch
+ * totals in the order of the enumerators below.  The causes of a finished game (reset_buf != 0):
+ *   FAR      the squared xy distance of the root to the path's target at progress * dt exceeds fail_dist^2 -- the target is sampled by
+ *            the device function the post-physics kernel samples it with, on the same traj_verts and progress_buf
+ *   FALLEN   terminate_buf is set and the game is not FAR
+ *   TIMEOUT  everything else
+ * MAX_SPEED2 / MAX_ANG_SPEED2 are the maxima over the env's 24 bodies and the epoch's steps of (vx vx + vy vy) + vz vz of the linear /
+ * angular velocity (float32 arithmetic; a NaN counts as 0 here and as a non-finite step), NONFINITE_STEPS the steps at which any of the
+ * env's 24 x 13 state values was NaN or +-Inf. */
+#define EMLOCO_EPISODE_RUNNING 4
+#define EMLOCO_EPISODE_MOMENTS 15
+#define EMLOCO_EPISODE_GAME_OUT 8
+enum {
+    EMLOCO_EPM_GAMES = 0, EMLOCO_EPM_TIMEOUT = 1, EMLOCO_EPM_FAR = 2, EMLOCO_EPM_FALLEN = 3,
+    EMLOCO_EPM_SUM_LEN = 4, EMLOCO_EPM_SUM_LEN2 = 5, EMLOCO_EPM_MIN_LEN = 6, EMLOCO_EPM_MAX_LEN = 7,
+    EMLOCO_EPM_SUM_RET = 8, EMLOCO_EPM_SUM_RET2 = 9, EMLOCO_EPM_SUM_LOC = 10, EMLOCO_EPM_SUM_POW = 11,
+    EMLOCO_EPM_NONFINITE_STEPS = 12, EMLOCO_EPM_MAX_SPEED2 = 13, EMLOCO_EPM_MAX_ANG_SPEED2 = 14
+};
+enum { EMLOCO_EPISODE_RUNS = 0, EMLOCO_EPISODE_TIMEOUT = 1, EMLOCO_EPISODE_FAR = 2, EMLOCO_EPISODE_FALLEN = 3 };
+
+/* One env step of the bookkeeping, for all n_envs envs; to be launched after the step's post-physics pass and before the finished envs
+ * are reset.  Stands in for amp_continuous_value.py:63-64 (the inversion penalty: rew_buf * -inversion_scale where dev_inverted is set;
+ * dev_inverted may be NULL, as for the policy trainer), :94-101 / amp_continuous.py:153-154 / common_agent.py:399-400 (current_rewards,
+ * current_lengths, game_rewards.update, game_lengths.update) and :104-107 (the running values of a finished env start again from zero).
+ *   dev_rew_buf [E], dev_reward_raw [E][2], dev_reset_buf / dev_terminate_buf / dev_progress_buf [E] int64, dev_rb_state [E][24][13],
+ *   dev_traj_verts [E][101][3]; dt, traj_dur, fail_dist as in EmlocoTaskBufs
+ *   dev_running [E][EMLOCO_EPISODE_RUNNING] float, dev_totals [E][EMLOCO_EPISODE_MOMENTS] double: in/out, zeroed by the caller once
+ *   dev_game_out [E][EMLOCO_EPISODE_GAME_OUT] float or NULL (tests): [0..3] the running values of the game that finished at this step
+ *   (zeros otherwise), [4] its cause (EMLOCO_EPISODE_*), [5, 6] the target's xy, [7] the squared distance
+ * A NULL required buffer, n_envs <= 0, or a dt / traj_dur / fail_dist that is not positive and finite: -1, nothing is written. */
+int emloco_episode_stats_step(int n_envs, const float *dev_rew_buf, const float *dev_reward_raw, const int64_t *dev_reset_buf,
+                              const int64_t *dev_terminate_buf, const int64_t *dev_progress_buf, const float *dev_rb_state,
+                              const float *dev_traj_verts, const uint8_t *dev_inverted, float inversion_scale, float dt, float traj_dur,
+                              float fail_dist, float *dev_running, double *dev_totals, float *dev_game_out, void *stream);
+
+/* Once per epoch, one workgroup: dev_moments[EMLOCO_EPISODE_MOMENTS] (double) = the per-env totals folded over the envs in a fixed tree
+ * order -- sums, MIN_LEN a minimum over the envs that finished a game (0 when none did), MAX_LEN / MAX_SPEED2 / MAX_ANG_SPEED2 maxima
+ * -- then dev_totals is cleared; dev_running (the games in progress) is not touched.  What CommonAgent.train reads off the meters once
+ * per epoch (common_agent.py:199-201: game_rewards.get_mean, game_lengths.get_mean) comes from this vector; the means here are over the
+ * games of the epoch, not over rl_games' window of the last games.  NULL buffers or n_envs <= 0: -1, nothing is written. */
+int emloco_episode_stats_reduce(int n_envs, double *dev_totals, double *dev_moments, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
