@@ -205,8 +205,9 @@ __device__ __forceinline__ void ref_exp_map_to_quat(const float *e, float *o) {
     float n = sqrtf(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2]);
     if (n < 1e-9f) n = 1e-9f;
     float th = angle / 2.0f;
-    float s = cr_sinf(th);
-    float q[4] = {ax[0] / n * s, ax[1] / n * s, ax[2] / n * s, cr_cosf(th)};
+    float s, c;
+    cr_sincosf(th, &s, &c);
+    float q[4] = {ax[0] / n * s, ax[1] / n * s, ax[2] / n * s, c};
     float qn = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
     if (qn < 1e-9f) qn = 1e-9f;
     o[0] = q[0] / qn; o[1] = q[1] / qn; o[2] = q[2] / qn; o[3] = q[3] / qn;

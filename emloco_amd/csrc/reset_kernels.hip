@@ -409,9 +409,14 @@ traj_reset_kernel(EmlocoResetBufs t, const int32_t *ids, int n, const float *rnd
 __device__ __forceinline__ void reset_amp_history_row_to(const EmlocoResetBufs &t, const float *betas, float *out, int k, int mid, float mt, int lane, float *sm) {
     float *sh_root = sm, *sh_dp = sm + 16, *sh_dv = sh_dp + RNDOF, *sh_key = sh_dv + RNDOF;
     const FrameBlend fb = frame_blend(t, mid, mt - t.dt * (float)k);
+    // one slerp pass for the 24 blended rotations: lane 0 the root's global rotation, lanes 1..23 the joints' local ones
+    float q[4] = {0.0f, 0.0f, 0.0f, 1.0f};
+    if (lane < RNB) {
+        const float *qs = lane == 0 ? t.grs : t.lrs;
+        ref_slerp(qs + (fb.f0 * RNB + lane) * 4, qs + (fb.f1 * RNB + lane) * 4, fb.blend, q);
+    }
     if (lane >= 1 && lane < RNB) {
-        float q[4], e[3];
-        ref_slerp(t.lrs + (fb.f0 * RNB + lane) * 4, t.lrs + (fb.f1 * RNB + lane) * 4, fb.blend, q);
+        float e[3];
         ref_quat_to_exp_map(q, e);
         for (int c = 0; c < 3; ++c) {
             sh_dp[(lane - 1) * 3 + c] = e[c];
@@ -424,7 +429,7 @@ __device__ __forceinline__ void reset_amp_history_row_to(const EmlocoResetBufs &
             sh_root[7 + c] = lerp1(t.gvs[(fb.f0 * RNB) * 3 + c], t.gvs[(fb.f1 * RNB) * 3 + c], fb.blend);
             sh_root[10 + c] = lerp1(t.gavs[(fb.f0 * RNB) * 3 + c], t.gavs[(fb.f1 * RNB) * 3 + c], fb.blend);
         }
-        ref_slerp(t.grs + (fb.f0 * RNB) * 4, t.grs + (fb.f1 * RNB) * 4, fb.blend, sh_root + 3);
+        for (int c = 0; c < 4; ++c) sh_root[3 + c] = q[c];
     }
     if (lane < 4) {
         const int kb = t.key_bodies[lane];

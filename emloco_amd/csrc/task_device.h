@@ -191,26 +191,47 @@ __device__ __forceinline__ void post_physics_env(const EmlocoTaskBufs &t, int mo
     if (mode & EMLOCO_POST_OBS) {
         float *obs = t.obs_buf + (long)env * EMLOCO_OBS;
         float *fobs = t.flip_obs_buf + (long)env * EMLOCO_OBS;
-        float hinv[4], hinv_f[4];
-        ref_quat_about_z(-ref_calc_heading(root + 3), hinv);
-        const float froot_rot[4] = {-root[3], root[4], -root[5], root[6]};
-        ref_quat_about_z(-ref_calc_heading(froot_rot), hinv_f);
+        // ---- the three heading quaternions in ONE pass: lane 0 the root's inverse heading, lane 1 the mirrored root's, lane 2 the head's
+        // heading (a wave pays for the double-precision atan2 + sincos once, whatever the number of lanes in it; one after the other
+        // they were three wave-uniform evaluations).  Broadcast with v_readlane: wave-uniform values, held in scalar registers
+        float hinv[4], hinv_f[4], hq[4];
+        {
+            const float *src = lane == 2 ? sh_body[t.head_body] + 3 : root + 3;
+            const float q[4] = {lane == 1 ? -src[0] : src[0], src[1], lane == 1 ? -src[2] : src[2], src[3]};
+            const float h = ref_calc_heading(q);
+            float hl[4];
+            ref_quat_about_z(lane == 2 ? h : -h, hl);
+            for (int k = 0; k < 4; ++k) { hinv[k] = lane_bcast(hl[k], 0); hinv_f[k] = lane_bcast(hl[k], 1); hq[k] = lane_bcast(hl[k], 2); }
+        }
         PPSTAMP(2);
-        // ---- self obs + mirrored self obs (lane = body); staged in LDS so the row is written coalesced
-        if (lane < TNB) {
-            const float *bd = sh_body[lane];
-            self_obs_body(lane, root, hinv, bd, bd + 3, bd + 7, bd + 10, sh_obs);
-            const float *sb = sh_body[t.left_to_right[lane]];
-            const float fp[3] = {sb[0], -sb[1], sb[2]};
-            const float fr[4] = {-sb[3], sb[4], -sb[5], sb[6]};
-            const float fv[3] = {sb[7], -sb[8], sb[9]};
-            const float fa[3] = {-sb[10], sb[11], -sb[12]};
-            const float froot_pos[3] = {root[0], -root[1], root[2]};
-            self_obs_body(lane, froot_pos, hinv_f, fp, fr, fv, fa, sh_fobs);
-        } else if (lane < TNB + 11) {
-            const float bv = t.betas[(long)env * 17 + (lane - TNB)];
-            sh_obs[357 + lane - TNB] = bv;
-            sh_fobs[357 + lane - TNB] = bv;
+        // ---- centre-height probes (3x3, yaw only) around the root: the map loads are issued here and consumed behind the self
+        // observation, whose arithmetic covers their latency
+        int16_t ch1 = 0, ch2 = 0;
+        if (lane < 9) {
+            float wx, wy;
+            int px, py;
+            center_probe(root, root + 3, lane, &wx, &wy);
+            map_index(t.hf_rows, t.hf_cols, wx, wy, t.hscale, &px, &py);
+            ch1 = t.heightfield[px * t.hf_cols + py];
+            ch2 = t.heightfield[(px + 1) * t.hf_cols + (py + 1)];
+        }
+        // ---- self obs (lanes 0..23 = body) and mirrored self obs (lanes 24..47 = body + 24) in one pass; staged in LDS so the row is
+        // written coalesced
+        if (lane < 2 * TNB) {
+            const bool mir = lane >= TNB;
+            const int b = mir ? lane - TNB : lane;
+            const float *sb = sh_body[mir ? t.left_to_right[b] : b];
+            const float bp[3] = {sb[0], mir ? -sb[1] : sb[1], sb[2]};
+            const float br[4] = {mir ? -sb[3] : sb[3], sb[4], mir ? -sb[5] : sb[5], sb[6]};
+            const float bv[3] = {sb[7], mir ? -sb[8] : sb[8], sb[9]};
+            const float ba[3] = {mir ? -sb[10] : sb[10], sb[11], mir ? -sb[12] : sb[12]};
+            const float rp[3] = {root[0], mir ? -root[1] : root[1], root[2]};
+            const float hv[4] = {mir ? hinv_f[0] : hinv[0], mir ? hinv_f[1] : hinv[1], mir ? hinv_f[2] : hinv[2], mir ? hinv_f[3] : hinv[3]};
+            self_obs_body(b, rp, hv, bp, br, bv, ba, mir ? sh_fobs : sh_obs);
+        } else if (lane < 2 * TNB + 11) {
+            const float bv = t.betas[(long)env * 17 + (lane - 2 * TNB)];
+            sh_obs[357 + lane - 2 * TNB] = bv;
+            sh_fobs[357 + lane - 2 * TNB] = bv;
         }
         // ---- location obs (lane = sample)
         if (lane < EMLOCO_TRAJ_SAMPLES) {
@@ -222,11 +243,9 @@ __device__ __forceinline__ void post_physics_env(const EmlocoTaskBufs &t, int mo
             fobs[EMLOCO_SELF_OBS + 2 * lane] = rr[0];
             fobs[EMLOCO_SELF_OBS + 2 * lane + 1] = -rr[1];
         }
-        // ---- centre-height probes (3x3, yaw only) around the root
         if (lane < 9) {
-            float wx, wy;
-            center_probe(root, root + 3, lane, &wx, &wy);
-            sh_center[lane] = sample_height(t.heightfield, t.hf_rows, t.hf_cols, wx, wy, t.hscale, t.vscale);
+            const int16_t hm = ch1 < ch2 ? ch1 : ch2;                        // sample_height_at
+            sh_center[lane] = (float)hm * t.vscale;
         }
         __syncthreads();
         PPSTAMP(3);
@@ -234,8 +253,6 @@ __device__ __forceinline__ void post_physics_env(const EmlocoTaskBufs &t, int mo
         const float cmean = mean9(sh_center);
         // ---- 32x32 height grid around the head, rotated by the head's heading (16 points per lane)
         const float *head = sh_body[t.head_body];
-        float hq[4];
-        ref_quat_about_z(ref_calc_heading(head + 3), hq);
         PPSTAMP(4);
         float *hobs = obs + EMLOCO_SELF_OBS + 2 * EMLOCO_TRAJ_SAMPLES;
         float *fhobs = fobs + EMLOCO_SELF_OBS + 2 * EMLOCO_TRAJ_SAMPLES;

@@ -16,7 +16,7 @@ pool = torch.randn(64, E, 69, device=dev, generator=g) * float(np.exp(-2.9))
 lib = L.load()
 buf = (C.c_longlong * 8)()
 lib.emloco_task_post_profile(buf)
-names = ["load bodies + trajectory samples", "heading quaternions (2 x atan2 + sincos)", "self obs -> LDS, location obs, centre probes", "row writes + head heading",
+names = ["load bodies + trajectory samples", "heading quaternions (root, mirrored root, head: one pass)", "centre probes, self obs -> LDS, location obs", "row writes",
          "height grid 32 x 32", "AMP shift (reward / flags are not in this role)", "AMP row"]
 acc = []
 for rep in range(20):
