@@ -48,13 +48,6 @@ int check_device_error(EmlocoSim *s, const char *where) {
     return fail(EMLOCO_E_HIP, buf);
 }
 
-__global__ void copy_rows_kernel(const float *src, float *dst, const int *ids, int n_ids, int row_len) {
-    const int i = blockIdx.x;
-    if (i >= n_ids) return;
-    const long base = (long)ids[i] * row_len;
-    for (int k = threadIdx.x; k < row_len; k += blockDim.x) dst[base + k] = src[base + k];
-}
-
 __global__ void fill_quat_kernel(float *root, int n_env) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e < n_env) root[(long)e * 13 + 6] = 1.0f;
@@ -452,7 +445,7 @@ static int set_indexed(EmlocoSim *s, const float *dev_full, float *own, int row_
     if (n == 0) return EMLOCO_OK;
     hipStream_t st = (hipStream_t)stream;
     if (dev_full != own) {
-        hipLaunchKernelGGL(copy_rows_kernel, dim3((unsigned)n), dim3(64), 0, st, dev_full, own, (const int *)ids, n, row_len);
+        hipLaunchKernelGGL(emloco::copy_rows_kernel, dim3((unsigned)n), dim3(64), 0, st, dev_full, own, (const int *)ids, n, row_len, s->n_env);
         HIPCHK(hipGetLastError());
     }
     hipLaunchKernelGGL(emloco::sim_fk_kernel, dim3((unsigned)(n > 256 ? 256 : n)), dim3(64), 0, st, s->dev, (const int *)ids, n);

@@ -1928,6 +1928,20 @@ sim_fk_kernel(EmlocoSimDev d, const int *env_ids, int n_ids) {
     }
 }
 
+// Rows of the listed envs from a caller's full tensor into the simulator's own (the *_indexed setters when `dev_full` is not the
+// sim's alias): one workgroup per list entry.  Entries outside [0, n_env) are skipped -- the -1 padding of a device-compacted list
+// (emloco_sim.h: valid ids first, -1 after them) and, since the check costs nothing, ids past the end -- so no entry can make a
+// store land outside the destination.
+__global__ void __launch_bounds__(64)
+copy_rows_kernel(const float *src, float *dst, const int *ids, int n_ids, int row_len, int n_env) {
+    const int i = blockIdx.x;
+    if (i >= n_ids) return;
+    const int env = ids[i];
+    if (env < 0 || env >= n_env) return;
+    const long base = (long)env * row_len;
+    for (int k = threadIdx.x; k < row_len; k += blockDim.x) dst[base + k] = src[base + k];
+}
+
 }  // namespace emloco
 
 #undef cross3

@@ -162,7 +162,11 @@ int emloco_sim_step(EmlocoSim *sim, int n_calls, void *stream);
  * issued as two launches on two streams: the envs that just finished an episode are reset and stepped beside the others,
  * amp_continuous_value.py:46,74 env_reset(done_indices) followed by env.step).  Exactly one of the two selectors:
  * `dev_skip` (int64 per env, the task's reset_buf layout): envs with a non-zero entry are left untouched;
- * `dev_env_ids` (int32, n_ids entries): a device-compacted list, valid ids first and -1 after them (emloco_task_compact_done). */
+ * `dev_env_ids` (int32, n_ids entries): a device-compacted list, valid ids first and -1 after them (emloco_task_compact_done).
+ * Id lists, here and in emloco_sim_fk_indexed / emloco_sim_set_*_indexed: n entries with 0 <= n <= n_env; the ids lie in
+ * [0, n_env) and are distinct (one workgroup per entry: two entries naming one env would race); the valid ids come first and
+ * -1 padding after them -- the step skips a -1 wherever it stands, the forward kinematics end at the first one.  An id >= n_env
+ * is the caller's error: nothing checks it on the device ahead of the step or the forward kinematics. */
 int emloco_sim_step_subset(EmlocoSim *sim, int n_calls, const int64_t *dev_skip, const int32_t *dev_env_ids, int n_ids, void *stream);
 /* Split launch (extension, off = 1 part by default; results do not depend on it).  The substeps of an env.step run as
  * `n_parts` workgroups per env in ONE launch -- all first parts, then all second parts, ... -- a later part continuing from
@@ -186,8 +190,9 @@ int emloco_sim_sync(EmlocoSim *sim, void *stream);
 int emloco_sim_debug_poison_part(EmlocoSim *sim, int env, int spin_max);
 /* Diagnostics and one cross-unit helper (no counterpart in the gym API; the product's Python never calls the three diagnostic
  * ones -- tools/sim_phase_profile.py, tools/exp/cost_hist.py do).  They synchronise the device and copy to HOST buffers.
- *   emloco_sim_fk_indexed   forward kinematics of the listed envs (device int32 ids); the reset chain of emloco_task.h calls it
- *                           (the two translation units link through this symbol)
+ *   emloco_sim_fk_indexed   forward kinematics of the listed envs (device int32 ids, the id-list contract of emloco_sim_step_subset:
+ *                           in [0, n_env), distinct, valid ids first; the pass ends at the first -1); the reset chain of
+ *                           emloco_task.h calls it (the two translation units link through this symbol)
  *   emloco_sim_cost_ticks   per-env durations (100 MHz ticks) of the latest step, the key of the cost-ordered dispatch
  *                           (emloco_sim_set_cost_order must be on) and, from the second call on, each workgroup's start stamps
  *                           (host_start: 2 n_envs entries, or NULL)
@@ -198,7 +203,10 @@ int emloco_sim_cost_ticks(EmlocoSim *sim, unsigned *host_ticks, unsigned long lo
 int emloco_sim_profile(EmlocoSim *sim, long long *host_out, int n);
 /* gym.set_actor_root_state_tensor_indexed / set_dof_state_tensor_indexed -- humanoid.py:470-475.
  * `dev_full` is the full tensor (may be the sim's own alias); rows of the listed envs are applied and the
- * rigid-body state of those envs is recomputed.  `dev_env_ids` int32 device pointer, n entries. */
+ * rigid-body state of those envs is recomputed.  `dev_env_ids` int32 device pointer, n entries, 0 <= n <= n_env (n = 0: nothing
+ * is launched); the list follows the id-list contract stated at emloco_sim_step_subset (ids in [0, n_env), distinct, valid ids
+ * first, -1 padding after them).  The row copy skips every entry outside [0, n_env), so padding writes nothing; the forward
+ * kinematics behind it end at the first -1, and an id >= n_env is the caller's error there. */
 int emloco_sim_set_root_state_indexed(EmlocoSim *sim, const float *dev_full, const int32_t *dev_env_ids, int n, void *stream);
 int emloco_sim_set_dof_state_indexed(EmlocoSim *sim, const float *dev_full, const int32_t *dev_env_ids, int n, void *stream);
 /* gym.refresh_rigid_body_state_tensor after host-side state edits: recompute body states of all envs */

@@ -53,7 +53,7 @@ def _hf_plane(hf, cx, cy):
     """csrc/sim_kernels.hip: hf_plane in float64: height of the cell triangle's plane under (cx, cy), its unit normal, the triangle's id."""
     smp, hs, vs = hf["samples"], hf["horizontal_scale"], hf["vertical_scale"]
     nx, ny = smp.shape
-    gx, gy = cx / hs, cy / hs
+    gx, gy = (cx - hf.get("origin_x", 0.0)) / hs, (cy - hf.get("origin_y", 0.0)) / hs      # sample (0, 0) sits at the origin
     i, j = int(np.clip(np.floor(gx), 0, nx - 2)), int(np.clip(np.floor(gy), 0, ny - 2))
     u, v = gx - i, gy - j
     h00, h01, h10, h11 = (vs * float(smp[i, j]), vs * float(smp[i, j + 1]), vs * float(smp[i + 1, j]), vs * float(smp[i + 1, j + 1]))

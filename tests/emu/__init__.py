@@ -61,8 +61,11 @@ def model_desc(arr):
                      _p(arr["effort"]))
 
 
-def sim_step(osim, n_calls=1, expect_error=None):
-    """Advance an oracle.Sim-shaped state holder with the emulated HIP kernel (same arrays, in place)."""
+def sim_step(osim, n_calls=1, expect_error=None, cost_ticks=None):
+    """Advance an oracle.Sim-shaped state holder with the emulated HIP kernel (same arrays, in place).  `cost_ticks`: a uint32 array
+    [n_env] that takes the key of the cost-ordered dispatch (what emloco_sim_cost_ticks reads back on the device)."""
+    assert cost_ticks is None or (cost_ticks.dtype == np.uint32 and cost_ticks.shape == (osim.E,) and cost_ticks.flags.c_contiguous)
+    lib().emu_sim_set_cost_ticks(C.c_void_p(cost_ticks.ctypes.data if cost_ticks is not None else None))
     desc = model_desc(osim.arr)
     sc = getattr(osim, "sc", None)
     scd = None
@@ -92,6 +95,16 @@ def sim_step(osim, n_calls=1, expect_error=None):
 def sim_fk(osim):
     desc = model_desc(osim.arr)
     assert lib().emu_sim_fk(C.byref(desc), _p(osim.root_state), _p(osim.dof_state), _p(osim.rb_state)) == 0
+
+
+def sim_copy_rows(src, dst, ids, row_len, n_env):
+    """copy_rows_kernel (the *_indexed setters with a foreign `dev_full`) on host arrays: `dst` may be a view into a larger buffer."""
+    assert src.dtype == np.float32 and dst.dtype == np.float32 and ids.dtype == np.int32
+    assert src.flags.c_contiguous and dst.flags.c_contiguous and ids.flags.c_contiguous
+    fn = lib().emu_sim_copy_rows
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
+    fn.restype = None
+    fn(src.ctypes.data, dst.ctypes.data, ids.ctypes.data, len(ids), row_len, n_env)
 
 
 # ------------------------------------------------------------------ task kernels

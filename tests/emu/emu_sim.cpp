@@ -22,6 +22,9 @@ extern "C" void emu_sim_set_heightfield(const short *samples, int nx, int ny, fl
     g_hf = {samples, nx, ny, hs, vs, ox, oy, mv};       // mv: packed vertex moves of the slope-corrected mesh (emloco_types.h: hf_mv) or NULL
 }
 
+static unsigned *g_ticks = nullptr;   // set by emu_sim_set_cost_ticks: [n_env] words that take the key of the cost-ordered dispatch (or NULL)
+extern "C" void emu_sim_set_cost_ticks(unsigned *ticks) { g_ticks = ticks; }
+
 extern "C" int emu_sim_step(const EmlocoSimParams *prm, const EmlocoModelDesc *m, float *root_state,
                             float *dof_state, const float *pd_target, float *rb_state, float *contact_force,
                             float *dof_force, float *lambda_ws, int n_calls) {
@@ -48,7 +51,8 @@ extern "C" int emu_sim_step(const EmlocoSimParams *prm, const EmlocoModelDesc *m
     p.n_sub = prm->n_sub * n_calls;
     // EMLOCO_EMU_PARTS=n: the split launch (emloco_sim_set_split) -- n workgroups per env, all first parts first
     const char *pe = getenv("EMLOCO_EMU_PARTS");
-    const int n_parts = pe ? atoi(pe) : 1;
+    int n_parts = pe ? atoi(pe) : 1;
+    if (n_parts > p.n_sub) n_parts = p.n_sub;             // at least one substep per part, as emloco_sim_step clamps it
     std::vector<float> part_state((size_t)m->n_env * EMLOCO_PART_WORDS, 0.0f);
     std::vector<unsigned> part_flag((size_t)m->n_env, 0u);
     d.n_parts = n_parts; d.part_seq = 1; d.part_state = part_state.data(); d.part_flag = part_flag.data();
@@ -58,6 +62,7 @@ extern "C" int emu_sim_step(const EmlocoSimParams *prm, const EmlocoModelDesc *m
     unsigned err = 0u;
     d.part_spin_max = 4; d.part_poison = po ? atoi(po) : -1; d.err = &err;
     d.n_slots = m->n_env;
+    d.step_ticks = g_ticks;
     emu::launch((unsigned)(((m->n_env + EMU_ENVS_PER_WG - 1) / EMU_ENVS_PER_WG) * n_parts), 64, [&] { if (d.hf) emloco::sim_step_kernel<1>(p, d); else emloco::sim_step_kernel<0>(p, d); });
     return (int)err;
 }
@@ -74,4 +79,10 @@ extern "C" int emu_sim_fk(const EmlocoModelDesc *m, float *root_state, float *do
     d.root_state = root_state; d.dof_state = dof_state; d.rb_state = rb_state;
     emu::launch((unsigned)m->n_env, 64, [&] { emloco::sim_fk_kernel(d, nullptr, m->n_env); });
     return 0;
+}
+
+// copy_rows_kernel as the *_indexed setters launch it when `dev_full` is not the simulator's own tensor: one workgroup per list entry
+extern "C" void emu_sim_copy_rows(const float *src, float *dst, const int *ids, int n_ids, int row_len, int n_env) {
+    if (n_ids < 1) return;
+    emu::launch((unsigned)n_ids, 64, [&] { emloco::copy_rows_kernel(src, dst, ids, n_ids, row_len, n_env); });
 }
