@@ -1,9 +1,11 @@
 // emloco_types.h -- device-side argument structs shared by the kernels and the C-ABI layer.
 #pragma once
-#define EMLOCO_PART_WORDS 416   /* 24 x 12 joint registers | 16 root | 8 momentum | 64 multipliers | 32 slot map | 4 misc | pad: 16-byte granules */
+#define EMLOCO_PART_WORDS 800   /* hand-over block of an env: 200 self-tagged 16-byte granules {a, tag, b, tag} -- 128 (two per lane: joint quaternions |
+                                 * 16 root | 8 momentum | 64 multipliers | 32 slot map | 4 misc | 4 angular momentum) + 72 (joint rates, rotation vectors) */
 #include "../../include/emloco_sim.h"
 /* hand-over tag of part `part` of the launch numbered `seq`: unique whatever n_parts the launches before it used (list launches
- * and unsplit launches bump the sequence number without publishing, so a stale flag can never equal an awaited tag) */
+ * and unsplit launches bump the sequence number without publishing, so a stale granule can never carry an awaited tag).  The
+ * first launch is number 1: tags start at 4, and a zeroed block carries none */
 #define EMLOCO_PART_TAG(seq, part) ((seq) * 4u + (unsigned)(part))
 #define EMLOCO_ERR_PART_TIMEOUT 1u
 
@@ -54,13 +56,14 @@ struct EmlocoSimDev {
     const int *step_order;
     unsigned *step_ticks;
     // split launch (emloco_sim_set_split): the substeps of an env.step as n_parts workgroups per env, part p + 1 continuing
-    // from the registers / LDS part p left in part_state [n_env][EMLOCO_PART_WORDS] once part_flag[env] holds the predecessor's tag (EMLOCO_PART_TAG)
+    // from the registers / LDS part p left in part_state [n_env][EMLOCO_PART_WORDS] once every granule of it carries the predecessor's
+    // tag (EMLOCO_PART_TAG).  part_flag [n_env]: the flag word of the two-envs-per-wave kernel's hand-over (sim_pair_kernels.hip) only
     int n_parts; unsigned part_seq;
     float *part_state;
     unsigned *part_flag;
     unsigned *err;                    /* device error word (sim_capi.hip: surfaced by emloco_sim_sync and by the next step): bit 0 = a part of a
                                          split launch gave up waiting for its predecessor's hand-over; that env's step was abandoned */
     int part_spin_max;                /* bound of a part's wait for its predecessor, in 16 x 64-clock sleeps (default 1 << 22: seconds) */
-    int part_poison;                  /* test hook (emloco_sim_debug_poison_part): the first part of this env withholds its flag; -1: none */
+    int part_poison;                  /* test hook (emloco_sim_debug_poison_part): the first part of this env withholds its hand-over; -1: none */
     unsigned long long *step_start;   /* diagnostic (emloco_sim_cost_ticks): wall clock at the start of each env's workgroup, else NULL */
 };

@@ -401,6 +401,8 @@ int emloco_sim_set_split(EmlocoSim *s, int n_parts) {
     if (n_parts > 1 && !s->d_part_state.p) {
         HIPCHK(hipSetDevice(s->device));
         HIPCHK(s->d_part_state.alloc((size_t)s->n_env * EMLOCO_PART_WORDS));
+        // recycled device memory may hold the tagged granules of a destroyed simulator: no zeroed granule carries a tag (they start at 4)
+        HIPCHK(hipMemset(s->d_part_state.p, 0, sizeof(float) * (size_t)s->n_env * EMLOCO_PART_WORDS));
         HIPCHK(s->d_part_flag.alloc((size_t)s->n_env));
         HIPCHK(hipMemset(s->d_part_flag.p, 0, sizeof(unsigned) * (size_t)s->n_env));
     }
@@ -428,7 +430,7 @@ int emloco_sim_sync(EmlocoSim *s, void *stream) {
     return check_device_error(s, "emloco_sim_sync");
 }
 
-// fault injection (include/emloco_sim.h): the first part of `env` withholds its hand-over flag in the split launches that
+// fault injection (include/emloco_sim.h): the first part of `env` publishes no hand-over granules in the split launches that
 // follow (-1: back to normal) and a part's wait is bounded by `spin_max` sleeps (<= 0: the default) -- lets a test see the
 // timeout of a lost hand-over surface as EMLOCO_E_HIP instead of waiting seconds for it
 int emloco_sim_debug_poison_part(EmlocoSim *s, int env, int spin_max) {
@@ -478,7 +480,13 @@ int emloco_sim_fk_indexed(EmlocoSim *s, const int32_t *ids, int n, void *stream)
 }
 
 // internal diagnostic: the per-env durations (100 MHz ticks) the cost-ordered dispatch sorts by and, from the second call on,
-// the wall clock at which each env's workgroup started in the latest launch
+// the wall clock at which each env's workgroup started in the latest launch [2][n_env] -- in a schedule-trace build
+// (-DEMLOCO_SIM_SCHED=1) the four stamps of every workgroup instead, [4 parts][n_env][4] (sim_kernels.hip, SCHED_HANDED)
+#ifdef EMLOCO_SIM_SCHED
+#define EMLOCO_STEP_START_WORDS 16
+#else
+#define EMLOCO_STEP_START_WORDS 2
+#endif
 int emloco_sim_cost_ticks(EmlocoSim *s, unsigned *host_ticks, unsigned long long *host_start, int n) {
     if (!s || !host_ticks || n < 1 || !s->d_ticks.p) return fail(EMLOCO_E_ARG, "emloco_sim_cost_ticks: bad argument / cost order off");
     HIPCHK(hipDeviceSynchronize());
@@ -487,11 +495,11 @@ int emloco_sim_cost_ticks(EmlocoSim *s, unsigned *host_ticks, unsigned long long
     if (host_start) {
         if (!s->dev.step_start) {
             unsigned long long *p = nullptr;
-            HIPCHK(hipMalloc((void **)&p, sizeof(unsigned long long) * 2 * (size_t)s->n_env));
-            HIPCHK(hipMemset(p, 0, sizeof(unsigned long long) * 2 * (size_t)s->n_env));
+            HIPCHK(hipMalloc((void **)&p, sizeof(unsigned long long) * EMLOCO_STEP_START_WORDS * (size_t)s->n_env));
+            HIPCHK(hipMemset(p, 0, sizeof(unsigned long long) * EMLOCO_STEP_START_WORDS * (size_t)s->n_env));
             s->dev.step_start = p;
         }
-        HIPCHK(hipMemcpy(host_start, s->dev.step_start, sizeof(unsigned long long) * 2 * (size_t)s->n_env, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(host_start, s->dev.step_start, sizeof(unsigned long long) * EMLOCO_STEP_START_WORDS * (size_t)s->n_env, hipMemcpyDeviceToHost));
     }
     return EMLOCO_OK;
 }

@@ -67,43 +67,48 @@ __device__ __forceinline__ void contact_entries3(const float *sh_A, int ao, int 
     else { x0 = sh_A[tri_index(ls, r)]; x1 = sh_A[tri_index(ls, r + 1)]; x2 = sh_A[tri_index(ls, r + 2)]; }
 }
 
-// Hand-over of a split launch (emloco_sim_set_split): 16-byte granules written with `sc1` (write-through) stores and read
-// with `sc1` loads -- coherent across the XCDs' L2s and the CUs' L1s access by access (MI355X_MICROARCH.md, inter-workgroup
-// visibility: "sc1 stores and loads both sides") -- and a flag word (relaxed agent-scope atomic) that goes out once the
-// stores have completed (s_waitcnt vmcnt(0)).  Measured alternatives: agent-scope fences on every lane (__threadfence) write
-// back / invalidate whole caches per workgroup: launch 0.54 -> 0.68 ms; one 4-byte agent atomic per word: as fast as this,
-// but every word is a fabric write of its own (HBM counters 46 -> 124 MB per launch).
+// Hand-over of a split launch (emloco_sim_set_split): self-tagged 16-byte granules {a, tag, b, tag} -- each 8-byte half carries
+// one payload word and the tag of the publishing part (EMLOCO_PART_TAG) -- written with `sc1` (write-through) stores and read
+// with `sc1` loads, coherent across the XCDs' L2s and the CUs' L1s access by access (MI355X_MICROARCH.md, inter-workgroup
+// visibility: "sc1 stores and loads both sides"; hand-off by data-tagged granules).  The producer stores and leaves: no drain,
+// no flag.  The consumer loads all its granules in one burst and takes them when every half carries the awaited tag -- one
+// memory round trip where the flag form took two (poll the flag, then load) behind the producer's s_waitcnt vmcnt(0).  Only the
+// 8-byte halves are relied on to arrive whole (observed on gfx950, not an architectural guarantee), hence a tag in each.
+// Layout of an env's block (EMLOCO_PART_WORDS), one lane address for every instruction:
+//   granules [0, 128)    lane + 64 k, k = 0, 1: every lane -- a body lane's joint quaternion; lanes NB .. NB + 31 one 4-word
+//                        group of LDS state each (root 4 | momentum 2 | multipliers 16 | slot map 8 | work | angular momentum)
+//   granules [128, 200)  128 + lane + NB k, k = 0 .. 2: body lanes only -- joint rates | rotation vector
+// Measured alternatives to sc1 accesses: agent-scope fences on every lane (__threadfence) write back / invalidate whole caches
+// per workgroup: launch 0.54 -> 0.68 ms; one 4-byte agent atomic per word: every word is a fabric write of its own (HBM
+// counters 46 -> 124 MB per launch).
 typedef float part_f4 __attribute__((ext_vector_type(4)));
+#define PART_G1 (64 * 4)              /* words from a lane's first granule to its second */
+#define PART_GB (128 * 4)             /* first word of the body lanes' region */
+static_assert(EMLOCO_PART_WORDS >= PART_GB + 3 * EMLOCO_NB * 4, "hand-over block too small for its layout");
 #ifdef EMLOCO_EMU
 __device__ __forceinline__ void part_st16(float *p, float a, float b, float c, float d) { p[0] = a; p[1] = b; p[2] = c; p[3] = d; }
-__device__ __forceinline__ void part_ld16(const float *p, float *v) { for (int k = 0; k < 4; ++k) v[k] = p[k]; }
-__device__ __forceinline__ void part_ld48(const float *p, float *v) { for (int g = 0; g < 3; ++g) for (int k = 0; k < 4; ++k) v[4 * g + k] = p[g * 4 * EMLOCO_NB + k]; }
-__device__ __forceinline__ void part_stores_done() {}
-__device__ __forceinline__ void part_flag_set(unsigned *f, unsigned v) { *f = v; }
-__device__ __forceinline__ unsigned part_flag_get(const unsigned *f) { return *f; }
+__device__ __forceinline__ void part_ld80(const float *pa, const float *pb, float *v) {
+    for (int k = 0; k < 4; ++k) { v[k] = pa[k]; v[4 + k] = pa[PART_G1 + k]; }
+    for (int g = 0; g < 3; ++g) for (int k = 0; k < 4; ++k) v[8 + 4 * g + k] = pb[g * 4 * EMLOCO_NB + k];
+}
 __device__ __forceinline__ void part_err_raise(unsigned *e, unsigned bit) { if (e) *e |= bit; }
 #else
 __device__ __forceinline__ void part_st16(float *p, float a, float b, float c, float d) {
     const part_f4 v = {a, b, c, d};
     asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(p), "v"(v) : "memory");
 }
-__device__ __forceinline__ void part_ld16(const float *p, float *v) {
-    part_f4 a;
-    asm volatile("global_load_dwordx4 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(a) : "v"(p) : "memory");
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-}
-__device__ __forceinline__ void part_ld48(const float *p, float *v) {
-    part_f4 a, b, c;
-    static_assert(EMLOCO_NB * 16 == 384, "granule-major hand-over: a lane's three granules are 24 x 16 bytes apart");
-    asm volatile("global_load_dwordx4 %0, %3, off sc1\n\tglobal_load_dwordx4 %1, %3, off offset:384 sc1\n\t"
-                 "global_load_dwordx4 %2, %3, off offset:768 sc1\n\ts_waitcnt vmcnt(0)"
-                 : "=&v"(a), "=&v"(b), "=&v"(c) : "v"(p) : "memory");
+// a lane's two granules at pa and its three at pb (lanes without a body hand in pa again: loaded, never looked at)
+__device__ __forceinline__ void part_ld80(const float *pa, const float *pb, float *v) {
+    part_f4 a, b, c, e, f;
+    static_assert(PART_G1 * 4 == 1024 && EMLOCO_NB * 16 == 384, "granule-major hand-over: the offsets of a lane's granules");
+    asm volatile("global_load_dwordx4 %0, %5, off sc1\n\tglobal_load_dwordx4 %1, %5, off offset:1024 sc1\n\t"
+                 "global_load_dwordx4 %2, %6, off sc1\n\tglobal_load_dwordx4 %3, %6, off offset:384 sc1\n\t"
+                 "global_load_dwordx4 %4, %6, off offset:768 sc1\n\ts_waitcnt vmcnt(0)"
+                 : "=&v"(a), "=&v"(b), "=&v"(c), "=&v"(e), "=&v"(f) : "v"(pa), "v"(pb) : "memory");
     v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-    v[8] = c.x; v[9] = c.y; v[10] = c.z; v[11] = c.w;
+    v[8] = c.x; v[9] = c.y; v[10] = c.z; v[11] = c.w; v[12] = e.x; v[13] = e.y; v[14] = e.z; v[15] = e.w;
+    v[16] = f.x; v[17] = f.y; v[18] = f.z; v[19] = f.w;
 }
-__device__ __forceinline__ void part_stores_done() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ void part_flag_set(unsigned *f, unsigned v) { __hip_atomic_store(f, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ unsigned part_flag_get(const unsigned *f) { return __hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void part_err_raise(unsigned *e, unsigned bit) { if (e) __hip_atomic_fetch_or(e, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
 #endif
 
@@ -138,6 +143,15 @@ __device__ __forceinline__ void ld4(const float *base, int off, float *v) {
 #define PSTAMP(i) do { if (d.prof && env == 0 && lane == 0) d.prof[sub * 16 + (i)] = (long long)wall_clock64(); FRESH_LANE(); } while (0)
 #else
 #define PSTAMP(i) FRESH_LANE()
+#endif
+
+// Schedule trace (diagnostic build -DEMLOCO_SIM_SCHED=1, tools/exp/sim_sched.py): with the start stamps switched on
+// (emloco_sim_cost_ticks) every workgroup leaves four words in step_start [n_parts][n_env][4] -- wall clock at its first
+// instruction, once its predecessor's hand-over is in, at its last instruction, and part | dispatch slot << 8.
+#ifdef EMLOCO_SIM_SCHED
+#define SCHED_HANDED() do { if (d.step_start && threadIdx.x == 0) d.step_start[((size_t)part * d.n_env + env) * 4 + 1] = (unsigned long long)wall_clock64(); } while (0)
+#else
+#define SCHED_HANDED() do { } while (0)
 #endif
 
 // Height-field ground under the world point (cx, cy): height zt of the cell triangle's plane there and its unit normal.
@@ -377,7 +391,12 @@ __device__ __forceinline__ void sim_step_env(const EmlocoSimParams &prm, const E
     float *dofs_env = d.dof_state + (size_t)env * NDOF * 2;
     float *cf_env = d.contact_force + (size_t)env * NB * 3;
     float *lws_env = d.lambda_ws + (size_t)env * MAXCAND * 3;
-    if (lane < NB) sh_pd[lane] = topo[EMLOCO_TOPO_PDPACK + lane];
+    // Part prologue: what does not depend on the predecessor is requested BEFORE the hand-over is polled -- the topology word and
+    // the model record of the first substep's phase 1 (joint offset | mass) -- and is in flight during the wait; the topology
+    // word reaches LDS behind it.
+    const int pd_w = lane < NB ? topo[EMLOCO_TOPO_PDPACK + lane] : 0;
+    float jm[4];                                     // joint offset xyz | body mass
+    ld4(mdl, o_dyn, jm);
     sh_slot[lane] = 255; sh_slot[lane + 64] = 255;
 
     // ---------------------------------------------------------------- state -> registers
@@ -407,38 +426,45 @@ __device__ __forceinline__ void sim_step_env(const EmlocoSimParams &prm, const E
             for (int k = 0; k < 4; ++k) sh_root[3 + k] = q0[k];
         }
     } else {
-        // The predecessor has published its state.  Parts are workgroups of one launch at ascending indices, so in dispatch
-        // order the flag is set long before; the wait is bounded all the same (a lost flag must not hang the device) and a
-        // wait that runs out is an ERROR, not a reason to go on from stale hand-over state: the workgroup raises the device
-        // error word (emloco_sim_sync / the next step return EMLOCO_E_HIP) and abandons this env's step.
-        if (lane == 0) {
-            int spins = 0;
-            const unsigned want = EMLOCO_PART_TAG(d.part_seq, part - 1);
-            while (part_flag_get(d.part_flag + env) != want && ++spins < d.part_spin_max) __builtin_amdgcn_s_sleep(16);
-            sh_V0[0] = spins < d.part_spin_max ? 1.0f : 0.0f;
-            if (spins >= d.part_spin_max) part_err_raise(d.err, EMLOCO_ERR_PART_TIMEOUT);
+        // The predecessor publishes its state as self-tagged granules (see part_ld80).  Parts are workgroups of one launch at
+        // ascending indices, so in dispatch order the granules are there long before and the first burst takes them; the wait
+        // is bounded all the same (a lost hand-over must not hang the device) and a wait that runs out is an ERROR, not a
+        // reason to go on from stale hand-over state: the workgroup raises the device error word (emloco_sim_sync / the next
+        // step return EMLOCO_E_HIP) and abandons this env's step.  Every lane loads its own granules and checks their tags;
+        // the ballot makes the verdict wave-uniform, so no lane leaves the loop on its own.
+        const unsigned want = EMLOCO_PART_TAG(d.part_seq, part - 1);
+        const float *pa = pst + lane * 4, *pb = lane < NB ? pst + PART_GB + lane * 4 : pa;
+        float v[20];
+        int spins = 0;
+        bool bad;
+        for (;;) {
+            part_ld80(pa, pb, v);
+            bool miss = __float_as_uint(v[1]) != want || __float_as_uint(v[3]) != want || __float_as_uint(v[5]) != want || __float_as_uint(v[7]) != want;
+            if (lane < NB)
+                for (int k = 9; k < 20; k += 2) miss = miss || __float_as_uint(v[k]) != want;
+            bad = __ballot(miss) != 0ull;
+            if (!bad || ++spins >= d.part_spin_max) break;
+            __builtin_amdgcn_s_sleep(16);
         }
-        __syncthreads();
-        if (sh_V0[0] == 0.0f) { work = -1; return; }
-        __syncthreads();
-        if ((lane < NB)) {          // granules lane, 24 + lane, 48 + lane (granule-major: the lanes of one store / load instruction
-            float v[12];        // touch one contiguous 384-byte run): joint quaternion | rates, e_0 | e_1, e_2
-            part_ld48(pst + lane * 4, v);
-            for (int k = 0; k < 4; ++k) qj[k] = v[k];
-            for (int k = 0; k < 3; ++k) wj[k] = v[4 + k];
-            edof[0] = v[7]; edof[1] = v[8]; edof[2] = v[9];
-        } else if (lane < NB + 32) {   // one granule of LDS state per lane: root (4) | momentum (2) | multipliers (16) | slot map (8) | misc | angular momentum
+        if (bad) {
+            if (lane == 0) part_err_raise(d.err, EMLOCO_ERR_PART_TIMEOUT);
+            work = -1;
+            return;
+        }
+        if ((lane < NB)) {          // joint quaternion | rates | rotation vector
+            qj[0] = v[0]; qj[1] = v[2]; qj[2] = v[4]; qj[3] = v[6];
+            wj[0] = v[8]; wj[1] = v[10]; wj[2] = v[12];
+            edof[0] = v[14]; edof[1] = v[16]; edof[2] = v[18];
+        } else if (lane < NB + 32) {   // one 4-word group of LDS state per lane: root (4) | momentum (2) | multipliers (16) | slot map (8) | work | angular momentum
             const int g = lane - NB;
-            float v[4];
-            part_ld16(pst + NB * 12 + 4 * g, v);
             float *dst = g < 4 ? sh_root + 4 * g : g < 6 ? sh_P + 4 * (g - 4) : g < 22 ? sh_lam + 4 * (g - 6) : g < 30 ? (float *)sh_slot + 4 * (g - 22) : sh_L;
-            if (g != 30) for (int k = 0; k < 4; ++k) dst[k] = v[k];
-            else sh_V0[0] = v[0];                               // the work counter, picked up below
+            if (g != 30) { dst[0] = v[0]; dst[1] = v[2]; dst[2] = v[4]; dst[3] = v[6]; }
         }
-        __syncthreads();
-        work = __float_as_int(sh_V0[0]);
+        work = __shfl(__float_as_int(v[0]), NB + 30);          // the work counter so far
     }
+    if (lane < NB) sh_pd[lane] = pd_w;
     __syncthreads();
+    SCHED_HANDED();
 
     const float h = prm.h;
     // registers that persist across phases (lane = body)
@@ -462,10 +488,8 @@ __device__ __forceinline__ void sim_step_env(const EmlocoSimParams &prm, const E
             for (int k = 0; k < 9; ++k) sh_R[0][k] = R[k];
             for (int k = 0; k < 6; ++k) { sh_V[0][k] = sh_root[7 + k]; sh_Aacc[0][k] = 0.0f; }
         }
-        // joint offsets: re-read per substep (L2 hit) instead of held for the launch, but ahead of the level loop so that the
-        // load's latency is not paid inside every level
-        float jm[4];                                     // joint offset xyz | body mass
-        ld4(mdl, o_dyn, jm);
+        // joint offsets | mass (jm): re-read per substep (L2 hit) instead of held for the launch -- requested ahead of the hand-over
+        // (the prologue) or at the end of the substep before, so that the round trip is not paid here
         const float joff[3] = {jm[0], jm[1], jm[2]};
         __syncthreads();
         const int pd1 = sh_pd[lane < NB ? lane : 0];
@@ -662,6 +686,10 @@ __device__ __forceinline__ void sim_step_env(const EmlocoSimParams &prm, const E
             }
         }
         if (final_pass) break;
+        // drive gains and targets of phase 2: requested here, a phase ahead, so that the limb-limb phase covers the round trip
+        float drv[3][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}}, tgv[3] = {0, 0, 0};    // kp, kd, armature, effort limit | target of each dof
+        if ((lane < NB))
+            for (int k = 0; k < 3; ++k) { ld4(mdl, o_drv + 4 * k, drv[k]); tgv[k] = tgt_env[jdof + k]; }
 
         // ============================================================ 1b. limb-limb contacts (self-collision, penalty)
         // lane = body: world collision capsule -> LDS; lane = pair (4 rounds of 64): closest points, spring-damper force;
@@ -784,10 +812,9 @@ __device__ __forceinline__ void sim_step_env(const EmlocoSimParams &prm, const E
         if ((lane < NB)) {
             // implicit PD drive: tau~ = kp (q* - q) - (kd + h kp) qd, joint-space diagonal d = armature + h kd + h^2 kp
             for (int k = 0; k < 3; ++k) {
-                float dr[4];                                     // kp, kd, armature, effort limit of this dof
-                ld4(mdl, o_drv + 4 * k, dr);
+                const float *dr = drv[k];                        // kp, kd, armature, effort limit of this dof
                 const float kp = lane >= 1 ? dr[0] : 0.0f, kd = lane >= 1 ? dr[1] : 0.0f;
-                const float arm = lane >= 1 ? dr[2] : 0.0f, tgt = lane >= 1 ? tgt_env[jdof + k] : 0.0f;
+                const float arm = lane >= 1 ? dr[2] : 0.0f, tgt = lane >= 1 ? tgv[k] : 0.0f;
                 const float e = tgt - edof[k];
                 if (prm.drive_mode == 1) {       // effort drive (gymapi.DOF_MODE_EFFORT): the given torque within the limit, nothing implicit
                     const float eff = lane >= 1 ? dr[3] : 0.0f;
@@ -828,6 +855,7 @@ __device__ __forceinline__ void sim_step_env(const EmlocoSimParams &prm, const E
         // tau~ - (h kd + h^2 kp) qdd; where that exceeds the effort limit the drive becomes a constant torque at the limit
         // (no implicit terms) and the env repeats the two phases once (rare: wave-uniform branch per env).
         float pA[6];
+        int cand_w[2] = {0, 0};              // topology words of this lane's two ground-contact candidates (phase 5)
         for (int pass = 0; pass < 2; ++pass) {
         // ============================================================ 2b. inertia about O and bias force of every body (lane = body)
         // They stay in this lane's registers until its level of the up pass below takes them over in place -- no trip through
@@ -968,6 +996,12 @@ __device__ __forceinline__ void sim_step_env(const EmlocoSimParams &prm, const E
 
         PSTAMP(3);
         // ============================================================ 4. down pass: joint accelerations, v_free
+        // drive gains and limits for the effort check behind the down pass: requested ahead of it (the level loop covers the round trip)
+        float drc[3][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+        if (pass == 0 && (lane < NB) && lane >= 1)
+            for (int k = 0; k < 3; ++k) ld4(mdl, o_drv + 4 * k, drc[k]);
+        // ... and the candidates' topology words for phase 5 (their geometry records hang on them: two dependent round trips)
+        for (int s = 0; s < 2; ++s) cand_w[s] = lane + 64 * s < d.n_cand ? topo[EMLOCO_TOPO_CAND + lane + 64 * s] : 0;
         const int pd4 = sh_pd[lane < NB ? lane : 0];
         for (int lev = 1; lev <= d.max_depth; ++lev) {
             if ((lane < NB) && PD_DEPTH(pd4) == lev) {
@@ -999,8 +1033,7 @@ __device__ __forceinline__ void sim_step_env(const EmlocoSimParams &prm, const E
             bool over = false;
             if ((lane < NB) && lane >= 1)
                 for (int k = 0; k < 3; ++k) {
-                    float dr[4];
-                    ld4(mdl, o_drv + 4 * k, dr);
+                    const float *dr = drc[k];
                     const float kp = dr[0], kd = dr[1], eff = dr[3];
                     const float ti = tau[k] - (h * kd + h * h * kp) * qdd[k];
                     if (sat[k] == 0 && fabsf(ti) > eff) { sat[k] = ti > 0.0f ? 1 : -1; tau[k] = ti > 0.0f ? eff : -eff; dd[k] = dr[2]; over = true; }
@@ -1026,7 +1059,7 @@ __device__ __forceinline__ void sim_step_env(const EmlocoSimParams &prm, const E
             const int c = lane + 64 * s;
             cb[s] = -1; act[s] = false; cdist[s] = 0.0f;
             if (c < d.n_cand) {
-                const int cp = topo[EMLOCO_TOPO_CAND + c], body = cp & 0xff, k = (cp >> 8) & 0xff, gt = cp >> 16;
+                const int cp = cand_w[s], body = cp & 0xff, k = (cp >> 8) & 0xff, gt = cp >> 16;
                 float ga[4], gb[4], clp[3];                      // geom a xyz, radius | geom b xyz
                 ld4(mdl, EMLOCO_MB_GEO + body * 8, ga); ld4(mdl, EMLOCO_MB_GEO + body * 8 + 4, gb);
                 const float crad = ga[3];
@@ -1616,23 +1649,31 @@ __device__ __forceinline__ void sim_step_env(const EmlocoSimParams &prm, const E
         }
         __syncthreads();
         PSTAMP(10);
+        // the next substep's (or the final pass's) joint offsets | mass.  Unconditional on purpose: behind a condition the compiler
+        // would have to carry this substep's copy through the whole loop body; a part of one substep drops the request
+        ld4(mdl, o_dyn, jm);
     }
 
-    if (part < n_parts - 1) {         // hand over to the next part (see above) and publish
-        if ((lane < NB)) {
-            float *ps = pst + lane * 4;
-            part_st16(ps, qj[0], qj[1], qj[2], qj[3]);
-            part_st16(ps + 4 * NB, wj[0], wj[1], wj[2], edof[0]);
-            part_st16(ps + 8 * NB, edof[1], edof[2], 0.0f, 0.0f);
-        } else if (lane < NB + 32) {
+    if (part < n_parts - 1) {         // hand over to the next part (see part_ld80): store the tagged granules and leave
+        if (part == 0 && env == d.part_poison) return;             // test hook: this env's first part publishes nothing
+        const float tg = __uint_as_float(EMLOCO_PART_TAG(d.part_seq, part));
+        float w[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if ((lane < NB)) { w[0] = qj[0]; w[1] = qj[1]; w[2] = qj[2]; w[3] = qj[3]; }
+        else if (lane < NB + 32) {
             const int g = lane - NB;
             const float *src = g < 4 ? sh_root + 4 * g : g < 6 ? sh_P + 4 * (g - 4) : g < 22 ? sh_lam + 4 * (g - 6) : g < 30 ? (const float *)sh_slot + 4 * (g - 22) : sh_L;
-            if (g != 30) part_st16(pst + NB * 12 + 4 * g, src[0], src[1], src[2], src[3]);
-            else part_st16(pst + NB * 12 + 4 * g, __int_as_float(work), 0.0f, 0.0f, 0.0f);
+            if (g != 30) { w[0] = src[0]; w[1] = src[1]; w[2] = src[2]; w[3] = src[3]; }
+            else w[0] = __int_as_float(work);
         }
-        part_stores_done();           // the stores above have completed ...
-        __syncthreads();
-        if (lane == 0 && !(part == 0 && env == d.part_poison)) part_flag_set(d.part_flag + env, EMLOCO_PART_TAG(d.part_seq, part));      // ... before the flag goes out
+        float *pa = pst + lane * 4;
+        part_st16(pa, w[0], tg, w[1], tg);
+        part_st16(pa + PART_G1, w[2], tg, w[3], tg);
+        if ((lane < NB)) {
+            float *pb = pst + PART_GB + lane * 4;
+            part_st16(pb, wj[0], tg, wj[1], tg);
+            part_st16(pb + 4 * NB, wj[2], tg, edof[0], tg);
+            part_st16(pb + 8 * NB, edof[1], tg, edof[2], tg);
+        }
         return;
     }
     // ---------------------------------------------------------------- write back (state after the final kinematics pass)
@@ -1693,15 +1734,28 @@ sim_step_kernel(EmlocoSimParams prm, EmlocoSimDev d) {
 #else
         d.step_ticks[env] = (unsigned)work;
 #endif
+#ifndef EMLOCO_SIM_SCHED
         if (d.step_start) { d.step_start[env] = (unsigned long long)t0; d.step_start[d.n_env + env] = (unsigned long long)wall_clock64(); }
+#endif
     }
+#ifdef EMLOCO_SIM_SCHED
+    if (d.step_start && threadIdx.x == 0) {
+        unsigned long long *ss = d.step_start + ((size_t)part * d.n_env + env) * 4;
+        ss[0] = (unsigned long long)t0; ss[2] = (unsigned long long)wall_clock64(); ss[3] = (unsigned long long)(part | slot << 8);
+    }
+#endif
 }
 
 // Dispatch order of the next full launch: env ids sorted by the contact work of their last step (sum over its substeps of
 // 10 + number of contacts where there were any: the contact phases are ~45 % of a substep and grow with the contact count),
 // most first (counting sort, one 1024-thread workgroup).  The measured duration of the last step is the worse key: it is
-// dominated by what the env's wave shared its SIMD and CU with (correlation between consecutive steps 0.2).  Workgroups are handed to the CUs in index order and the launch is two
-// resident rounds of waves (4096 envs on 256 CUs x 8), so its length is set by what the LAST workgroups cost: with the
+// dominated by what the env's wave shared its SIMD and CU with (correlation between consecutive steps 0.2).  Workgroups are
+// handed to the CUs in index order.  The split launch (emloco_sim_set_split, 4 parts) is 16 384 one-wave workgroups for 4096
+// envs -- all first parts in this order, then all second parts in the same order, and so on -- on 3072 wave slots (256 CUs x
+// 12): the first 3072 first parts start at once, everything behind them takes a slot as one frees up.  A later part finds
+// its predecessor's hand-over complete when it starts (it queued ~19 us for its slot, median; tools/exp/sim_sched.py,
+// profiles/r09_sim_serial_path.txt): the launch is bound by the slots, 82 % of the slot-time is spent running and 15 % is the
+// fill and drain at its two ends.  Its length is therefore set by what the LAST workgroups of each part cost: with the
 // expensive envs (many contacts) first and the cheap ones (airborne) last, the slots that free up late receive short work.
 // The order within a bucket is whatever the LDS atomics give -- envs are independent, results do not depend on it.
 __global__ void __launch_bounds__(1024)

@@ -183,7 +183,7 @@ int emloco_sim_set_cost_order(EmlocoSim *sim, int on);
 /* gym.fetch_results(sim, True) -- base_task.py:258: host waits for the stream */
 int emloco_sim_sync(EmlocoSim *sim, void *stream);
 /* Fault injection for the split launch's hand-over (no counterpart in the gym API; the product never calls it).  The first
- * part of `env` withholds its hand-over flag in the split launches that follow (env = -1: back to normal), and a later part's
+ * part of `env` withholds its hand-over (it publishes nothing) in the split launches that follow (env = -1: back to normal), and a later part's
  * wait is bounded by `spin_max` sleeps (<= 0: the default, 1 << 22).  A wait that runs out raises the device error word that
  * emloco_sim_sync / the next emloco_sim_step return as EMLOCO_E_HIP: this call lets a test see that path in milliseconds
  * instead of seconds (tests/test_gpu_sim.py).  Costs the kernel one scalar compare per part. */
@@ -195,7 +195,10 @@ int emloco_sim_debug_poison_part(EmlocoSim *sim, int env, int spin_max);
  *                           emloco_task.h calls it (the two translation units link through this symbol)
  *   emloco_sim_cost_ticks   per-env durations (100 MHz ticks) of the latest step, the key of the cost-ordered dispatch
  *                           (emloco_sim_set_cost_order must be on) and, from the second call on, each workgroup's start stamps
- *                           (host_start: 2 n_envs entries, or NULL)
+ *                           (host_start: 2 n_envs entries, or NULL).  A library built with -DEMLOCO_SIM_SCHED=1 (the schedule
+ *                           trace of tools/exp/sim_sched.py) copies 16 n_envs entries instead -- [4 parts][n_env][first instruction,
+ *                           hand-over complete, last instruction, part | slot << 8] -- so a caller that may meet such a build
+ *                           passes 16 n_envs entries
  *   emloco_sim_profile      wall-clock stamps of env 0, 16 per substep (kernels built with -DEMLOCO_SIM_PROFILE; without it the
  *                           buffer stays zero).  The first call allocates the stamp buffer and returns. */
 int emloco_sim_fk_indexed(EmlocoSim *sim, const int32_t *dev_env_ids, int n, void *stream);

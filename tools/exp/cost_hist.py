@@ -18,9 +18,12 @@ for k in range(150):
 torch.cuda.synchronize()
 lib = task.sim.native.lib
 buf = (C.c_uint * E)()
-st = (C.c_ulonglong * (2 * E))()
+st = (C.c_ulonglong * (16 * E))()      # 2 E entries are used; a schedule-trace build (-DEMLOCO_SIM_SCHED=1) copies 16 E (include/emloco_sim.h)
+st[16 * E - 1] = 0xFFFFFFFFFFFFFFFF
 lib.emloco_sim_cost_ticks.argtypes = [C.c_void_p, C.POINTER(C.c_uint), C.POINTER(C.c_ulonglong), C.c_int]
 assert lib.emloco_sim_cost_ticks(task.sim.native._h, buf, st, E) == 0      # allocates the start stamps
+if st[16 * E - 1] != 0xFFFFFFFFFFFFFFFF:
+    raise SystemExit("this library is a schedule-trace build (-DEMLOCO_SIM_SCHED=1): its stamps have another layout, use tools/exp/sim_sched.py")
 prev = np.array(buf[:], dtype=np.float64)
 for k in range(3):
     env.reset_done(); env.step(pool[k % 64])
