@@ -66,6 +66,7 @@ class Humanoid(BaseTask):
         self._has_limb_weight_obs = e.get("has_weight_obs", False)
         self._has_limb_weight_obs_disc = e.get("has_weight_obs_disc", False)
         self.has_shape_variation = e.get("has_shape_variation", False)
+        self.shape_resampling_interval = int(e.get("shape_resampling_interval", 100))     # humanoid.py:246-247; 0: never (learning/pre_epoch.py)
         self._has_self_collision = e.get("has_self_collision", False)
         self._has_jt_limit = e.get("has_jt_limit", True)
         self._has_dof_subset = e.get("has_dof_subset", False)

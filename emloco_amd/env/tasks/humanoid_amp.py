@@ -73,14 +73,47 @@ class HumanoidAMP(Humanoid):
             # an AMASS pickle in the reference's format (convert_amass_isaac.py:309-317): one clip per env on that env's skeleton
             # (humanoid_amp.py:256-271); the height fix through the SMPL mesh is replaced by the lowest-collision-point fix at reset
             from ...utils.motion_lib_smpl import MotionLib
+            # motion_build (run.py --motion_build): "host" builds each clip with clip_cache in float64, "device" with emloco_motion_build
             self._motion_lib = MotionLib(motion_file=motion_file, key_body_ids=self._key_body_ids.cpu().numpy(), device=self.device,
-                                         fix_height=False, masterfoot_conifg=None, min_length=self._min_motion_len if hasattr(self, "_min_motion_len") else -1)
+                                         fix_height=False, masterfoot_conifg=None, min_length=self._min_motion_len if hasattr(self, "_min_motion_len") else -1,
+                                         build=self.cfg["env"].get("motion_build", "host") or "host")
             self._motion_lib.load_motions(skeleton_trees=[a.model for a in self.humanoid_assets], gender_betas=self.humanoid_betas.cpu(),
                                           limb_weights=None, random_sample=True)
             return
         self._motion_lib = MotionLibSynthetic(self.humanoid_assets[0].model, self._key_body_ids.cpu().numpy(),
                                               self.device, num_motions=int(self.cfg["env"].get("num_motions", 64)),
                                               seed=int(self.cfg["env"].get("motion_seed", 0)))
+        return
+
+    def resample_motions(self):                                   # humanoid_amp.py:114-124
+        """Draw a new clip per env from the pickle (`load_motions` with the skeletons and betas of construction, random_sample) in the
+        library's build mode.  The streams of the rollout loop are joined first, so that no reset kernel reads a cache that is being
+        rewritten; everything that reads the cache afterwards -- resets, `fetch_amp_obs_demo` -- sees the new draw.  None with the
+        synthetic library, which is built once; otherwise what the schedule logs."""
+        import time
+        ml = self._motion_lib
+        if isinstance(ml, MotionLibSynthetic):
+            return None
+        t0 = time.time()
+        cuda = torch.device(self.device).type == "cuda"
+        if hasattr(self, "wait_obs"):
+            self.wait_obs()
+        if hasattr(self, "wait_reset"):
+            self.wait_reset()
+        if cuda:
+            torch.cuda.synchronize(self.device)
+        grown = ml.num_reallocations
+        ml.load_motions(skeleton_trees=[a.model for a in self.humanoid_assets], gender_betas=self.humanoid_betas.cpu(), limb_weights=None,
+                        random_sample=True)
+        moved = ml.build == "host" or ml.num_reallocations != grown        # the host build leaves new tensors every time
+        self._motion_cache_rebuilt(moved)
+        if cuda:
+            torch.cuda.synchronize(self.device)
+        return dict(distinct_clips=len(set(ml._curr_motion_ids.tolist())), num_motions=ml.num_motions(), seconds=time.time() - t0,
+                    build=ml.build, reallocated=moved)
+
+    def _motion_cache_rebuilt(self, moved):
+        """hook: the motion library's cache holds a new draw; `moved`: its arrays live at new addresses"""
         return
 
     def _build_lowest_point_tables(self):

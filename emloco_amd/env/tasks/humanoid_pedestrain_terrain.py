@@ -178,6 +178,23 @@ class HumanoidPedestrianTerrain(humanoid_traj.HumanoidTraj):
             p(self.progress_buf), p(self.reset_buf), p(self._terminate_buf), p(self.waypoint_traj), p(self.init_pose), p(self.init_vel),
             p(self._amp_obs_buf), p(self._reset_motion_ids), p(self._reset_motion_times), p(self._reset_ground_h))
 
+    def _motion_cache_rebuilt(self, moved):
+        """After `resample_motions`: the structures that hold the motion cache by address -- `_reset_bufs` and its copy without the AMP
+        history, `_reset_bufs_noamp` -- take the new addresses in place (their other buffers, the inversion flags among them, are those
+        of the games in progress and stay), and the pool of pre-drawn episodes is dropped: its entries were sampled from the old
+        clips, and a fresh pool (tags 0) sends the next reset down the direct path."""
+        if moved:
+            ml = self._motion_lib
+            for name in ("_reset_bufs", "_reset_bufs_noamp"):
+                b = getattr(self, name, None)
+                if b is not None:
+                    for field, t in (("gts", ml.gts), ("grs", ml.grs), ("lrs", ml.lrs), ("gvs", ml.gvs), ("gavs", ml.gavs), ("dvs", ml.dvs),
+                                     ("motion_len", ml._motion_lengths), ("motion_dt", ml._motion_dt),
+                                     ("motion_nframes", ml._motion_num_frames), ("motion_start", ml.length_starts)):
+                        setattr(b, field, t.data_ptr())
+                    b.n_motions = ml.num_motions()
+        self._pool = None
+
     def _fused_reset_envs(self, env_ids, rnd=None):
         """reset(env_ids) as three kernel launches + the indexed observation launch (replaces ~1 100 torch launches)."""
         import ctypes as C

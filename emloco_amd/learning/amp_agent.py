@@ -839,7 +839,12 @@ class AMPAgent:
         if amp_obs.shape[0] > 0:
             self._amp_replay_buffer.store({"amp_obs": amp_obs[:self._amp_replay_buffer.get_buffer_size()]})
 
+    def pre_epoch(self, epoch_num):                               # amp_continuous.py:203-210
+        from .pre_epoch import pre_epoch
+        return pre_epoch(self.task, epoch_num)
+
     def train_epoch(self):
+        self.pre_epoch(self.epoch_num + 1)                        # the epoch that begins, counted from 1 as the reference counts them
         t0 = time.time()
         batch = self.play_steps()
         torch.cuda.synchronize(self.device)

@@ -605,7 +605,12 @@ class LocoValRollout:
             self.vnet_scheduler.step()
         self.epoch_num += 1
 
+    def pre_epoch(self, epoch_num):                               # amp_continuous.py:203-210: the value agent inherits it
+        from .pre_epoch import pre_epoch
+        return pre_epoch(self.task, epoch_num)
+
     def play_steps(self):
+        self.pre_epoch(self.epoch_num + 1)                        # the epoch that begins, counted from 1 as the reference counts them
         for n in range(self.horizon_length):
             self.step_once()
         self.end_epoch()

@@ -292,6 +292,7 @@ class LocoValTrainee:
     def run_epoch(self):
         a = self.agent
         t0 = time.time()
+        a.pre_epoch(a.epoch_num + 1)                     # the motion clips are redrawn on the reference's schedule (learning/pre_epoch.py)
         for _ in range(a.horizon_length):
             a.step_once()
         a.end_epoch()

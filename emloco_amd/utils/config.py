@@ -27,6 +27,9 @@ def get_args(argv=None):
         {"name": "--cfg_env", "type": str, "default": DEFAULT_CFG_ENV},
         {"name": "--cfg_train", "type": str, "default": ""},
         {"name": "--motion_file", "type": str, "default": "synthetic"},
+        {"name": "--motion_build", "type": str, "default": "host", "choices": ["host", "device"],
+         "help": "how the clips of a --motion_file pickle are built, at the first load and at every resample: on the host in float64 "
+                 "(clip_cache) or on the device in float32 (emloco_motion_build)"},
         {"name": "--network_path", "type": str, "default": "output/"},
         {"name": "--exp_name", "type": str, "default": "emloco"},
         {"name": "--epoch", "type": int, "default": 0},
@@ -78,6 +81,7 @@ def load_cfg(args):
     cfg["name"] = args.task
     cfg["headless"] = args.headless
     cfg["env"]["motion_file"] = args.motion_file
+    cfg["env"]["motion_build"] = getattr(args, "motion_build", "host")
     if getattr(args, "pred_traj_file", ""):
         cfg["env"]["pred_traj_data"] = args.pred_traj_file
     if getattr(args, "real_traj_file", ""):

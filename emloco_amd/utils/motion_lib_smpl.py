@@ -82,14 +82,35 @@ def clip_cache(clip, local_translation, parents):
     return dict(gts=gp, grs=gq, lrs=lq, gvs=gv, gavs=gav, dvs=dv, fps=fps)
 
 
+def gaussian_taps(sigma=2.0, radius=8):
+    """The weights scipy's gaussian_filter1d(sigma, truncate=4) applies, computed in float64 and normalised, as float32: what
+    emloco_motion_build (include/emloco_task.h) takes as its filter."""
+    x = np.arange(-radius, radius + 1, dtype=np.float64)
+    w = np.exp(-0.5 * (x / sigma) ** 2)
+    return (w / w.sum()).astype(np.float32)
+
+
+BUILD_MODES = ("host", "device")
+FRAME_KEYS = ("gts", "grs", "lrs", "gvs", "gavs", "dvs")
+_FRAME_SHAPES = dict(gts=(24, 3), grs=(24, 4), lrs=(24, 4), gvs=(24, 3), gavs=(24, 3), dvs=(69,), _motion_aa=(72,), _quat_in=(24, 4), _trans_in=(3,))
+CAPACITY_FACTOR = 1.5               # spare frame rows of the device build's arrays over its first draw
+
+
 class MotionLib(MotionLibBase):
     """`MotionLib(motion_file, key_body_ids, device)` + `load_motions(skeleton_trees, gender_betas, limb_weights, random_sample,
     start_idx)` (motion_lib_smpl.py:176-363): one clip per skeleton (= per env), drawn from the pickle with `_sampling_prob`, each
     built on ITS skeleton.  A skeleton is anything with `.joint_off` (24, 3) and `.parent` (24,) -- emloco_amd.model.HumanoidModel --
     or a (local_translation, parent_indices) pair."""
 
-    def __init__(self, motion_file, key_body_ids, device, fix_height=False, masterfoot_conifg=None, min_length=-1):
+    def __init__(self, motion_file, key_body_ids, device, fix_height=False, masterfoot_conifg=None, min_length=-1, build="host"):
         import joblib
+        if build not in BUILD_MODES:
+            raise ValueError(f"build must be one of {BUILD_MODES}, not {build!r}")
+        self.build = build              # how load_motions builds the clip cache unless told otherwise
+        self.num_reallocations = 0      # device builds whose draw did not fit the frame arrays (their addresses changed)
+        self._frame_capacity = 0
+        self._store = {}
+        self._build_events = None
         if masterfoot_conifg is not None:
             raise NotImplementedError("masterfoot skeletons are not part of this path")
         if fix_height:
@@ -118,7 +139,14 @@ class MotionLib(MotionLibBase):
         lt, par = s
         return np.asarray(lt, np.float64), np.asarray(par)
 
-    def load_motions(self, skeleton_trees, gender_betas=None, limb_weights=None, random_sample=True, start_idx=0):
+    def load_motions(self, skeleton_trees, gender_betas=None, limb_weights=None, random_sample=True, start_idx=0, build=None):
+        """`build`: "host" -- every (clip, skeleton) pair through `clip_cache` in float64 -- or "device" -- the drawn clips' raw frames
+        uploaded as float32 and built by emloco_motion_build; None: the library's mode (`self.build`).  Both leave the same attributes."""
+        build = self.build if build is None else build
+        if build not in BUILD_MODES:
+            raise ValueError(f"build must be one of {BUILD_MODES}, not {build!r}")
+        if build == "device":
+            return self._load_motions_device(skeleton_trees, gender_betas, limb_weights, random_sample, start_idx)
         n = len(skeleton_trees)
         if random_sample:
             ids = torch.multinomial(self._sampling_prob, num_samples=n, replacement=True)
@@ -164,6 +192,119 @@ class MotionLib(MotionLibBase):
         self._num_motions = n
         self.motion_ids = torch.arange(n, dtype=torch.long, device=dev)
         return self
+
+    # ------------------------------------------------------------------ the device build
+    def _clip_frames32(self, i):
+        """clip i's raw frames as the kernel takes them: float32, contiguous (no copy where the pickle holds them so)"""
+        clip = self._motion_data_list[i]
+        quat = np.ascontiguousarray(np.asarray(clip["pose_quat_global"]), dtype=np.float32).reshape(-1, 24, 4)
+        trans = np.ascontiguousarray(np.asarray(clip["root_trans_offset"]), dtype=np.float32).reshape(-1, 3)
+        aa = (np.ascontiguousarray(np.asarray(clip["pose_aa"]), dtype=np.float32).reshape(-1, 72) if "beta" in clip
+              else np.zeros((quat.shape[0], 72), np.float32))
+        if quat.shape[0] != trans.shape[0] or quat.shape[0] != aa.shape[0]:
+            raise ValueError(f"clip {self._motion_data_keys[i]}: rotations, translations and poses differ in their frame counts")
+        return quat, trans, aa, float(clip.get("fps", 30))
+
+    def _frame_rows(self, F):
+        """The frame arrays with room for F rows: the ones in use when F fits their capacity -- their addresses stay valid -- and new
+        ones with CAPACITY_FACTOR x F rows otherwise.  True when they were (re)allocated."""
+        if F <= self._frame_capacity:
+            return False
+        if self._frame_capacity:
+            self.num_reallocations += 1
+        self._frame_capacity = int(np.ceil(CAPACITY_FACTOR * F))
+        self._store = {k: torch.zeros((self._frame_capacity,) + s, dtype=torch.float32, device=self._device) for k, s in _FRAME_SHAPES.items()}
+        return True
+
+    def _set_rows(self, name, value):
+        """a per-motion array: rewritten in place when its shape is unchanged (its address stays valid)"""
+        old = getattr(self, name, None)
+        if isinstance(old, torch.Tensor) and old.shape == value.shape and old.dtype == value.dtype and old.device == value.device:
+            old.copy_(value)
+        else:
+            setattr(self, name, value.contiguous())
+
+    def _load_motions_device(self, skeleton_trees, gender_betas, limb_weights, random_sample, start_idx):
+        from .. import _lib
+        dev = self._device
+        if dev.type != "cuda":
+            raise _lib.EmlocoError(f'load_motions(build="device") builds the clip cache with a HIP kernel: it needs a GPU device, not {dev}; '
+                                   'use build="host" there')
+        lib = _lib.require_device()
+        n = len(skeleton_trees)
+        if random_sample:
+            ids = torch.multinomial(self._sampling_prob, num_samples=n, replacement=True)
+        else:
+            ids = torch.clip(torch.arange(n) + start_idx, 0, self._num_unique_motions - 1)
+        self._curr_motion_ids = ids
+        self._sampling_batch_prob = self._sampling_prob[ids] / self._sampling_prob[ids].sum()
+        # the skeleton table: one row per distinct set of joint offsets
+        skel_rows, skel_of, skel_id, parent = [], {}, np.zeros(n, np.int32), None
+        for j, s in enumerate(skeleton_trees):
+            lt, par = self._skeleton(s)
+            par = np.asarray(par, np.int32)
+            if lt.shape != (24, 3) or par.shape != (24,) or (parent is not None and not np.array_equal(par, parent)):
+                raise ValueError("the device build takes 24-body skeletons that share one parent list")
+            parent = par
+            key = lt.tobytes()
+            if key not in skel_of:
+                skel_of[key] = len(skel_rows)
+                skel_rows.append(lt.astype(np.float32))
+            skel_id[j] = skel_of[key]
+        frames = [self._clip_frames32(i) for i in ids.tolist()]
+        nfr = np.asarray([f[0].shape[0] for f in frames], np.int32)
+        if int(nfr.min()) < 2:
+            raise ValueError("a clip needs at least 2 frames")
+        fps = np.asarray([f[3] for f in frames], np.float32)
+        start = np.zeros(n, np.int64)
+        np.cumsum(nfr[:-1], out=start[1:])
+        F = int(nfr.sum())
+        self.reallocated = self._frame_rows(F)
+        st = self._store
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        ev[0].record()
+        # only the drawn clips travel: their frames concatenated, env after env
+        st["_quat_in"][:F].copy_(torch.from_numpy(np.concatenate([f[0] for f in frames])))
+        st["_trans_in"][:F].copy_(torch.from_numpy(np.concatenate([f[1] for f in frames])))
+        st["_motion_aa"][:F].copy_(torch.from_numpy(np.concatenate([f[2] for f in frames])))
+        self._set_rows("_motion_num_frames", torch.from_numpy(nfr.astype(np.int64)).to(dev))
+        self._set_rows("length_starts", torch.from_numpy(start).to(dev))
+        self._set_rows("_motion_fps", torch.from_numpy(fps).to(dev))
+        d_nfr32, d_skel = torch.from_numpy(nfr).to(dev), torch.from_numpy(skel_id).to(dev)
+        d_lt = torch.from_numpy(np.ascontiguousarray(np.stack(skel_rows))).to(dev)
+        ev[1].record()
+        taps = gaussian_taps()
+        rc = lib.emloco_motion_build(n, len(skel_rows), F, st["_quat_in"].data_ptr(), st["_trans_in"].data_ptr(), self.length_starts.data_ptr(),
+                                     d_nfr32.data_ptr(), self._motion_fps.data_ptr(), d_skel.data_ptr(), start.ctypes.data, nfr.ctypes.data,
+                                     skel_id.ctypes.data, d_lt.data_ptr(), parent.ctypes.data, taps.ctypes.data,
+                                     *[st[k].data_ptr() for k in FRAME_KEYS], 0, torch.cuda.current_stream().cuda_stream)
+        if rc != 0:
+            raise _lib.EmlocoError(f"emloco_motion_build failed (code {rc})")
+        ev[2].record()
+        self._build_events = ev
+        for k in FRAME_KEYS + ("_motion_aa",):
+            setattr(self, k, st[k][:F])                    # the live rows: a view at the storage's address
+        self._set_rows("_motion_lengths", torch.from_numpy(((nfr - 1) / fps.astype(np.float64)).astype(np.float32)).to(dev))
+        self._set_rows("_motion_dt", 1.0 / self._motion_fps)
+        bodies = []
+        for j, i in enumerate(ids.tolist()):
+            has_beta = "beta" in self._motion_data_list[i] and gender_betas is not None
+            bodies.append(torch.as_tensor(np.asarray(gender_betas[j].cpu() if isinstance(gender_betas[j], torch.Tensor) else gender_betas[j]),
+                                          dtype=torch.float32) if has_beta else torch.zeros(17))
+        self._set_rows("_motion_bodies", torch.stack(bodies).to(dev).float())
+        self._set_rows("_motion_limb_weights", torch.as_tensor(limb_weights).float().to(dev) if limb_weights is not None else torch.zeros(n, 10, device=dev))
+        self._set_rows("_motion_weights", self._sampling_batch_prob.to(dev).float())
+        self._set_rows("motion_ids", torch.arange(n, dtype=torch.long, device=dev))
+        self._num_motions = n
+        return self
+
+    def build_times(self):
+        """(upload ms, kernel ms) of the last device build from its HIP events; waits for the build to finish"""
+        if self._build_events is None:
+            return None
+        e0, e1, e2 = self._build_events
+        e2.synchronize()
+        return e0.elapsed_time(e1), e1.elapsed_time(e2)
 
     def get_motion_files(self, motion_ids):
         return self._motion_data_keys[self._curr_motion_ids[torch.as_tensor(motion_ids).cpu()]]

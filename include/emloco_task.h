@@ -356,6 +356,32 @@ int emloco_episode_stats_step(int n_envs, const float *dev_rew_buf, const float 
  * games of the epoch, not over rl_games' window of the last games.  NULL buffers or n_envs <= 0: -1, nothing is written. */
 int emloco_episode_stats_reduce(int n_envs, double *dev_totals, double *dev_moments, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * The motion library's clip cache from raw clip frames: what utils/motion_lib_smpl.py `clip_cache` (the reference's
+ * load_motion_with_skeleton + poselib, motion_lib_smpl.py:84-131, skeleton3d.py:1249-1272) builds per (clip, skeleton) pair on the host
+ * in float64, for n_clips pairs in one launch in float32.  The frames of all clips lie in rows [0, n_frames_total) of every array;
+ * clip c owns rows frame_start[c] .. frame_start[c] + n_frames[c] - 1.
+ *   dev_quat_global [F][24][4]  global body rotations xyzw (the pickle's pose_quat_global);  dev_root_trans [F][3]
+ *   dev_frame_start [n_clips] int64, dev_n_frames [n_clips] (>= 2), dev_fps [n_clips], dev_skel_id [n_clips]
+ *   host_frame_start / host_n_frames / host_skel_id: HOST copies of the same arrays, validated here (no device read-back): at least 2
+ *       frames, skel_id in [0, n_skel), every clip inside the F rows
+ *   dev_local_translation [n_skel][24][3]  joint offsets of the skeletons
+ *   host_parent [24]  HOST: -1 for body 0, otherwise an index below the child's;  host_taps [EMLOCO_MOTION_TAPS]  HOST: the gaussian
+ *       filter's weights (sigma 2, radius 8, computed in float64 and normalised by the caller); both travel with the launch
+ *   outputs, [F] rows each: dev_gts [24][3], dev_grs [24][4] (= the input, bit for bit), dev_lrs [24][4], dev_gvs [24][3],
+ *       dev_gavs [24][3], dev_dvs [69]
+ *   grid: workgroups to launch, 0 = one per (clip, 64-frame tile) up to 4096; the result does not depend on it
+ * Angles are taken as 2 atan2(|xyz|, w); identical consecutive frames give exactly zero velocities.  A NULL array, n_clips < 1, a
+ * clip with fewer than 2 frames or outside the arrays, a skel_id out of range, a bad parent list, a negative grid: -1, nothing is
+ * launched. */
+#define EMLOCO_MOTION_TAPS 17
+#define EMLOCO_MOTION_BODIES 24
+int emloco_motion_build(int n_clips, int n_skel, int64_t n_frames_total, const float *dev_quat_global, const float *dev_root_trans,
+                        const int64_t *dev_frame_start, const int32_t *dev_n_frames, const float *dev_fps, const int32_t *dev_skel_id,
+                        const int64_t *host_frame_start, const int32_t *host_n_frames, const int32_t *host_skel_id,
+                        const float *dev_local_translation, const int32_t *host_parent, const float *host_taps, float *dev_gts,
+                        float *dev_grs, float *dev_lrs, float *dev_gvs, float *dev_gavs, float *dev_dvs, int grid, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
