@@ -20,7 +20,9 @@ extern "C" {
 
 #define EMLOCO_NB 24        /* rigid bodies per humanoid (humanoid.py:264) */
 #define EMLOCO_NDOF 69      /* 23 joints x 3 (humanoid.py:516-521) */
-#define EMLOCO_MAXC 20      /* contacts kept per env and substep */
+#define EMLOCO_MAXC 20      /* contacts kept per env and substep: of the candidates inside the contact offset the shallowest are dropped
+                               one by one, of candidates at bit-equal distance the one with the highest candidate id first (candidates
+                               are numbered body-major: sphere centre | capsule ends a, b | box corners 0..7), the rest keep their order */
 #define EMLOCO_MAXCAND 96   /* contact-candidate slots per env (warm-start storage) */
 
 enum { EMLOCO_GEOM_SPHERE = 0, EMLOCO_GEOM_CAPSULE = 1, EMLOCO_GEOM_BOX = 2 };

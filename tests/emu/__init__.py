@@ -61,11 +61,22 @@ def model_desc(arr):
                      _p(arr["effort"]))
 
 
-def sim_step(osim, n_calls=1, expect_error=None, cost_ticks=None):
+def sim_step(osim, n_calls=1, expect_error=None, cost_ticks=None, order=None, ids=None, skip=None, parts=0, grid_pad=0):
     """Advance an oracle.Sim-shaped state holder with the emulated HIP kernel (same arrays, in place).  `cost_ticks`: a uint32 array
-    [n_env] that takes the key of the cost-ordered dispatch (what emloco_sim_cost_ticks reads back on the device)."""
+    [n_env] that takes the key of the cost-ordered dispatch (what emloco_sim_cost_ticks reads back on the device).  The launch-level
+    arguments of emloco_sim_step / emloco_sim_step_subset: `order` int32 [n_env], a permutation -- workgroup i of a full launch steps
+    env order[i] (emloco_sim_set_cost_order); `ids` int32, a compacted id list (valid ids first, -1 after them): only the listed envs
+    are stepped, unsplit; `skip` int64 [n_env]: envs with a non-zero flag are left untouched; `parts`: the split launch
+    (emloco_sim_set_split; 0: the EMLOCO_EMU_PARTS variable decides); `grid_pad`: that many workgroups past the launch's last one."""
     assert cost_ticks is None or (cost_ticks.dtype == np.uint32 and cost_ticks.shape == (osim.E,) and cost_ticks.flags.c_contiguous)
+    assert order is None or (order.dtype == np.int32 and order.flags.c_contiguous and sorted(order.tolist()) == list(range(osim.E)))
+    assert ids is None or (ids.dtype == np.int32 and ids.flags.c_contiguous and ids.ndim == 1 and len(ids) <= osim.E and ids.max(initial=-1) < osim.E)
+    assert skip is None or (skip.dtype == np.int64 and skip.shape == (osim.E,) and skip.flags.c_contiguous)
+    assert ids is None or skip is None, "exactly one of skip flags / id list, as emloco_sim_step_subset asks"
     lib().emu_sim_set_cost_ticks(C.c_void_p(cost_ticks.ctypes.data if cost_ticks is not None else None))
+    fl = lib().emu_sim_set_launch
+    fl.argtypes, fl.restype = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int], None
+    fl(_vp(order), _vp(ids), len(ids) if ids is not None else 0, _vp(skip), int(parts), int(grid_pad))
     desc = model_desc(osim.arr)
     sc = getattr(osim, "sc", None)
     scd = None
@@ -92,19 +103,24 @@ def sim_step(osim, n_calls=1, expect_error=None, cost_ticks=None):
     return rc
 
 
-def sim_fk(osim):
+def sim_fk(osim, ids=None, grid=0):
+    """sim_fk_kernel: body states of every env, or of the envs of an int32 id list up to its first -1; `grid` > 0: that many
+    workgroups stride over the list."""
     desc = model_desc(osim.arr)
-    assert lib().emu_sim_fk(C.byref(desc), _p(osim.root_state), _p(osim.dof_state), _p(osim.rb_state)) == 0
+    assert ids is None or (ids.dtype == np.int32 and ids.flags.c_contiguous and ids.max(initial=-1) < osim.E)
+    fn = lib().emu_sim_fk
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+    assert fn(C.byref(desc), _vp(osim.root_state), _vp(osim.dof_state), _vp(osim.rb_state), _vp(ids), len(ids) if ids is not None else 0, int(grid)) == 0
 
 
-def sim_copy_rows(src, dst, ids, row_len, n_env):
+def sim_copy_rows(src, dst, ids, row_len, n_env, grid_pad=0):
     """copy_rows_kernel (the *_indexed setters with a foreign `dev_full`) on host arrays: `dst` may be a view into a larger buffer."""
     assert src.dtype == np.float32 and dst.dtype == np.float32 and ids.dtype == np.int32
     assert src.flags.c_contiguous and dst.flags.c_contiguous and ids.flags.c_contiguous
     fn = lib().emu_sim_copy_rows
-    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
     fn.restype = None
-    fn(src.ctypes.data, dst.ctypes.data, ids.ctypes.data, len(ids), row_len, n_env)
+    fn(src.ctypes.data, dst.ctypes.data, ids.ctypes.data, len(ids), row_len, n_env, int(grid_pad))
 
 
 # ------------------------------------------------------------------ task kernels

@@ -25,6 +25,17 @@ extern "C" void emu_sim_set_heightfield(const short *samples, int nx, int ny, fl
 static unsigned *g_ticks = nullptr;   // set by emu_sim_set_cost_ticks: [n_env] words that take the key of the cost-ordered dispatch (or NULL)
 extern "C" void emu_sim_set_cost_ticks(unsigned *ticks) { g_ticks = ticks; }
 
+// The launch-level arguments of emloco_sim_step / emloco_sim_step_subset (csrc/sim_capi.hip) for the next emu_sim_step calls:
+// `order` [n_env] the dispatch order of a full launch (emloco_sim_set_cost_order), `ids` [n_ids] a compacted id list (valid ids
+// first, -1 after them: workgroup i steps entry i, never split), `skip` [n_env] int64 flags (non-zero: left untouched), `parts`
+// the split (emloco_sim_set_split; 0: EMLOCO_EMU_PARTS decides).  All NULL / 0: the plain step.
+// `grid_pad`: workgroups beyond the launch's last one (a launcher that rounds its grid up): the kernel's guard sends them home.
+struct EmuLaunch { const int *order; const int *ids; int n_ids; const long long *skip; int parts; int grid_pad; };
+static EmuLaunch g_launch = {nullptr, nullptr, 0, nullptr, 0, 0};
+extern "C" void emu_sim_set_launch(const int *order, const int *ids, int n_ids, const long long *skip, int parts, int grid_pad) {
+    g_launch = {order, ids, n_ids, skip, parts, grid_pad};
+}
+
 extern "C" int emu_sim_step(const EmlocoSimParams *prm, const EmlocoModelDesc *m, float *root_state,
                             float *dof_state, const float *pd_target, float *rb_state, float *contact_force,
                             float *dof_force, float *lambda_ws, int n_calls) {
@@ -51,23 +62,31 @@ extern "C" int emu_sim_step(const EmlocoSimParams *prm, const EmlocoModelDesc *m
     p.n_sub = prm->n_sub * n_calls;
     // EMLOCO_EMU_PARTS=n: the split launch (emloco_sim_set_split) -- n workgroups per env, all first parts first
     const char *pe = getenv("EMLOCO_EMU_PARTS");
-    int n_parts = pe ? atoi(pe) : 1;
+    int n_parts = g_launch.parts > 0 ? g_launch.parts : (pe ? atoi(pe) : 1);
     if (n_parts > p.n_sub) n_parts = p.n_sub;             // at least one substep per part, as emloco_sim_step clamps it
-    std::vector<float> part_state((size_t)m->n_env * EMLOCO_PART_WORDS, 0.0f);
-    std::vector<unsigned> part_flag((size_t)m->n_env, 0u);
-    d.n_parts = n_parts; d.part_seq = 1; d.part_state = part_state.data(); d.part_flag = part_flag.data();
+    if (g_launch.ids) n_parts = 1;                        // the list launch is not split (emloco_sim_step_subset)
+    // the hand-over buffers exist only for a split launch, as emloco_sim_set_split allocates them
+    std::vector<float> part_state(n_parts > 1 ? (size_t)m->n_env * EMLOCO_PART_WORDS : 0, 0.0f);
+    std::vector<unsigned> part_flag(n_parts > 1 ? (size_t)m->n_env : 0, 0u);
+    d.n_parts = n_parts; d.part_seq = 1;
+    d.part_state = n_parts > 1 ? part_state.data() : nullptr; d.part_flag = n_parts > 1 ? part_flag.data() : nullptr;
     // EMLOCO_EMU_POISON=env: the first part of that env withholds its hand-over flag (emloco_sim_debug_poison_part); the
     // device error word is the return value (0: fine)
     const char *po = getenv("EMLOCO_EMU_POISON");
     unsigned err = 0u;
     d.part_spin_max = 4; d.part_poison = po ? atoi(po) : -1; d.err = &err;
-    d.n_slots = m->n_env;
+    d.n_slots = g_launch.ids ? g_launch.n_ids : m->n_env;
     d.step_ticks = g_ticks;
-    emu::launch((unsigned)(((m->n_env + EMU_ENVS_PER_WG - 1) / EMU_ENVS_PER_WG) * n_parts), 64, [&] { if (d.hf) emloco::sim_step_kernel<1>(p, d); else emloco::sim_step_kernel<0>(p, d); });
+    d.step_ids = g_launch.ids; d.step_skip = g_launch.skip;
+    d.step_order = g_launch.ids ? nullptr : g_launch.order;     // a list launch takes its envs from the list (emloco_sim_step_subset)
+    if (d.n_slots < 1) return 0;
+    emu::launch((unsigned)(((d.n_slots + EMU_ENVS_PER_WG - 1) / EMU_ENVS_PER_WG) * n_parts + g_launch.grid_pad), 64, [&] { if (d.hf) emloco::sim_step_kernel<1>(p, d); else emloco::sim_step_kernel<0>(p, d); });
     return (int)err;
 }
 
-extern "C" int emu_sim_fk(const EmlocoModelDesc *m, float *root_state, float *dof_state, float *rb_state) {
+// env_ids NULL: every env; else the listed ones, up to the first -1 (a device-compacted list).  grid < 1: one workgroup per entry,
+// else `grid` workgroups stride over the list (the launcher's cap of 256).
+extern "C" int emu_sim_fk(const EmlocoModelDesc *m, float *root_state, float *dof_state, float *rb_state, const int *env_ids, int n_ids, int grid) {
     emloco::Topology t;
     if (!t.build(m->parent, m->geom_type)) return -1;
     EmlocoSimDev d{};
@@ -77,12 +96,14 @@ extern "C" int emu_sim_fk(const EmlocoModelDesc *m, float *root_state, float *do
                                                        m->kp, m->kd, m->armature, m->effort, nullptr, nullptr, nullptr);
     d.topo = topo.data(); d.model = mdl.data();
     d.root_state = root_state; d.dof_state = dof_state; d.rb_state = rb_state;
-    emu::launch((unsigned)m->n_env, 64, [&] { emloco::sim_fk_kernel(d, nullptr, m->n_env); });
+    if (!env_ids) n_ids = m->n_env;
+    if (n_ids < 1) return 0;
+    emu::launch((unsigned)(grid < 1 ? n_ids : grid), 64, [&] { emloco::sim_fk_kernel(d, env_ids, n_ids); });
     return 0;
 }
 
 // copy_rows_kernel as the *_indexed setters launch it when `dev_full` is not the simulator's own tensor: one workgroup per list entry
-extern "C" void emu_sim_copy_rows(const float *src, float *dst, const int *ids, int n_ids, int row_len, int n_env) {
+extern "C" void emu_sim_copy_rows(const float *src, float *dst, const int *ids, int n_ids, int row_len, int n_env, int grid_pad) {
     if (n_ids < 1) return;
-    emu::launch((unsigned)n_ids, 64, [&] { emloco::copy_rows_kernel(src, dst, ids, n_ids, row_len, n_env); });
+    emu::launch((unsigned)(n_ids + grid_pad), 64, [&] { emloco::copy_rows_kernel(src, dst, ids, n_ids, row_len, n_env); });
 }
