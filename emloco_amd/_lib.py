@@ -128,6 +128,18 @@ class ResetPool(C.Structure):   # EmlocoResetPool
                 ("next_seed", C.c_uint64)]
 
 
+GETUP_STATS = 6                # EMLOCO_GETUP_STATS
+GETUP_STAT_RECOVER, GETUP_STAT_FALL, GETUP_STAT_NORMAL, GETUP_STAT_COUNTER_SUM, GETUP_STAT_FLAG_CALLS, GETUP_STAT_HELD = range(6)
+
+
+class GetupBufs(C.Structure):
+    """EmlocoGetupBufs (include/emloco_task.h): the get-up task's fall pool and per-env recovery state."""
+    _fields_ = [("n_env", C.c_int32), ("n_pool", C.c_int32), ("pool_root", C.c_void_p), ("pool_dof", C.c_void_p),
+                ("pool_taken", C.c_void_p), ("assign", C.c_void_p), ("recovery_counter", C.c_void_p),
+                ("progress_buf", C.c_void_p), ("reset_buf", C.c_void_p), ("terminate_buf", C.c_void_p),
+                ("split_ws", C.c_void_p), ("stats", C.c_void_p)]
+
+
 class LocoValStep(C.Structure):
     """EmlocoLocoValStep (include/emloco_predictor.h)."""
     _fields_ = [("n_env", C.c_int32), ("step_to_pred", C.c_int32), ("gamma", C.c_float), ("inversion_penalty", C.c_float),

@@ -839,9 +839,9 @@ class AMPAgent:
         if amp_obs.shape[0] > 0:
             self._amp_replay_buffer.store({"amp_obs": amp_obs[:self._amp_replay_buffer.get_buffer_size()]})
 
-    def pre_epoch(self, epoch_num):                               # amp_continuous.py:203-210
+    def pre_epoch(self, epoch_num):                               # amp_continuous.py:203-220
         from .pre_epoch import pre_epoch
-        return pre_epoch(self.task, epoch_num)
+        return pre_epoch(self.task, epoch_num, agent=self)
 
     def train_epoch(self):
         self.pre_epoch(self.epoch_num + 1)                        # the epoch that begins, counted from 1 as the reference counts them

@@ -29,6 +29,11 @@ the reference's line (`Ep: .. rwd: .. fps_step: .. eps_len: ..`, :236-238) from 
 LocoVal fit, `NAME.pth` and `NAME_<epoch:08d>.pth` for the policy -- every --save_freq epochs, every fifth of those also as an
 intermediate, and at the end.  `--resume` carries an experiment on from them (not the simulator's state nor the random streams: a
 valid continuation, not a bit-identical one).  `--stats` alone: the statistics and the line, nothing on disk.
+
+    python -m emloco_amd.run --task HumanoidPedestrianTerrainGetup --cfg_env emloco_amd/data/cfg/pacer_getup.yaml --train_policy ...
+
+trains the policy on the get-up curriculum (env/tasks/humanoid_pedestrain_terrain_getup.py; learning/pre_epoch.py holds its schedule); the
+epoch's line and log record gain the share of recovery / fall / normal resets and the mean recovery counter (`getup`).
 """
 import json
 import os
@@ -341,6 +346,12 @@ class PolicyTrainee:
             out["games"] = self.stats.end_epoch()
         out["tail"] = (f"\ta_loss {info['actor_loss']:.4f} c_loss {info['critic_loss']:.4f} disc_loss {info['disc_loss']:.4f} "
                        f"kl {info['kl']:.5f}")
+        task = getattr(self.agent, "task", None)
+        if self.stats is not None and hasattr(task, "getup_epoch_stats"):
+            # the get-up task's reset mix and mean recovery counter of the epoch, from sums its kernels keep on the device (one read)
+            g = out["getup"] = task.getup_epoch_stats()
+            out["tail"] += (f"\tgetup rec/fall/normal {g['getup_recovery_share']:.2f}/{g['getup_fall_share']:.2f}/{g['getup_normal_share']:.2f}"
+                            f" counter {g['getup_mean_recovery_counter']:.1f}")
         return out
 
     def save(self, mof, epoch=None):

@@ -2,9 +2,10 @@
 import numpy as np
 
 from ..env.tasks.humanoid_pedestrain_terrain import HumanoidPedestrianTerrain
+from ..env.tasks.humanoid_pedestrain_terrain_getup import HumanoidPedestrianTerrainGetup
 from ..env.tasks.vec_task_wrappers import VecTaskPythonWrapper
 
-TASKS = {"HumanoidPedestrianTerrain": HumanoidPedestrianTerrain}
+TASKS = {"HumanoidPedestrianTerrain": HumanoidPedestrianTerrain, "HumanoidPedestrianTerrainGetup": HumanoidPedestrianTerrainGetup}
 
 
 def parse_task(args, cfg, cfg_train, sim_params):

@@ -382,6 +382,83 @@ int emloco_motion_build(int n_clips, int n_skel, int64_t n_frames_total, const f
                         const float *dev_local_translation, const int32_t *host_parent, const float *host_taps, float *dev_gts,
                         float *dev_grs, float *dev_lrs, float *dev_gvs, float *dev_gavs, float *dev_dvs, int grid, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * The get-up task (HumanoidPedestrianTerrainGetup, pacer/pacer/env/tasks/humanoid_pedestrain_terrain_getup.py): a reset is one of
+ *   recovery   the env keeps the (fallen) state it terminated in and may not terminate for recovery_steps steps   :125-133,156-158
+ *   fall       the env starts from a row of a pool of pre-generated fallen poses, same grace period              :137-141,160-174
+ *   normal     the reset of emloco_task_reset*                                                                    :144-147
+ * The state of the task lives in caller-owned device memory; P = n_pool fallen poses (the task uses P = n_env).  A slot of the pool is
+ * held by at most one env: pool_taken[slot] != 0 and assign[env] == slot go together; a slot with pool_taken set that no env holds
+ * (a pose with a non-finite value) is never handed out.  assign starts at -1 (the reference's 0 can free slot 0 under another env). */
+#define EMLOCO_GETUP_STATS 6
+enum {
+    EMLOCO_GETUP_STAT_RECOVER = 0, EMLOCO_GETUP_STAT_FALL = 1, EMLOCO_GETUP_STAT_NORMAL = 2,   /* list entries of each kind, summed over splits */
+    EMLOCO_GETUP_STAT_COUNTER_SUM = 3,     /* sum over envs and emloco_getup_flags calls of recovery_counter (after the decrement) */
+    EMLOCO_GETUP_STAT_FLAG_CALLS = 4,      /* emloco_getup_flags calls */
+    EMLOCO_GETUP_STAT_HELD = 5             /* envs held back by a counter > 0, summed over emloco_getup_flags calls */
+};
+typedef struct EmlocoGetupBufs {
+    int32_t n_env, n_pool;
+    const float *pool_root;         /* [P][13], velocities zero */
+    const float *pool_dof;          /* [P][69][2], velocities zero */
+    uint8_t *pool_taken;            /* [P] */
+    int32_t *assign;                /* [E] slot the env holds, -1: none */
+    int32_t *recovery_counter;      /* [E] */
+    int64_t *progress_buf, *reset_buf, *terminate_buf;     /* [E] the task's buffers (EmlocoTaskBufs) */
+    int32_t *split_ws;              /* [P] scratch of emloco_getup_split: the free slots in the order they are handed out */
+    int64_t *stats;                 /* [EMLOCO_GETUP_STATS] running sums for the epoch's log line, or NULL; the caller reads and clears them */
+} EmlocoGetupBufs;
+
+/* _reset_actors :122-154 as ONE launch, without a host read: splits an id list (explicit ascending ids, or a list of
+ * emloco_task_compact_done*: the entries in front of the first negative id are the list) into three.
+ *   two uniforms per list entry: dev_rnd [n][2], or NULL: entry i draws reset_rnd_value(seed, i, 0 | 1), the hash emloco_task_reset_seeded
+ *   fills its rows with
+ *   1. every listed env that holds a slot gives it back (pool_taken[assign[env]] = 0, assign[env] = -1)                :123
+ *   2. an entry is RECOVERY iff u0 < recovery_prob and terminate_buf[env] == 1                                         :125-128
+ *   3. otherwise FALL iff u1 < fall_prob                                                                               :137-139
+ *   4. otherwise NORMAL
+ *   5. the j-th fall entry of the call, in list order, takes the j-th slot with pool_taken == 0 in the order P_key(0), P_key(1), ...
+ *      (the keyed bijection of [0, P) the real paths are picked with, key = slot_key; the reference draws torch.randperm :165); a fall
+ *      entry for which no free slot is left becomes a normal entry (the reference asserts :164)
+ *   6. recovery_counter[env] = recovery_steps for recovery and fall entries, 0 for normal ones                          :147,157,169
+ * dev_normal, dev_fall, dev_recover, dev_fall_slot (parallel to dev_fall): n + 1 entries each, in the input's order -- valid entries
+ * first, -1 behind them, the count at [n]; the id-list contract of emloco_task_compact_done, so every list feeds the entry points of
+ * this library as it is; none of them may alias the input list or another output.  Integer logic on one workgroup: the result does not depend on the launch.  n == 0 writes the four counts.
+ * A NULL structure, list or output, n < 0 or above n_env, n_pool < 1, a missing buffer: -1, nothing is written. */
+int emloco_getup_split(const EmlocoGetupBufs *getup, const int32_t *dev_env_ids, int n, const float *dev_rnd, uint64_t seed,
+                       float recovery_prob, float fall_prob, int recovery_steps, uint32_t slot_key, int32_t *dev_normal,
+                       int32_t *dev_fall, int32_t *dev_recover, int32_t *dev_fall_slot, void *stream);
+
+/* _reset_fall_episode :160-174 and what _reset_env_tensors (humanoid.py:467-481) / _reset_task (humanoid_pedestrain_terrain.py:493-523)
+ * do to an env whose state is in place, for the fall and recovery lists of emloco_getup_split (n + 1 or n entries each):
+ *   fall list        pool row dev_fall_slot[i] -> the simulator's root / dof rows of env dev_fall[i], warm-start impulses zeroed, then the
+ *                    forward kinematics of those envs (emloco_sim_fk_indexed: the body state is rewritten, where the reference leaves it
+ *                    stale until the next simulate)
+ *   both lists       progress_buf = reset_buf = terminate_buf = 0, contact forces zeroed, trajectory from the env's root position and
+ *                    velocity, LocoVal waypoints, init_pose, init_vel, the inversion flag -- the device functions of emloco_task_reset
+ *                    (reset_traj_to, reset_capture_pose), so the same bytes as emloco_task_traj_reset for the same rows; NO height fix
+ *   recovery list    root, dof and body state and the warm-start impulses are not written at all
+ * Random rows, [n][EMLOCO_RESET_RND] per list, row i for list entry i as emloco_task_traj_reset takes them: dev_rnd_fall and
+ * dev_rnd_recover, or both NULL: made on the device into dev_rnd_ws ([2 n][EMLOCO_RESET_RND]: the fall list's rows, then the recovery
+ * list's) from `seed` (fall) and ~seed (recovery), with a fresh real-path permutation as emloco_task_reset_seeded.
+ * Of `reset` the trajectory fields, traj_verts, inverted, the three flag buffers, waypoint_traj, init_pose, init_vel are read.
+ * A NULL simulator / structure / list, n < 0 or above the simulator's env count, one random block without the other, neither rows
+ * nor a workspace, a missing buffer: -1 (-3: simulator not prepared), nothing is written. */
+int emloco_getup_apply(struct EmlocoSim *sim, const EmlocoResetBufs *reset, const EmlocoGetupBufs *getup, const int32_t *dev_fall,
+                       const int32_t *dev_fall_slot, const int32_t *dev_recover, int n, const float *dev_rnd_fall,
+                       const float *dev_rnd_recover, uint64_t seed, float *dev_rnd_ws, void *stream);
+
+/* _init_amp_obs_default (humanoid_amp.py:499-502, called for the fall envs: humanoid_pedestrain_terrain_getup.py:183-187): history rows 1..14 of the listed envs = their
+ * newest row, in the layout bufs->amp_ring says (EMLOCO_AMP_PHYS_ROW).  NULL structure or list, n < 0 or above n_env, no AMP
+ * buffer: -1, nothing is written. */
+int emloco_getup_amp_default(const EmlocoTaskBufs *bufs, const int32_t *dev_env_ids, int n, void *stream);
+
+/* _update_recovery_count :191-194 and the recovery part of _compute_reset :196-204 for all envs, to be launched right behind a step's
+ * post-physics launch: recovery_counter = max(recovery_counter - 1, 0); where it is still > 0: reset_buf = terminate_buf = 0,
+ * progress_buf -= 1.  (The reference decrements in pre_physics_step and masks in _compute_reset of the same step; nothing reads the
+ * counter in between.)  NULL structure, n_env < 1, a missing buffer: -1, nothing is written. */
+int emloco_getup_flags(const EmlocoGetupBufs *getup, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
