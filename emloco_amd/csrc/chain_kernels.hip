@@ -81,6 +81,52 @@ struct ChainArgs {
                                 // observation workgroup, else NULL
 };
 
+// ---- The launcher's arithmetic: ONE definition for emloco_task_reset_obs_pooled (task_capi.hip) and for the launch on the CPU
+// (tests/emu/emu_task.cpp), as densify_pack is for emloco_traj_densify.  Arguments are those of the C entry (include/emloco_task.h).
+
+// What is wrong with the pool argument of a call, or nullptr.
+inline const char *chain_pool_error(const EmlocoResetPool *pool) {
+    if (!pool) return nullptr;
+    if (pool->k < 0 || pool->k > 4096) return "bad pool (k in [0, 4096], every pool buffer with its tag array)";
+    if (pool->k == 0) return nullptr;
+    if ((pool->cur && !pool->cur_tag) || (pool->next && !pool->next_tag)) return "bad pool (k in [0, 4096], every pool buffer with its tag array)";
+    if ((pool->cur && pool->cur == pool->next) || (pool->cur_tag && pool->cur_tag == pool->next_tag))
+        return "bad pool (cur and next are the same buffer: the launch reads the one while it fills the other)";
+    return nullptr;
+}
+
+// Fills `a` and `keyed` (the reset buffers with this call's real-path permutation key) and returns the grid: n_slots reset
+// workgroups, 2 pool_k pool-draw workgroups, n_env observation workgroups of the live envs, n_hist h_slots history workgroups.
+// 0: nothing to launch (an empty list without a live role and without a pool to draw into).
+inline unsigned chain_pack(const EmlocoResetBufs &rb, int n_env, int live_mode, const int64_t *skip, const int32_t *ids, int n, uint64_t seed,
+                           float *rnd_ws, const float *rnd, const EmlocoResetPool *pool, long long *prof, ChainArgs *a, EmlocoResetBufs *keyed) {
+    a->n = n;
+    a->n_slots = n < 256 ? (n > 0 ? n : 1) : 256;
+    a->h_slots = a->n_slots;
+    a->n_hist = (rb.flags & EMLOCO_RESET_NO_AMP_HISTORY) ? 0 : EMLOCO_AMP_STEPS - 1;
+    a->live_mode = live_mode & ~EMLOCO_POST_SKIP_DONE;
+    a->reset_mode = EMLOCO_POST_OBS | EMLOCO_POST_AMP_ROW;
+    a->seeded = rnd ? 0 : 1;
+    a->seed_lo = (unsigned)(seed & 0xffffffffu); a->seed_hi = (unsigned)(seed >> 32);
+    a->ids = ids; a->skip = skip; a->rnd_in = rnd; a->rnd_ws = rnd_ws;
+    a->prof = prof;
+    const bool pooled = pool && pool->k > 0 && a->seeded;
+    const bool read = pooled && seed != 0;      // a tag of zero means "never drawn": a call with seed 0 reads no pool entry
+    a->pool_k = pooled ? pool->k : 0;
+    a->pool_cur = read ? pool->cur : nullptr; a->tag_cur = read ? (const unsigned long long *)pool->cur_tag : nullptr;
+    a->pool_next = pooled ? pool->next : nullptr; a->tag_next = pooled ? (unsigned long long *)pool->next_tag : nullptr;
+    const uint64_t nseed = pooled ? pool->next_seed : 0;
+    a->nseed_lo = (unsigned)(nseed & 0xffffffffu); a->nseed_hi = (unsigned)(nseed >> 32);
+    a->next_key = (uint32_t)((nseed * 0xD6E8FEB86659FD93ull) >> 32);
+    *keyed = rb;
+    if (a->seeded) {                             // a fresh real-path permutation per call, as emloco_task_reset_seeded
+        keyed->real_pick = nullptr;
+        keyed->real_pick_key = (uint32_t)((seed * 0xD6E8FEB86659FD93ull) >> 32);
+    }
+    if (n == 0 && !a->live_mode && !a->pool_next) return 0;
+    return (unsigned)(a->n_slots + a->h_slots * a->n_hist + (a->pool_next ? a->pool_k * 2 : 0) + (a->live_mode ? n_env : 0));
+}
+
 // Between the phases of the reset role the lane index and the env are redefined through an empty asm: what a phase derived from
 // them (addresses, masks) dies with the phase instead of being held in registers for the whole chain (the kernel must fit the
 // register budget of the 4096 observation workgroups that share the launch).

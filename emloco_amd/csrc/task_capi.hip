@@ -284,8 +284,7 @@ int emloco_task_reset_obs_pooled(EmlocoSim *sim, const EmlocoResetBufs *rb, cons
                                  const int32_t *dev_env_ids, int n, uint64_t seed, float *dev_rnd_ws, const float *dev_rnd,
                                  const EmlocoResetPool *pool, void *stream) {
     if (!sim || !rb || !pb || !dev_env_ids) return tfail(-1, "emloco_task_reset_obs: null argument");
-    if (pool && (pool->k < 0 || pool->k > 4096 || (pool->k > 0 && ((pool->cur && !pool->cur_tag) || (pool->next && !pool->next_tag)))))
-        return tfail(-1, "emloco_task_reset_obs: bad pool (k in [0, 4096], every pool buffer with its tag array)");
+    if (const char *why = emloco::chain_pool_error(pool)) { char buf[192]; snprintf(buf, sizeof(buf), "emloco_task_reset_obs: %s", why); return tfail(-1, buf); }
     if (!sim->prepared) return tfail(-3, "emloco_task_reset_obs: sim not prepared");
     if (n < 0 || n > sim->n_env) return tfail(-1, "emloco_task_reset_obs: bad env count");
     if (!dev_rnd && !dev_rnd_ws) return tfail(-1, "emloco_task_reset_obs: neither random rows nor a workspace for them");
@@ -306,30 +305,9 @@ int emloco_task_reset_obs_pooled(EmlocoSim *sim, const EmlocoResetBufs *rb, cons
         !pb->left_to_right || !pb->amp_obs_buf || !pb->dof_subset || !pb->key_bodies || !pb->dof_state || bad_dof_subset(pb->n_dof_subset))
         return tfail(-1, "emloco_task_reset_obs: missing observation buffers");
     emloco::ChainArgs a;
-    a.n = n;
-    a.n_slots = n < 256 ? (n > 0 ? n : 1) : 256;
-    a.h_slots = n < 256 ? (n > 0 ? n : 1) : 256;
-    a.n_hist = (b->flags & EMLOCO_RESET_NO_AMP_HISTORY) ? 0 : EMLOCO_AMP_STEPS - 1;
-    a.live_mode = live_mode & ~EMLOCO_POST_SKIP_DONE;
-    a.reset_mode = EMLOCO_POST_OBS | EMLOCO_POST_AMP_ROW;
-    a.seeded = dev_rnd ? 0 : 1;
-    a.seed_lo = (unsigned)(seed & 0xffffffffu); a.seed_hi = (unsigned)(seed >> 32);
-    a.ids = dev_env_ids; a.skip = dev_skip; a.rnd_in = dev_rnd; a.rnd_ws = dev_rnd_ws;
-    a.prof = g_chain_prof;
-    const bool pooled = pool && pool->k > 0 && a.seeded;
-    a.pool_k = pooled ? pool->k : 0;
-    a.pool_cur = pooled ? pool->cur : nullptr; a.tag_cur = pooled ? (const unsigned long long *)pool->cur_tag : nullptr;
-    a.pool_next = pooled ? pool->next : nullptr; a.tag_next = pooled ? (unsigned long long *)pool->next_tag : nullptr;
-    const uint64_t nseed = pooled ? pool->next_seed : 0;
-    a.nseed_lo = (unsigned)(nseed & 0xffffffffu); a.nseed_hi = (unsigned)(nseed >> 32);
-    a.next_key = (uint32_t)((nseed * 0xD6E8FEB86659FD93ull) >> 32);
-    EmlocoResetBufs keyed = *rb;
-    if (a.seeded) {                              // a fresh real-path permutation per call, as emloco_task_reset_seeded
-        keyed.real_pick = nullptr;
-        keyed.real_pick_key = (uint32_t)((seed * 0xD6E8FEB86659FD93ull) >> 32);
-    }
-    const unsigned grid = (unsigned)(a.n_slots + a.h_slots * a.n_hist + (a.pool_next ? a.pool_k * 2 : 0) + (a.live_mode ? pb->n_env : 0));
-    if (n == 0 && !a.live_mode && !a.pool_next) return 0;
+    EmlocoResetBufs keyed;
+    const unsigned grid = emloco::chain_pack(*rb, pb->n_env, live_mode, dev_skip, dev_env_ids, n, seed, dev_rnd_ws, dev_rnd, pool, g_chain_prof, &a, &keyed);
+    if (grid == 0) return 0;
     hipLaunchKernelGGL(emloco::reset_obs_kernel, dim3(grid), dim3(64), 0, (hipStream_t)stream, *pb, keyed, sim->dev, a);
     THIPCHK(hipGetLastError());
     return 0;

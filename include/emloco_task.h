@@ -269,7 +269,18 @@ int emloco_task_reset_obs(struct EmlocoSim *sim, const EmlocoResetBufs *reset_bu
  * with another seed take the direct path; same bytes either way.
  * The caller alternates two buffers: this call's `next` is the following call's `cur`.  Ignored (direct path, nothing drawn)
  * when dev_rnd is given.  With a pool, dev_env_ids must be a list of emloco_task_compact_done* (n + 1 entries: the draw count
- * follows dev_env_ids[n], the number of finished envs). */
+ * follows dev_env_ids[n], the number of finished envs).
+ * Rules (tests/chain_cases.py holds the library and the kernel to them):
+ *   two buffers   `cur` and `next` (and their tag arrays) are different buffers: the launch reads entries of the one while it fills
+ *                 the other.  With k > 0, cur == next or cur_tag == next_tag (non-NULL) is refused: -1, nothing is written.  So is
+ *                 k < 0, k > 4096 and a pool buffer without its tag array.
+ *   zero tag      a tag of 0 means "empty": pool buffers start zeroed and no entry of a zeroed buffer is ever used.  Seed 0 is
+ *                 therefore reserved: a call with seed == 0 takes the direct path for every entry (same bytes as without a pool) and
+ *                 still draws `next` for next_seed as usual.  Entries drawn for next_seed == 0 are never used.
+ *   drawn entries entries [0, min(k, c + c / 4 + 32)) of `next` and their tags are written, c = dev_env_ids[n]; entries and tags behind
+ *                 them are left as they were (stale tags of an earlier seed cannot match a fresh seed).
+ *   dev_rnd_ws    row i is written only for the present entries that take the direct path; rows of entries served from the pool
+ *                 are left as they were.  Nothing in the library reads the workspace after the launch: it is scratch, not an output. */
 #define EMLOCO_POOL_FLOATS 512      /* per entry: root 13 | misc | dof 138 | trajectory 303 | waypoints 45 */
 typedef struct {
     int32_t k;                      /* entries per pool buffer (0: no pool) */

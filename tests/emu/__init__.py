@@ -181,14 +181,23 @@ class TaskHost:
         assert rc == 0
 
 
-def task_pd_targets(actions, offset, scale, zero_mask):
+def task_pd_targets(actions, offset, scale, zero_mask, copy=None):
+    """pd_targets_kernel; copy: a float32 array like `actions` that takes the kernel's copy of the actions (emloco_task_pd_targets_copy)"""
     actions = np.ascontiguousarray(actions, np.float32)
     out = np.zeros_like(actions)
-    fn = lib().emu_task_pd_targets
-    fn.argtypes = [C.c_int] + [C.c_void_p] * 5
+    fn = lib().emu_task_pd_targets_copy
+    fn.argtypes = [C.c_int] + [C.c_void_p] * 6
     fn(actions.shape[0], _vp(actions), _vp(np.ascontiguousarray(offset, np.float32)),
-       _vp(np.ascontiguousarray(scale, np.float32)), _vp(np.ascontiguousarray(zero_mask, np.uint8)), _vp(out))
+       _vp(np.ascontiguousarray(scale, np.float32)), _vp(np.ascontiguousarray(zero_mask, np.uint8)), _vp(out), _vp(copy))
     return out
+
+
+def chain_prof(buf):
+    """the stamps of emloco_task_chain_profile under emulation: `buf` (int64 [16], or None to stop) is stamped by every later reset_obs"""
+    assert buf is None or (buf.dtype == np.int64 and buf.shape == (16,) and buf.flags.c_contiguous)
+    fn = lib().emu_task_set_chain_prof
+    fn.argtypes, fn.restype = [C.c_void_p], None
+    fn(_vp(buf))
 
 
 # ------------------------------------------------------------------ reset kernels
@@ -242,10 +251,24 @@ class ResetHost:
         fn.argtypes = [C.c_int, C.c_void_p, C.c_void_p] + [C.c_void_p] * 5 + [C.c_void_p, C.c_int, C.c_void_p]
         assert fn(stages, C.byref(b), *self._sim_args(), _vp(ids), n, _vp(rnd)) == 0
 
-    def reset_obs(self, task_host, ids, n, seed=0, rnd_ws=None, rnd=None, **override):
-        """the reset roles of reset_obs_kernel; task_host: a TaskHost whose state arrays are this object's"""
+    def reset_obs(self, task_host, ids, n, seed=0, rnd_ws=None, rnd=None, pool=None, live_mode=0, skip=None, may_refuse=False, **override):
+        """emloco_task_reset_obs_pooled through the launcher's own arithmetic (emloco::chain_pack); task_host: a TaskHost whose state
+        arrays are this object's.  pool: None or (k, cur, cur_tag, next, next_tag, next_seed) -- float32 [k][512] / uint64 [k] arrays or
+        None; with a pool `ids` holds n + 1 entries.  live_mode / skip: the live envs' role and its flag snapshot (int64 [E]).
+        may_refuse=True: returns 0, or -1 for a pool argument that emloco::chain_pool_error refuses, instead of asserting 0."""
         b, pb = self.bufs(**override), task_host.bufs()
         pb.amp_ring = b.amp_ring
         fn = lib().emu_task_reset_obs
-        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_void_p] * 5 + [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p]
-        assert fn(C.byref(pb), C.byref(b), *self._sim_args(), _vp(ids), n, seed, _vp(rnd_ws), _vp(rnd)) == 0
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_void_p] * 5 + [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                                                  C.c_void_p, C.c_int, C.c_void_p]
+        pl = None
+        if pool is not None:
+            k, cur, cur_tag, nxt, nxt_tag, next_seed = pool
+            pl = self.L.ResetPool(k, *(a.ctypes.data if a is not None else None for a in (cur, cur_tag, nxt, nxt_tag)), next_seed)
+        rc = fn(C.byref(pb), C.byref(b), *self._sim_args(), _vp(ids), n, seed, _vp(rnd_ws), _vp(rnd), C.byref(pl) if pl is not None else None,
+                live_mode, _vp(skip))
+        if may_refuse:
+            lib().emu_task_reset_obs_error.restype = C.c_char_p
+            assert rc in (0, -1) and (rc == 0) == (lib().emu_task_reset_obs_error() == b""), rc
+            return rc
+        assert rc == 0, rc

@@ -31,6 +31,14 @@ extern "C" int emu_task_pd_targets(int n_env, const float *actions, const float 
     return 0;
 }
 
+// the launch of emloco_task_pd_targets_copy: the targets and (actions_copy != NULL) a copy of the actions in one pass
+extern "C" int emu_task_pd_targets_copy(int n_env, const float *actions, const float *offset, const float *scale,
+                                        const uint8_t *zero_mask, float *out, float *actions_copy) {
+    const int total = n_env * 69;
+    emu::launch((unsigned)((total + 255) / 256), 256, [&] { emloco::pd_targets_kernel(total, actions, offset, scale, zero_mask, out, actions_copy); });
+    return 0;
+}
+
 extern "C" int emu_compact_flags(const int64_t *flags, int n, int32_t *ids) {
     emu::launch(1, 1024, [&] { emloco::compact_flags_kernel(flags, n, ids, (int64_t *)nullptr); });
     return 0;
@@ -159,24 +167,31 @@ extern "C" int emu_task_reset_stages(int stages, const EmlocoResetBufs *b, const
     return 0;
 }
 
-// the reset roles of reset_obs_kernel (no live role, no pool): the reset chain of every list entry and, unless the flags say
-// EMLOCO_RESET_NO_AMP_HISTORY, its 14 history rows; random rows supplied (rnd) or made from the seed into rnd_ws (rnd = NULL)
+// emloco_task_reset_obs_pooled on the CPU: every role of reset_obs_kernel.  The pool rules, ChainArgs, the keyed reset buffers and
+// the grid are the product's own (emloco::chain_pool_error, emloco::chain_pack: what task_capi.hip calls); only the launch is the
+// emulator's.  ids holds n + 1 entries when a pool is passed (ids[n]: the number of finished envs).  -1: a refused pool argument.
+static const char *g_chain_why = "";
+static long long *g_chain_prof = nullptr;
+
+// the 16 wall-clock stamps of emloco_task_chain_profile: a host buffer that every later emu_task_reset_obs launch stamps (NULL: none)
+extern "C" void emu_task_set_chain_prof(long long *host16) { g_chain_prof = host16; }
+
+extern "C" const char *emu_task_reset_obs_error(void) { return g_chain_why; }
+
 extern "C" int emu_task_reset_obs(const EmlocoTaskBufs *pb, const EmlocoResetBufs *b, const EmlocoModelDesc *m, float *root, float *dof, float *rb,
-                                  float *contact, float *lambda_ws, const int32_t *ids, int n, uint64_t seed, float *rnd_ws, const float *rnd) {
+                                  float *contact, float *lambda_ws, const int32_t *ids, int n, uint64_t seed, float *rnd_ws, const float *rnd,
+                                  const EmlocoResetPool *pool, int live_mode, const int64_t *skip) {
+    const char *why = emloco::chain_pool_error(pool);
+    g_chain_why = why ? why : "";
+    if (why) return -1;
     EmuSimDev s;
-    if (!s.build(m, root, dof, rb, contact, lambda_ws)) return -1;
-    if (n < 1) return 0;
+    if (!s.build(m, root, dof, rb, contact, lambda_ws)) return -2;
     emloco::ChainArgs a; memset(&a, 0, sizeof(a));
-    a.n = n; a.n_slots = (int)reset_grid(n); a.h_slots = a.n_slots;
-    a.n_hist = (b->flags & EMLOCO_RESET_NO_AMP_HISTORY) ? 0 : EMLOCO_AMP_STEPS - 1;
-    a.live_mode = 0; a.reset_mode = EMLOCO_POST_OBS | EMLOCO_POST_AMP_ROW;
-    a.seeded = rnd ? 0 : 1;
-    a.seed_lo = (unsigned)(seed & 0xffffffffu); a.seed_hi = (unsigned)(seed >> 32);
-    a.ids = ids; a.rnd_in = rnd; a.rnd_ws = rnd_ws;
-    EmlocoResetBufs keyed = *b;
-    if (a.seeded) { keyed.real_pick = nullptr; keyed.real_pick_key = (uint32_t)((seed * 0xD6E8FEB86659FD93ull) >> 32); }
+    EmlocoResetBufs keyed;
+    const unsigned grid = emloco::chain_pack(*b, pb->n_env, live_mode, skip, ids, n, seed, rnd_ws, rnd, pool, g_chain_prof, &a, &keyed);
+    if (grid == 0) return 0;
     const EmlocoTaskBufs p = *pb;
     const EmlocoSimDev d = s.d;
-    emu::launch((unsigned)(a.n_slots + a.h_slots * a.n_hist), 64, [&] { emloco::reset_obs_kernel(p, keyed, d, a); });
+    emu::launch(grid, 64, [&] { emloco::reset_obs_kernel(p, keyed, d, a); });
     return 0;
 }

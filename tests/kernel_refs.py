@@ -1003,3 +1003,65 @@ def real_pick_perm(x, n, key):
 def seeded_real_key(seed):
     """the permutation key a seeded reset derives from its seed: the high word of seed x 0xD6E8FEB86659FD93 (mod 2^64)"""
     return ((seed * 0xD6E8FEB86659FD93) & 0xFFFFFFFFFFFFFFFF) >> 32
+
+
+RESET_INIT_HEADING, RESET_HEADING_INVERSION, RESET_ADJUST_ROOT_VEL, RESET_REAL_PATH = 2, 4, 8, 16
+RND_REAL, RND_INVERSION, RND_HEADING, RND_SPEED0, RND_DTHETA, RND_SHARP, RND_BERN, RND_DSPEED = 5, 7, 8, 9, 16, 116, 216, 316
+
+
+def reset_trajectory(u, ip, rv, p, flags, real=None, real_rows=None, dtype=F64):
+    """TrajGenerator.reset (traj_generator.py:60-237) for n list entries from their random rows u [n][512], start ip [n][2] and root
+    velocity rv [n][3]; p: the scalar fields of EmlocoResetBufs by name (float32 numbers).  A clamped random walk of 100 segments (the
+    first heading free, a sharp turn where the Bernoulli draw is below sharp_prob; with ADJUST_ROOT_VEL every segment's speed scaled by
+    |rv_xy| / the first speed and clamped again); with REAL_PATH and u[RND_REAL] > hybrid_prob row real_rows[i] of real [R][101][3]
+    instead, moved to ip (ADJUST_ROOT_VEL: scaled so that its first segment, at least speed_min vert_dt long, is |rv_xy| vert_dt);
+    INIT_HEADING: turned about its start so that the first segment points along rv (plus pi where HEADING_INVERSION and
+    u[RND_INVERSION] > 0.5; a zero velocity or a zero first segment counts as heading 0).  -> verts [n][101][3], inverted, is_real [n]"""
+    u, ip, rv = _c(u, dtype), _c(ip, dtype), _c(rv, dtype)
+    f = lambda k: torch.tensor(p[k], dtype=F32).to(dtype)
+    vdt, smin, smax = f("vert_dt"), f("speed_min"), f("speed_max")
+    pi = torch.tensor(math.pi, dtype=dtype)
+    n = u.shape[0]
+    adjust = bool(flags & RESET_ADJUST_ROOT_VEL)
+    hv = torch.sqrt(rv[:, 0] * rv[:, 0] + rv[:, 1] * rv[:, 1])
+    speed = (smax - smin) * u[:, RND_SPEED0] + smin
+    ratio = hv / speed
+    theta, px, py = torch.zeros(n, dtype=dtype), torch.zeros(n, dtype=dtype), torch.zeros(n, dtype=dtype)
+    verts = torch.zeros(n, 101, 3, dtype=dtype)
+    verts[:, 0, 0], verts[:, 0, 1] = ip[:, 0], ip[:, 1]
+    for i in range(100):
+        dth = (2.0 * u[:, RND_DTHETA + i] - 1.0) * (f("dtheta_max") * vdt)
+        dth = torch.where(u[:, RND_BERN + i] < f("sharp_prob"), pi * (2.0 * u[:, RND_SHARP + i] - 1.0), dth)
+        if i == 0:
+            dth = pi * (2.0 * u[:, RND_HEADING] - 1.0)
+        else:
+            speed = torch.clamp(speed + (2.0 * u[:, RND_DSPEED + i] - 1.0) * (f("accel_max") * vdt), smin, smax)
+        sp = torch.clamp(ratio * speed, smin, smax) if adjust else speed
+        theta = theta + dth
+        px, py = px + torch.cos(theta) * (sp * vdt), py - torch.sin(theta) * (sp * vdt)
+        verts[:, i + 1, 0], verts[:, i + 1, 1] = px + ip[:, 0], py + ip[:, 1]
+    is_real = torch.zeros(n, dtype=torch.bool)
+    if (flags & RESET_REAL_PATH) and real is not None and real.shape[0] > 0:
+        is_real = u[:, RND_REAL] > f("hybrid_prob")
+        src = _c(real, dtype)[torch.as_tensor(real_rows).long()]
+        sc = torch.ones(n, dtype=dtype)
+        if adjust:
+            first = torch.clamp_min((src[:, 1] - src[:, 0]).norm(dim=-1), smin * vdt)
+            sc = hv / first * vdt
+        moved = torch.cat([sc[:, None, None] * (src[:, :, :2] - src[:, :1, :2]) + ip[:, None, :], src[:, :, 2:]], dim=-1)
+        verts = torch.where(is_real[:, None, None], moved, verts)
+    inverted = torch.zeros(n, dtype=torch.bool)
+    if flags & RESET_INIT_HEADING:
+        o = verts[:, 0, :2].clone()
+        d = verts[:, 1, :2] - o
+        rmag, dmag = rv.norm(dim=-1), d.norm(dim=-1)
+        zero = torch.zeros(n, dtype=dtype)
+        root_rot = torch.where(rmag > 0, torch.atan2(rv[:, 1], rv[:, 0]), zero)
+        ih = torch.where(dmag > 0, torch.atan2(d[:, 1], d[:, 0]), zero)
+        if flags & RESET_HEADING_INVERSION:
+            inverted = u[:, RND_INVERSION] > 0.5
+        rd = torch.where(inverted, ih - root_rot + pi, ih - root_rot)
+        c, s = torch.cos(rd)[:, None], torch.sin(rd)[:, None]
+        x, y = verts[:, :, 0] - o[:, :1], verts[:, :, 1] - o[:, 1:]
+        verts = torch.stack([(x * c + y * s) + o[:, :1], (-x * s + y * c) + o[:, 1:], verts[:, :, 2]], dim=-1)
+    return verts, inverted, is_real

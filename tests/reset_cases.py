@@ -3,7 +3,10 @@ run on the CPU (tests/test_reset_matrix_cpu.py) and the device run (tests/test_g
 
 Scope: reset_sample_kernel (frame blend, slerp, rotation vectors, the random-heading turn, placement, centre-height mean), the
 kinematics of the reset envs, reset_fix_height, reset_capture_pose, reset_amp_history_kernel and reset_fill_rnd_kernel.  Trajectory
-generation is pinned to the reference goldens elsewhere; here only the real-path row pick is observed through traj_verts.
+generation is pinned to the reference goldens elsewhere; here only the real-path row pick is observed through traj_verts -- unless a
+case says traj=True (the cases of tests/chain_cases.py do): then judge_traj holds traj_verts, waypoint_traj and the inversion flag to
+kernel_refs.reset_trajectory in float64.  Such a case may also carry its own scalars of EmlocoResetBufs ("scalars"), tables
+("const": see const_of) and explicit real-path rows ("real_pick").
 
 An executor takes a case (make_case) and returns every buffer a reset may write as CPU numpy arrays (OUT_KEYS), having started from
 initial(): garbage in the simulator state, NaN / sentinels in the outputs.  judge() compares the listed envs with the float64
@@ -124,10 +127,20 @@ def cache_np():
 def scalars(case):
     """the scalar fields of EmlocoResetBufs of a case"""
     vert_dt = 168 * DT / 100.0
-    return dict(flags=case["flags"], n_motions=len(CLIP_FRAMES), n_real=N_REAL if case["flags"] & REAL_PATH else 0, n_valid=N_VALID, n_dof_subset=57,
-                hf_rows=83, hf_cols=61, fixed_x=FIXED_XY[0], fixed_y=FIXED_XY[1], dt=DT, height_tolerance=HEIGHT_TOL, vert_dt=vert_dt,
-                dtheta_max=2.0, speed_min=0.0005, speed_max=3.0, accel_max=2.0, sharp_prob=0.02, hybrid_prob=0.0 if case["flags"] & REAL_PATH else 0.5,
-                traj_dur=101 * vert_dt, sample_dt=0.4, hscale=HSCALE, vscale=VSCALE, real_pick_key=case["real_key"], amp_ring=case["amp_ring"])
+    s = dict(flags=case["flags"], n_motions=len(CLIP_FRAMES), n_real=N_REAL if case["flags"] & REAL_PATH else 0, n_valid=N_VALID, n_dof_subset=57,
+             hf_rows=83, hf_cols=61, fixed_x=FIXED_XY[0], fixed_y=FIXED_XY[1], dt=DT, height_tolerance=HEIGHT_TOL, vert_dt=vert_dt,
+             dtheta_max=2.0, speed_min=0.0005, speed_max=3.0, accel_max=2.0, sharp_prob=0.02, hybrid_prob=0.0 if case["flags"] & REAL_PATH else 0.5,
+             traj_dur=101 * vert_dt, sample_dt=0.4, hscale=HSCALE, vscale=VSCALE, real_pick_key=case["real_key"], amp_ring=case["amp_ring"])
+    s.update(case.get("scalars", {}))                            # a case's own values (tests/chain_cases.py: hybrid_prob in the middle)
+    return s
+
+
+def const_of(case):
+    """what a reset of `case` reads: the world's motion cache and real paths, with the arrays a case replaces (case["const"]: e.g. a clip
+    whose root does not move, real paths with a short or an empty first segment) -> (cache dict, real [R][101][3])"""
+    W = world()
+    over = case.get("const", {})
+    return {k: over.get(k, v) for k, v in W.cache.items()}, over.get("real_traj", W.real)
 
 
 def initial(seed=11):
@@ -283,7 +296,7 @@ def height_fix_error(pos, rot, m, gh, dtype):
     return R.lowest_collision_point(shifted, rot, *geo) - torch.as_tensor(gh).double() - float(np.float32(HEIGHT_TOL))
 
 
-def judge(case, init, out, tab, fails, shares=None, history=True, check_unlisted=True):
+def judge(case, init, out, tab, fails, shares=None, history=True, check_unlisted=True, amp_row0=True):
     """every buffer of `out` after the reset of case against the references; figures into `tab`, exact mismatches into `fails`"""
     import oracle
     W = world()
@@ -313,7 +326,7 @@ def judge(case, init, out, tab, fails, shares=None, history=True, check_unlisted
     got_mid = T("motion_ids")[env]
     if not torch.equal(got_mid[ok], mid[ok]):
         fail("motion_ids", (got_mid != mid).nonzero().reshape(-1)[:8].tolist())
-    c = W.cache
+    c, real_tab = const_of(case)
     t64 = u[:, RND_TIME].double() * c["motion_len"][mid].double()
     t32 = u[:, RND_TIME] * c["motion_len"][mid]
     got_t = T("motion_times")[env].double()
@@ -401,22 +414,57 @@ def judge(case, init, out, tab, fails, shares=None, history=True, check_unlisted
     for k in ("traj_verts", "waypoint_traj"):
         if not np.isfinite(out[k][env.numpy()]).all():
             fail(k, "not written")
+    sc = scalars(case)
+    rows = np.array([R.real_pick_perm(bi % N_REAL, N_REAL, case["real_key"]) for bi in range(n)], np.int64)
+    if case.get("real_pick") is not None:                        # explicit rows (supplied random rows only), clamped into the table
+        rows = np.clip(np.asarray(case["real_pick"][:n], np.int64), 0, N_REAL - 1)
     if flags & REAL_PATH:
         z = out["traj_verts"][env.numpy()].reshape(n, NV, 3)[:, :, 2]
-        want = np.array([R.real_pick_perm(bi % N_REAL, N_REAL, case["real_key"]) for bi in range(n)], np.float32)
+        is_real = (u[:, RND_REAL] > torch.tensor(sc["hybrid_prob"], dtype=F32)).numpy() & (sc["n_real"] > 0)
+        want = np.where(is_real, rows, 0).astype(np.float32)    # a generated path lies in the plane z = 0
         if not np.array_equal(z, np.repeat(want[:, None], NV, 1)):
             fail("real-path rows are not the permutation's", int((z[:, 0] != want).sum()))
-        if n <= N_REAL and len(set(z[:, 0].tolist())) != n:
+        if case.get("real_pick") is None and n <= N_REAL and len(set(z[is_real, 0].tolist())) != int(is_real.sum()):
             fail("real-path rows are not distinct")
+    if case.get("traj"):
+        judge_traj(case, init, out, tab, fails, env, u, root, rows, real_tab, sc)
     # ---- AMP history rows 1..14; row 0 untouched
     amp, amp0 = out["amp"][env.numpy()], init["amp"][env.numpy()]
-    if not same_bits(amp[:, phys_row(ring, 0)], amp0[:, phys_row(ring, 0)]):
+    if amp_row0 and not same_bits(amp[:, phys_row(ring, 0)], amp0[:, phys_row(ring, 0)]):
         fail("AMP row 0 changed")
     if history:
         judge_history(case, out, tab, fails, shares)
-    elif not same_bits(amp, amp0):
+    elif amp_row0 and not same_bits(amp, amp0):
         fail("AMP rows changed without the history back-fill")
+    elif not amp_row0:
+        hist = [phys_row(ring, k) for k in range(1, AMP_STEPS)]
+        if not same_bits(amp[:, hist], amp0[:, hist]):
+            fail("AMP history rows changed without the history back-fill")
     return shares
+
+
+def judge_traj(case, init, out, tab, fails, env, u, root, rows, real_tab, sc):
+    """traj_verts, waypoint_traj and inverted of the listed envs against R.reset_trajectory in float64 (from the root position and
+    velocity the reset wrote, as the kinematics are judged from the written joints); vertices relative to the start"""
+    name, n, flags = case["name"], case["n"], case["flags"]
+    fail = lambda *a: fails.append((name,) + a)
+    ip, rv = root[:, :2], root[:, 7:10]
+    use_real = real_tab if sc["n_real"] > 0 else None
+    ref, inv, _ = R.reset_trajectory(u, ip, rv, sc, flags, use_real, rows)
+    r32, _, _ = R.reset_trajectory(u, ip, rv, sc, flags, use_real, rows, dtype=F32)
+    got = torch.as_tensor(out["traj_verts"][env.numpy()]).reshape(n, NV, 3)
+    rel = lambda v: torch.cat([v[:, :, :2].double() - ip[:, None, :].double(), v[:, :, 2:].double()], dim=-1)
+    _add(tab, name, "trajectory", rel(got), rel(r32), rel(ref))
+    t = torch.arange(NS, dtype=F32)[None, :].expand(n, NS) * torch.tensor(sc["sample_dt"], dtype=F32)
+    dur = float(np.float32(sc["traj_dur"]))
+    w64, w32 = R.traj_calc_pos(got, t, dur), R.traj_calc_pos(got, t, dur, dtype=F32)
+    relw = lambda v: v.double().reshape(n, NS, 3) - torch.cat([ip.double(), torch.zeros(n, 1, dtype=F64)], dim=1)[:, None, :]
+    _add(tab, name, "waypoints", relw(torch.as_tensor(out["waypoint_traj"][env.numpy()])), relw(w32), relw(w64))
+    if (flags & INIT_HEADING) and (flags & HEADING_INVERSION):
+        if not np.array_equal(out["inverted"][env.numpy()], inv.numpy().astype(np.uint8)):
+            fail("inverted is not (u > 0.5)")
+    elif not np.array_equal(out["inverted"][env.numpy()], init["inverted"][env.numpy()]):
+        fail("inverted written without INIT_HEADING | HEADING_INVERSION")
 
 
 def judge_history(case, out, tab, fails, shares):
@@ -424,7 +472,7 @@ def judge_history(case, out, tab, fails, shares):
     W = world()
     name, n, ring = case["name"], case["n"], case["amp_ring"]
     env = torch.as_tensor(case["ids"][:n]).long()
-    c = W.cache
+    c, _ = const_of(case)
     K = AMP_STEPS - 1
     mid = torch.as_tensor(out["motion_ids"])[env].repeat_interleave(K)
     mt = torch.as_tensor(out["motion_times"])[env].repeat_interleave(K)

@@ -276,7 +276,7 @@ def test_fused_launch_observation_role_equals_the_post_physics_launch(golden):
     assert np.all(hosts[1].obs[[2, 7, 8]] == -5.0) and np.all(hosts[1].obs[0] != -5.0)
 
 
-def test_flags_launch_with_the_return_bookkeeping_equals_the_two_launches(golden):
+def _flags_launch_with_the_return_bookkeeping(golden, with_inverted):
     """post_physics_returns_kernel (emloco_task_post_physics_returns: the LocoVal return bookkeeping of an env right behind its reward
     and reset flag, one launch) against post_physics_kernel followed by locoval_returns_kernel on its outputs: task buffers, return
     accumulators, staged LocoVal inputs, targets and weights byte for byte, over several steps with episodes ending."""
@@ -306,6 +306,7 @@ def test_flags_launch_with_the_return_bookkeeping_equals_the_two_launches(golden
     lib.emu_locoval_returns.argtypes = [C.c_void_p] * 5
     lib.emu_task_post_physics_returns.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     inv = (rng.random(E) < 0.4).astype(np.uint8)
+    pinv = p(inv) if with_inverted else None                          # the inversion flags are optional (NULL: no env is inverted)
     emitted = 0
     for t in range(9):
         dof, frc = rng.normal(size=(E, 69, 2)).astype(np.float32), (rng.normal(size=(E, 69)) * 30).astype(np.float32)
@@ -316,15 +317,23 @@ def test_flags_launch_with_the_return_bookkeeping_equals_the_two_launches(golden
         (tha, sta), (thb, stb) = sides
         tha.post_physics(mode)
         rew, dones = np.ascontiguousarray(tha.rew), np.ascontiguousarray(tha.reset)
-        lib.emu_locoval_returns(C.addressof(steps[0]), p(rew), None, p(dones), p(inv))
+        lib.emu_locoval_returns(C.addressof(steps[0]), p(rew), None, p(dones), pinv)
         bb = thb.bufs()
-        assert lib.emu_task_post_physics_returns(C.byref(bb), mode, C.addressof(steps[1]), p(inv)) == 0
+        assert lib.emu_task_post_physics_returns(C.byref(bb), mode, C.addressof(steps[1]), pinv) == 0
         for name in ("progress", "reset", "terminate", "rew", "reward_raw", "amp"):
             np.testing.assert_array_equal(getattr(tha, name), getattr(thb, name), err_msg=f"{name} step {t}")
         for k in sta:
             np.testing.assert_array_equal(sta[k], stb[k], err_msg=f"{k} step {t}")
         emitted += int((sta["weight"] != 0).sum())
     assert emitted > 0 and int((sides[0][0].reset != 0).sum()) >= 0
+
+
+def test_flags_launch_with_the_return_bookkeeping_equals_the_two_launches(golden):
+    _flags_launch_with_the_return_bookkeeping(golden, True)
+
+
+def test_flags_launch_with_the_return_bookkeeping_without_inversion_flags(golden):
+    _flags_launch_with_the_return_bookkeeping(golden, False)
 
 
 def test_pd_targets_kernel_matches_reference_golden(golden):

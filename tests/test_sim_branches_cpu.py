@@ -39,77 +39,36 @@ Leaving any other new scene out fails the test and names the line (`python tests
     without ties_at_the_20th_contact        sim_kernels.hip: 3 (allowed 1) x `if (act[s] && (cdist[s] > best || (cdist[s] == best && ...`
     without joint_angles_at_and_beyond_pi   sim_math.h: 1 (allowed 0) x `const float sgn = (((long)kf) & 1) ? -1.0f : 1.0f;`
 """
-import collections
-import glob
 import json
 import os
 import shutil
 import subprocess
-import sys
 
 import pytest
 
+import gcov_branches as G
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-BUILD = os.path.join(HERE, "emu", "_build")
 ALLOW = os.path.join(HERE, "golden", "sim_branches_allow.json")
 FILES = ("sim_kernels.hip", "sim_math.h", "dev_math.h", "fk_device.h")        # (sim_pair_kernels.hip: an unshipped experiment)
+EXTRA = "--coverage"
 
 
 def run_table(extra_args=()):
-    """The scene table in a fresh child (tests/emu reads EMLOCO_EMU_EXTRA at import); returns its output.  Counters of earlier runs
-    are removed first: gcov adds up."""
-    for f in glob.glob(os.path.join(BUILD, "libemu_coverage*.gcda")):
-        os.remove(f)
-    env = dict(os.environ, EMLOCO_EMU_EXTRA="--coverage", PYTHONPATH=os.pathsep.join([ROOT, HERE] + sys.path))
-    env.pop("EMLOCO_EMU_PARTS", None)
-    r = subprocess.run([sys.executable, os.path.join(HERE, "sim_branch_cases.py"), *extra_args], cwd=HERE, env=env,
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout[-4000:]
-    return r.stdout
+    """The scene table in a fresh child (tests/gcov_branches.py); returns its output."""
+    return G.run_child("sim_branch_cases.py", EXTRA, extra_args)
 
 
 def gcov_tables():
-    """{file: (lines executed, lines, {(line number, branch index): summed count}, source lines)} from `gcov -b -c` on emu_sim"""
-    gcno = glob.glob(os.path.join(BUILD, "libemu_coverage*emu_sim.gcno"))
-    assert gcno, "the coverage build left no notes file for emu_sim"
-    newest = max(gcno, key=os.path.getmtime)                                   # a rebuild leaves the older notes behind
-    out = subprocess.run(["gcov", "-b", "-c", "--json-format", "--stdout", os.path.basename(newest)], cwd=BUILD,
-                         stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True, check=True).stdout
-    res = {}
-    for doc in out.splitlines():
-        if not doc.startswith("{"):
-            continue
-        for f in json.loads(doc)["files"]:
-            base = os.path.basename(f["file"])
-            if base not in FILES:
-                continue
-            lines, br = collections.defaultdict(int), collections.defaultdict(int)
-            for ln in f["lines"]:                                              # one entry per function instance that holds the line
-                lines[ln["line_number"]] += ln["count"]
-                for k, b in enumerate(x for x in ln["branches"] if not x["throw"]):
-                    br[(ln["line_number"], k)] += b["count"]
-            path = f["file"] if os.path.isabs(f["file"]) else os.path.normpath(os.path.join(BUILD, f["file"]))
-            with open(path) as src:
-                res[base] = (sum(1 for v in lines.values() if v), len(lines), dict(br), src.read().splitlines())
-    assert set(res) == set(FILES), sorted(res)
-    return res
+    """`gcov -b -c` on the emulator's emu_sim object"""
+    return G.gcov_tables(EXTRA, ("emu_sim",), FILES)
 
 
-def never_taken(tables):
-    """{(file, stripped source text): number of never-taken branches on that line}"""
-    out = collections.Counter()
-    for base, (_, _, br, src) in tables.items():
-        for (line, _), count in br.items():
-            if count == 0:
-                out[(base, src[line - 1].strip())] += 1
-    return out
+never_taken = G.never_taken
 
 
 def report(tables):
-    for base in FILES:
-        ex, n, br, _ = tables[base]
-        print(f"{base}: {ex} / {n} lines executed, {sum(1 for v in br.values() if v)} / {len(br)} branches taken")
+    G.report(tables, FILES)
 
 
 @pytest.mark.skipif(shutil.which("gcov") is None or shutil.which("g++") is None, reason="gcov / g++ not on this machine")

@@ -84,6 +84,23 @@ def test_emulated_entry_refuses_bad_arguments():
         assert (out == 7.0).all()                                     # nothing was launched
 
 
+def test_emulated_entry_refuses_null_tables_a_bad_count_an_unknown_flag_and_non_finite_queries():
+    """the refusals of densify_pack that the table above does not reach"""
+    P = lambda a: C.c_void_p(a.ctypes.data)
+    k, q = np.arange(13, dtype=np.float32), np.ascontiguousarray(TC.QUERY_101, np.float32)
+    bad_q = q.copy()
+    bad_q[50] = np.inf
+    way, out = np.ones((2, 13, 3), np.float32), np.full((2, q.size, 3), 7.0, np.float32)
+    fn = emu.lib().emu_traj_densify
+    for args, word in (((None, 13, P(way), C.c_int64(2), P(q), q.size, P(out), None, 0), "null"),
+                       ((P(k), 13, P(way), C.c_int64(2), None, q.size, P(out), None, 0), "null"),
+                       ((P(k), 13, P(way), C.c_int64(-1), P(q), q.size, P(out), None, 0), "n_traj"),
+                       ((P(k), 13, P(way), C.c_int64(2), P(q), q.size, P(out), None, 2), "flag"),
+                       ((P(k), 13, P(way), C.c_int64(2), P(bad_q), q.size, P(out), None, 0), "finite")):
+        assert fn(*args) == -1 and word in emu.lib().emu_traj_densify_error().decode(), (word, emu.lib().emu_traj_densify_error())
+        assert (out == 7.0).all()
+
+
 # ------------------------------------------------------------------------------------------------------------ the float64 host path
 @pytest.mark.parametrize("shape", list(TC.SHAPES))
 def test_host_path_matches_scipy(shape):
