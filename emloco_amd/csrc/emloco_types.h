@@ -66,4 +66,8 @@ struct EmlocoSimDev {
     int part_spin_max;                /* bound of a part's wait for its predecessor, in 16 x 64-clock sleeps (default 1 << 22: seconds) */
     int part_poison;                  /* test hook (emloco_sim_debug_poison_part): the first part of this env withholds its hand-over; -1: none */
     unsigned long long *step_start;   /* diagnostic (emloco_sim_cost_ticks): wall clock at the start of each env's workgroup, else NULL */
+    // part plan of the full launch (emloco_sim_set_plan, sim_plan.h): one word per workgroup -- which rank, which substeps, whether it
+    // consumes / publishes a hand-over or finishes the step.  NULL: the uniform split of n_parts (part = workgroup / n_env)
+    const unsigned *plan;
+    int plan_n;                       /* words of the plan = workgroups of the launch */
 };

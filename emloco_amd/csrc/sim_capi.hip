@@ -18,6 +18,7 @@
 #include "topology.h"
 #include "model_pack.h"
 #include "sim_state.h"
+#include "sim_plan.h"
 
 namespace {
 
@@ -87,7 +88,7 @@ int emloco_sim_destroy(EmlocoSim *s) {
     s->d_root.release(); s->d_dof.release(); s->d_tgt.release(); s->d_rb.release();
     s->d_cf.release(); s->d_df.release(); s->d_lws.release();
     s->d_ticks.release(); s->d_order.release(); s->d_order_ws.release();
-    s->d_part_state.release(); s->d_part_flag.release();
+    s->d_part_state.release(); s->d_part_flag.release(); s->d_plan.release();
     if (s->h_err) (void)hipHostFree(s->h_err);
     for (auto e : s->ev0) (void)hipEventDestroy(e);
     for (auto e : s->ev1) (void)hipEventDestroy(e);
@@ -318,6 +319,9 @@ static int launch_order(EmlocoSim *s, hipStream_t st) {
     return EMLOCO_OK;
 }
 
+// the part plan holds for the substep count it was built for (emloco_sim_set_plan); a launch of another one takes the uniform split
+static bool use_plan(const EmlocoSim *s, int n_sub) { return s->plan_n > 0 && s->plan_n_sub == n_sub; }
+
 int emloco_sim_step(EmlocoSim *s, int n_calls, void *stream) {
     if (!s) return fail(EMLOCO_E_ARG, "emloco_sim_step: null sim");
     if (!s->prepared) return fail(EMLOCO_E_STATE, "emloco_sim_step: sim not prepared");
@@ -340,7 +344,8 @@ int emloco_sim_step(EmlocoSim *s, int n_calls, void *stream) {
     d.part_seq = ++s->part_seq; d.part_state = s->d_part_state.p; d.part_flag = s->d_part_flag.p;
     d.part_spin_max = s->part_spin_max; d.part_poison = s->part_poison;
     d.n_slots = s->n_env;
-    const unsigned grid = (unsigned)(((s->n_env + EMLOCO_SIM_ENVS_PER_WG - 1) / EMLOCO_SIM_ENVS_PER_WG) * d.n_parts);       // one 64-lane workgroup per env (pair) and part
+    unsigned grid = (unsigned)(((s->n_env + EMLOCO_SIM_ENVS_PER_WG - 1) / EMLOCO_SIM_ENVS_PER_WG) * d.n_parts);       // one 64-lane workgroup per env (pair) and part
+    if (use_plan(s, p.n_sub)) { d.plan = s->d_plan.p; d.plan_n = s->plan_n; grid = (unsigned)s->plan_n; }             // or one per word of the plan
     if (d.hf) hipLaunchKernelGGL(emloco::sim_step_kernel<1>, dim3(grid), dim3(64), (size_t)s->lds_pad, st, p, d);
     else hipLaunchKernelGGL(emloco::sim_step_kernel<0>, dim3(grid), dim3(64), (size_t)s->lds_pad, st, p, d);
     HIPCHK(hipGetLastError());
@@ -382,7 +387,8 @@ int emloco_sim_step_subset(EmlocoSim *s, int n_calls, const int64_t *dev_skip, c
     d.part_seq = ++s->part_seq; d.part_state = s->d_part_state.p; d.part_flag = s->d_part_flag.p;
     d.part_spin_max = s->part_spin_max; d.part_poison = s->part_poison;
     d.n_slots = dev_ids ? n_ids : s->n_env;
-    const unsigned grid = (unsigned)(((d.n_slots + EMLOCO_SIM_ENVS_PER_WG - 1) / EMLOCO_SIM_ENVS_PER_WG) * d.n_parts);      // one 64-lane workgroup per slot (pair) and part
+    unsigned grid = (unsigned)(((d.n_slots + EMLOCO_SIM_ENVS_PER_WG - 1) / EMLOCO_SIM_ENVS_PER_WG) * d.n_parts);      // one 64-lane workgroup per slot (pair) and part
+    if (!dev_ids && use_plan(s, p.n_sub)) { d.plan = s->d_plan.p; d.plan_n = s->plan_n; grid = (unsigned)s->plan_n; }  // the list launch takes no plan either
     if (d.hf) hipLaunchKernelGGL(emloco::sim_step_kernel<1>, dim3(grid), dim3(64), (size_t)s->lds_pad, st, p, d);
     else hipLaunchKernelGGL(emloco::sim_step_kernel<0>, dim3(grid), dim3(64), (size_t)s->lds_pad, st, p, d);
     HIPCHK(hipGetLastError());
@@ -407,6 +413,28 @@ int emloco_sim_set_split(EmlocoSim *s, int n_parts) {
         HIPCHK(hipMemset(s->d_part_flag.p, 0, sizeof(unsigned) * (size_t)s->n_env));
     }
     s->n_parts = n_parts;
+    s->plan_n = 0;                              // back to the uniform split; the table stays allocated for the next plan
+    return EMLOCO_OK;
+}
+
+int emloco_sim_set_plan(EmlocoSim *s, const int32_t *classes, int n_classes, int tail, int shift, int n_calls) {
+    if (!s) return fail(EMLOCO_E_ARG, "emloco_sim_set_plan: null sim");
+    if (!s->prepared) return fail(EMLOCO_E_STATE, "emloco_sim_set_plan: sim not prepared");
+    if (EMLOCO_SIM_ENVS_PER_WG != 1) return fail(EMLOCO_E_ARG, "emloco_sim_set_plan: one env per workgroup only");
+    if (n_calls < 1 || n_calls > EMLOCO_PLAN_MAX_SUB) return fail(EMLOCO_E_ARG, "emloco_sim_set_plan: n_calls < 1 or beyond 7");
+    const int n_sub = s->prm.n_sub * n_calls;            // the substeps of the launches the plan is for: emloco_sim_step(sim, n_calls)
+    std::vector<unsigned> plan;
+    if (const char *why = emloco::sim_plan_build(s->n_env, n_sub, (const int *)classes, n_classes, tail, shift, plan))
+        return fail(EMLOCO_E_ARG, (std::string("emloco_sim_set_plan: ") + why).c_str());
+    // the checker stands between every plan and the device, whoever built it
+    if (const char *why = emloco::sim_plan_check(plan.data(), (int)plan.size(), s->n_env, n_sub))
+        return fail(EMLOCO_E_ARG, (std::string("emloco_sim_set_plan: the plan fails its check: ") + why).c_str());
+    if (const int rc = emloco_sim_set_split(s, 4)) return rc;          // the hand-over buffers; n_parts = 4 serves the launches the plan does not cover
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipDeviceSynchronize());                                   // no launch in flight reads the table that is replaced
+    if (s->d_plan.n < plan.size()) { s->d_plan.release(); HIPCHK(s->d_plan.alloc(plan.size())); }
+    HIPCHK(hipMemcpy(s->d_plan.p, plan.data(), sizeof(unsigned) * plan.size(), hipMemcpyHostToDevice));
+    s->plan_n = (int)plan.size(); s->plan_n_sub = n_sub;
     return EMLOCO_OK;
 }
 
@@ -481,9 +509,9 @@ int emloco_sim_fk_indexed(EmlocoSim *s, const int32_t *ids, int n, void *stream)
 
 // internal diagnostic: the per-env durations (100 MHz ticks) the cost-ordered dispatch sorts by and, from the second call on,
 // the wall clock at which each env's workgroup started in the latest launch [2][n_env] -- in a schedule-trace build
-// (-DEMLOCO_SIM_SCHED=1) the four stamps of every workgroup instead, [4 parts][n_env][4] (sim_kernels.hip, SCHED_HANDED)
+// (-DEMLOCO_SIM_SCHED=1) the four stamps of every workgroup instead, [5 parts][n_env][4] (sim_kernels.hip, SCHED_HANDED)
 #ifdef EMLOCO_SIM_SCHED
-#define EMLOCO_STEP_START_WORDS 16
+#define EMLOCO_STEP_START_WORDS 20
 #else
 #define EMLOCO_STEP_START_WORDS 2
 #endif

@@ -33,6 +33,7 @@
 #include "emloco_types.h"
 #include "fk_device.h"
 #include "order_device.h"
+#include "sim_plan.h"
 
 namespace emloco {
 
@@ -146,8 +147,8 @@ __device__ __forceinline__ void ld4(const float *base, int off, float *v) {
 #endif
 
 // Schedule trace (diagnostic build -DEMLOCO_SIM_SCHED=1, tools/exp/sim_sched.py): with the start stamps switched on
-// (emloco_sim_cost_ticks) every workgroup leaves four words in step_start [n_parts][n_env][4] -- wall clock at its first
-// instruction, once its predecessor's hand-over is in, at its last instruction, and part | dispatch slot << 8.
+// (emloco_sim_cost_ticks) every workgroup leaves four words in step_start [5 parts][n_env][4] -- wall clock at its first
+// instruction, once its predecessor's hand-over is in, at its last instruction, and part | rank << 8 | workgroup index << 32.
 #ifdef EMLOCO_SIM_SCHED
 #define SCHED_HANDED() do { if (d.step_start && threadIdx.x == 0) d.step_start[((size_t)part * d.n_env + env) * 4 + 1] = (unsigned long long)wall_clock64(); } while (0)
 #else
@@ -319,7 +320,7 @@ __device__ __noinline__ void mesh_walls(const EmlocoSimDev &d, const float P[3],
 #endif
 // one env's step: the body of both kernels below (one 64-lane wave)
 template <int HF>
-__device__ __forceinline__ void sim_step_env(const EmlocoSimParams &prm, const EmlocoSimDev &d, const int env, int &work, const int part, const int n_parts) {
+__device__ __forceinline__ void sim_step_env(const EmlocoSimParams &prm, const EmlocoSimDev &d, const int env, int &work, const SimPlanWork &pw) {
     int lane = threadIdx.x;                                   // redefined at every phase boundary (FRESH_LANE)
     work = 0;                                                 // contact work of this step: sum over substeps of (10 + contacts) where there are any
 
@@ -405,12 +406,15 @@ __device__ __forceinline__ void sim_step_env(const EmlocoSimParams &prm, const E
     // root, momentum balance, multipliers and their slot map: plain copies, so the parts together are the fused step bit
     // for bit).  Parts are workgroups of ONE launch, the later ones at higher indices: the wave slots that the first
     // parts of short envs free early are taken by second parts instead of idling until the launch's last workgroup ends.
-    const int sub_lo = (prm.n_sub * part) / n_parts, sub_hi = (prm.n_sub * (part + 1)) / n_parts;
+    // Which substeps, and whether the workgroup takes a hand-over, leaves one or finishes the step, is the launch's part plan
+    // (sim_plan.h): the uniform split, or the table of emloco_sim_set_plan -- there a part may hold two substeps, or none: the
+    // tail part, which enters the loop once for the final kinematics pass and writes back.
+    const int part = pw.part(), sub_lo = pw.sub_lo, sub_hi = pw.sub_hi;
     float *pst = d.part_state ? d.part_state + (long)env * EMLOCO_PART_WORDS : nullptr;
     // (the rotation vectors edof could wait in LDS -- they are read twice per substep -- but 96 more words put the 13th KB on the
     // env's LDS and cost the twelfth resident env per CU: measured slower than letting the compiler park them in scratch)
     float qj[4] = {0, 0, 0, 1}, wj[3] = {0, 0, 0}, edof[3] = {0, 0, 0};
-    if (part == 0) {
+    if (!pw.consumes()) {
         if ((lane < NB) && lane >= 1) {
             const float *ds = dofs_env + jdof * 2;
             float e[3] = {ds[0], ds[2], ds[4]};
@@ -474,7 +478,7 @@ __device__ __forceinline__ void sim_step_env(const EmlocoSimParams &prm, const E
                            // With it the torque report of the last substep needs no tau: three registers fewer across the contact phases
     float uh[3], qdd[3];
 
-    for (int sub = sub_lo; sub < sub_hi + (part == n_parts - 1 ? 1 : 0); ++sub) {
+    for (int sub = sub_lo; sub < sub_hi + (pw.final() ? 1 : 0); ++sub) {
         const bool final_pass = (sub == prm.n_sub);   // kinematics only, to write the body states
         const bool last = (sub == prm.n_sub - 1);
 
@@ -1654,8 +1658,8 @@ __device__ __forceinline__ void sim_step_env(const EmlocoSimParams &prm, const E
         ld4(mdl, o_dyn, jm);
     }
 
-    if (part < n_parts - 1) {         // hand over to the next part (see part_ld80): store the tagged granules and leave
-        if (part == 0 && env == d.part_poison) return;             // test hook: this env's first part publishes nothing
+    if (pw.publishes()) {             // hand over to the next part (see part_ld80): store the tagged granules and leave
+        if (!pw.consumes() && env == d.part_poison) return;        // test hook: this env's first part publishes nothing
         const float tg = __uint_as_float(EMLOCO_PART_TAG(d.part_seq, part));
         float w[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         if ((lane < NB)) { w[0] = qj[0]; w[1] = qj[1]; w[2] = qj[2]; w[3] = qj[3]; }
@@ -1718,16 +1722,18 @@ template <int HF>
 __global__ void __attribute__((amdgpu_flat_work_group_size(64, 64), amdgpu_waves_per_eu(EMLOCO_SIM_WAVES_PER_SIMD, EMLOCO_SIM_WAVES_PER_SIMD)))
 sim_step_kernel(EmlocoSimParams prm, EmlocoSimDev d) {
     const int n_parts = d.n_parts > 1 ? d.n_parts : 1;
-    const int part = (int)blockIdx.x / d.n_env, slot = (int)blockIdx.x - part * d.n_env;     // all first parts, then all second parts
-    if (part >= n_parts) return;
+    // the uniform split (all first parts, then all second parts, ...) or this workgroup's word of the part plan (sim_plan.h)
+    const SimPlanWork pw = sim_plan_decode(d.plan, d.plan_n, blockIdx.x, d.n_env, n_parts, prm.n_sub);
+    const int part = pw.part(), slot = pw.slot;
+    if (!pw.valid) return;
     int env = d.step_order ? d.step_order[slot] : slot;
     if (d.step_ids) { env = d.step_ids[slot]; if (env < 0) return; }   // list launch: workgroup i steps list entry i (-1: padding)
     if (d.step_skip && d.step_skip[env] != 0) return;            // flagged envs are stepped elsewhere
     env = __builtin_amdgcn_readfirstlane(env);                   // workgroup-uniform: the env's bases live in scalar registers
     const long long t0 = d.step_start ? (long long)wall_clock64() : 0ll;
     int work;
-    sim_step_env<HF>(prm, d, env, work, part, n_parts);
-    if (d.step_ticks && threadIdx.x == 0 && part == n_parts - 1) {
+    sim_step_env<HF>(prm, d, env, work, pw);
+    if (d.step_ticks && threadIdx.x == 0 && pw.final()) {
         // the key of the next launch's order: EMLOCO_COST_KEY_TICKS (diagnostic build) = measured duration in 5.12 us units
 #ifdef EMLOCO_COST_KEY_TICKS
         d.step_ticks[env] = (unsigned)(((long long)wall_clock64() - t0) >> 9);
@@ -1741,7 +1747,7 @@ sim_step_kernel(EmlocoSimParams prm, EmlocoSimDev d) {
 #ifdef EMLOCO_SIM_SCHED
     if (d.step_start && threadIdx.x == 0) {
         unsigned long long *ss = d.step_start + ((size_t)part * d.n_env + env) * 4;
-        ss[0] = (unsigned long long)t0; ss[2] = (unsigned long long)wall_clock64(); ss[3] = (unsigned long long)(part | slot << 8);
+        ss[0] = (unsigned long long)t0; ss[2] = (unsigned long long)wall_clock64(); ss[3] = (unsigned long long)(part | slot << 8) | (unsigned long long)blockIdx.x << 32;
     }
 #endif
 }
@@ -1758,6 +1764,13 @@ sim_step_kernel(EmlocoSimParams prm, EmlocoSimDev d) {
 // fill and drain at its two ends.  Its length is therefore set by what the LAST workgroups of each part cost: with the
 // expensive envs (many contacts) first and the cheap ones (airborne) last, the slots that free up late receive short work.
 // The order within a bucket is whatever the LDS atomics give -- envs are independent, results do not depend on it.
+// Where that empty slot-time lies (profiles/r10_sim_launch_plan.txt): 0.1 % before the first slot turns over, 2 % in the
+// middle, 15 % after the last workgroup has been dispatched -- 5.33 rounds of near-equal jobs leave the last round a third
+// full, and its jobs were the longest of the launch (the last part carries the final pass and the write-back).  Under a part
+// plan (emloco_sim_set_plan, sim_plan.h) the position in this order is a RANK and the plan's table says which workgroup
+// runs which substeps of which rank: the default plan gives every env a fifth, short workgroup for the final pass and the
+// write-back, and starts the cheaper half of this order one stage ahead of the other half, so that the stages of the two
+// halves interleave instead of ending together.
 __global__ void __launch_bounds__(1024)
 sim_order_kernel(const unsigned *ticks, int n, int *order, unsigned char *bucket_ws) {
     order_sort(ticks, n, order, bucket_ws);             // order_device.h

@@ -49,6 +49,10 @@ struct EmlocoSim {
     DevBuf<unsigned> d_part_flag;
     unsigned *h_err = nullptr;                 // device error word in pinned host memory (kernels raise bits with system-scope atomics)
     int part_spin_max = 1 << 22, part_poison = -1;
+    // part plan of the full launch (emloco_sim_set_plan, sim_plan.h): built and checked on the host for plan_n_sub substeps, uploaded once;
+    // plan_n = 0: none, the uniform split of n_parts
+    DevBuf<unsigned> d_plan;
+    int plan_n = 0, plan_n_sub = 0;
     int lds_pad = 0;                           // diagnostic (EMLOCO_SIM_LDS_PAD): extra dynamic LDS per workgroup of the step launch, caps the residency
     bool cost_order = false;
     bool order_ready = false;                   // d_order already holds the next full launch's order (emloco_task_compact_done_order sorted it)

@@ -43,6 +43,34 @@ def dptr(t):
     return C.c_void_p(t.data_ptr())
 
 
+def plan_from_spec(spec, n_env, n_sub, parts=4):
+    """Arguments of NativeSim.set_plan from a short description, or None for "0" / "" (the uniform split).  Terms joined by "+":
+    "T" = tail part; "C<K>" = the last K ranks (the cheapest envs of the cost order) run two parts of n_sub / 2 substeps, the others
+    `parts`; "S<K>:<shift>" = the last K ranks keep `parts` parts but stand <shift> stages later in the index order.  K is a count or
+    a share ("25%").  Example: "T+C1024"."""
+    spec = (spec or "").strip()
+    if spec in ("", "0"):
+        return None
+    parts = min(parts, n_sub)
+    tail, shift, k, light_parts = False, 0, 0, parts
+    for term in spec.split("+"):
+        term = term.strip()
+        if term == "T":
+            tail = True
+            continue
+        if not term or term[0] not in "CS":
+            raise L.EmlocoError(f"part plan {spec!r}: unknown term {term!r}")
+        body, _, sh = term[1:].partition(":")
+        k = int(round(n_env * float(body[:-1]) / 100.0)) if body.endswith("%") else int(body)
+        k = max(0, min(n_env, k))
+        if term[0] == "C":
+            light_parts = max(1, parts // 2)
+        else:
+            shift = int(sh or 1)
+    classes = [(0, n_env - k, parts), (n_env - k, n_env, light_parts)] if k else [(0, n_env, parts)]
+    return classes, tail, shift
+
+
 class NativeSim:
     def __init__(self, models, params=None, device_index=0, self_collision=None, heightfield=None):
         """`self_collision`: None / False = off; True = limb-limb contacts with the defaults of
@@ -106,6 +134,7 @@ class NativeSim:
         self.dof_force = self._tensor(L.T_DOF_FORCE).view(-1)
         self.pd_target = self._tensor(L.T_PD_TARGET)
         self.warm_start = self._tensor(L.T_WARM_START)
+        self._plan_spec, self._plan_parts, self._plan_calls = None, 4, 0       # set_plan_spec
 
     def _tensor(self, kind):
         ptr = C.c_void_p()
@@ -127,6 +156,8 @@ class NativeSim:
         L.check(self.lib.emloco_sim_set_dof_actuation_force(self._h, dptr(forces), self._stream()), "emloco_sim_set_dof_actuation_force")
 
     def step(self, n_calls=1):
+        if self._plan_spec is not None and self._plan_calls != n_calls:
+            self._plan_for(n_calls)
         L.check(self.lib.emloco_sim_step(self._h, int(n_calls), self._stream()), "emloco_sim_step")
 
     def set_cost_order(self, on=True):
@@ -134,8 +165,34 @@ class NativeSim:
         L.check(self.lib.emloco_sim_set_cost_order(self._h, int(bool(on))), "emloco_sim_set_cost_order")
 
     def set_split(self, n_parts=2):
-        """The substeps of a step as `n_parts` dependent workgroups per env in one launch (emloco_sim_set_split)."""
+        """The substeps of a step as `n_parts` dependent workgroups per env in one launch (emloco_sim_set_split); clears a plan."""
         L.check(self.lib.emloco_sim_set_split(self._h, int(n_parts)), "emloco_sim_set_split")
+        self._plan_spec = None
+
+    def set_plan(self, classes, tail=False, shift=0, n_calls=1):
+        """The full launch by a part plan (emloco_sim_set_plan): `classes` = [(lo, hi, parts), ...] tiling the ranks [0, num_envs);
+        `tail`: a further workgroup per env for the final pass and the write-back; `shift`: stages by which the classes behind the
+        first stand later in the index order; `n_calls`: the plan is for step(n_calls) launches.  set_split() goes back to the
+        uniform split."""
+        flat = np.ascontiguousarray(np.asarray(classes, dtype=np.int32).reshape(-1, 3))
+        L.check(self.lib.emloco_sim_set_plan(self._h, flat.ctypes.data_as(C.POINTER(C.c_int32)), int(flat.shape[0]), int(bool(tail)), int(shift),
+                                             int(n_calls)), "emloco_sim_set_plan")
+        self._plan_spec = None
+
+    def set_plan_spec(self, spec, parts=4):
+        """A part plan by description (plan_from_spec), set for whatever n_calls the steps that follow are issued with: the plan is
+        built at the first step, and again when n_calls changes; where the substeps of a step do not divide into the plan's parts the
+        uniform split stays.  "0" / "": none."""
+        self._plan_spec, self._plan_parts, self._plan_calls = (spec if plan_from_spec(spec, self.num_envs, 4) is not None else None), parts, 0
+
+    def _plan_for(self, n_calls):
+        plan = plan_from_spec(self._plan_spec, self.num_envs, int(self.get_params().n_sub) * n_calls, self._plan_parts)
+        spec = self._plan_spec
+        try:
+            self.set_plan(*plan, n_calls=n_calls)
+        except L.EmlocoError:                        # e.g. five substeps: no plan for these steps, the split of set_split stays
+            pass
+        self._plan_spec, self._plan_calls = spec, n_calls
 
     def step_subset(self, n_calls=1, skip=None, ids=None):
         """The step for a subset of the envs on the current stream: `skip` (int64 per env) leaves the flagged envs alone,
@@ -144,6 +201,8 @@ class NativeSim:
             assert skip.dtype == torch.int64 and skip.numel() == self.num_envs
         if ids is not None:
             assert ids.dtype == torch.int32
+        elif self._plan_spec is not None and self._plan_calls != n_calls:
+            self._plan_for(n_calls)
         L.check(self.lib.emloco_sim_step_subset(self._h, int(n_calls), dptr(skip), dptr(ids), 0 if ids is None else int(ids.numel()),
                                                 self._stream()), "emloco_sim_step_subset")
 

@@ -177,6 +177,25 @@ int emloco_sim_step_subset(EmlocoSim *sim, int n_calls, const int64_t *dev_skip,
  * slots of the cheap ones idle until the last workgroup ends; with parts they are refilled at half / quarter granularity.
  * n_sub * n_calls must be a multiple of n_parts to split evenly (otherwise the parts are uneven, still correct). */
 int emloco_sim_set_split(EmlocoSim *sim, int n_parts);
+/* Part plan of the full launches (extension, off by default; results do not depend on it).  The split launch as a table: which
+ * workgroup runs which substeps of which env, instead of "all first parts, then all second parts".  Position in the dispatch
+ * order is a RANK (rank = env id, or the position in the cost order when emloco_sim_set_cost_order is on: the most expensive
+ * envs have the lowest ranks).  `classes`: n_classes (1 .. 8) triples {lo, hi, parts} that tile the ranks [0, n_env) in
+ * ascending order (lo of the first = 0, lo of each = hi of the one before, hi of the last = n_env; hi = lo is an empty class);
+ * the envs of a class run their n_sub substeps as `parts` (1 .. 4) equal parts of 1, 2 or 4 substeps.  `tail` (0 / 1): every
+ * env gets one more workgroup that does only the final kinematics pass and the write-back, so that the launch ends on its
+ * shortest jobs.  `shift` (-4 .. 4): the parts of every class but the first stand that many stages later (negative: earlier) in
+ * the index order; stage j holds the j-th workgroups of all envs, in rank order.  The plan is built for the launches of
+ * emloco_sim_step(sim, n_calls), that is for n_sub * n_calls substeps (n_sub: EmlocoSimParams at the time of the call; the "n_sub"
+ * of this paragraph is that product), checked on the host -- every substep of every rank exactly once and in order, one
+ * final workgroup per rank, every consumer at a higher workgroup index than its producer, at most four publishing parts --
+ * and uploaded once; the call synchronises the device.  It allocates the hand-over buffers like emloco_sim_set_split(4), and
+ * launches it does not cover run as that split: steps with another n_sub * n_calls than the plan was built for, and the
+ * id-list launches of emloco_sim_step_subset (never split).  Skip flags work under a plan as under a split.
+ * emloco_sim_set_split clears the plan.  Refusals: EMLOCO_E_STATE before emloco_sim_prepare; EMLOCO_E_ARG for classes that
+ * overlap, descend, leave a gap or do not end at n_env, parts that do not divide n_sub, tail / shift / n_classes out of
+ * range, n_calls < 1, n_sub * n_calls > 7 or n_env > 65536 (the plan word's fields) -- the plan in force is kept. */
+int emloco_sim_set_plan(EmlocoSim *sim, const int32_t *classes, int n_classes, int tail, int shift, int n_calls);
 /* Cost-ordered dispatch of the step launch (extension, off by default; results do not depend on it: envs are independent).
  * Every workgroup records how long its env's step took; the next launch hands the envs to the CUs longest first (a counting
  * sort on the device, one small launch ahead of the step).  The launch is two resident rounds of waves, so its length is set

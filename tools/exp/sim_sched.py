@@ -1,12 +1,16 @@
 """Schedule of ONE rigid-body launch of the bench workload, workgroup by workgroup (run on the GPU box):
 
     EMLOCO_HIPCC_EXTRA_SIM="-DEMLOCO_SIM_SCHED=1" python -m emloco_amd.build --force      # diagnostic build
-    python tools/exp/sim_sched.py [--envs 4096] [--steps 150]
+    python tools/exp/sim_sched.py [--envs 4096] [--steps 150] [--plan T+C1024] [--dump trace.npz]
 
 Needs a library built with -DEMLOCO_SIM_SCHED=1: every workgroup then leaves its wall clock (100 MHz) at its first
 instruction, once its predecessor's hand-over is in and at its last instruction (sim_kernels.hip, SCHED_HANDED).  Prints the
 launch length, the split of the slot-time (running / waiting for the predecessor / empty), the longest env chains, the
-hop time (predecessor's last instruction -> successor has the hand-over) and the run time against the contact-work key."""
+hop time (predecessor's last instruction -> successor has the hand-over) and the run time against the contact-work key; then
+the resident workgroups against time in 5 us bins, the empty slot-time in three stretches (until the first slot turns over / between /
+after the last workgroup is dispatched) and the run time per part index and cost-key class.  --plan: the part plan of the launch
+(EMLOCO_SIM_PLAN, emloco_amd/sim.py: plan_from_spec); --dump: the stamps as an .npz for tools/exp/sim_replay.py.  Envs may differ in
+their number of parts under a plan; an env counts as traced when a gap-free run of its parts, at least two, lies in the launch."""
 import argparse
 import ctypes as C
 import os
@@ -22,7 +26,11 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--envs", type=int, default=4096)
 ap.add_argument("--steps", type=int, default=150, help="steps of the rollout loop before the launch that is traced")
 ap.add_argument("--slots", type=int, default=3072, help="wave slots of the device for this kernel: 256 CUs x 12")
+ap.add_argument("--plan", default=None, help="part plan of the launch (sets EMLOCO_SIM_PLAN)")
+ap.add_argument("--dump", default=None, help="write the stamps of the traced envs to this .npz")
 a = ap.parse_args()
+if a.plan is not None:
+    os.environ["EMLOCO_SIM_PLAN"] = a.plan
 E = a.envs
 env = bench.make_env(E, 0)
 task = env.task
@@ -40,9 +48,10 @@ torch.cuda.synchronize()
 lib = task.sim.native.lib
 SENT = 0xFFFFFFFFFFFFFFFF
 key_prev = (C.c_uint * E)()
-st = (C.c_ulonglong * (16 * E))(*([SENT] * (16 * E)))
+st = (C.c_ulonglong * (20 * E))(*([SENT] * (20 * E)))        # [5 parts][n_env][4]; a library from before the part plan fills [4 parts]
 lib.emloco_sim_cost_ticks.argtypes = [C.c_void_p, C.POINTER(C.c_uint), C.POINTER(C.c_ulonglong), C.c_int]
 assert lib.emloco_sim_cost_ticks(task.sim.native._h, key_prev, st, E) == 0      # allocates the stamps; key_prev: what the next launch is ordered by
+P_MAX = 5 if st[20 * E - 1] != SENT else 4
 if st[16 * E - 1] == SENT:
     raise SystemExit("this library was not built with -DEMLOCO_SIM_SCHED=1 (see the head of this file)")
 for k in range(3):
@@ -51,13 +60,22 @@ for k in range(3):
 torch.cuda.synchronize()
 key = (C.c_uint * E)()
 assert lib.emloco_sim_cost_ticks(task.sim.native._h, key, st, E) == 0
-s = np.array(st[:], dtype=np.int64).reshape(4, E, 4)
-n_parts = int((s[:, :, 2] > 0).any(axis=1).sum())
-s = s[:n_parts]
-# envs whose parts all ran in the latest full launch: the reset envs go through the unsplit list launch, their later parts' stamps
-# are a step old (launches start ~420 us apart and last ~350)
-med = np.median(s[n_parts - 1, :, 2])
-ran = ((np.abs(s[:, :, 0] - med) < 35000) & (np.abs(s[:, :, 2] - med) < 35000)).all(axis=0)
+s_all = np.array(st[:16 * E if P_MAX == 4 else 20 * E], dtype=np.uint64).reshape(P_MAX, E, 4)
+wg_index = (s_all[:, :, 3] >> np.uint64(32)).astype(np.int64)          # workgroup index (0 from a library from before the part plan)
+s_all = s_all.astype(np.int64)
+s_all[:, :, 3] &= 0xFFFFFFFF
+# parts that ran in the latest full launch: the reset envs go through the unsplit list launch, their later parts' stamps are a step
+# old (launches start ~420 us apart and last ~350), and under a plan an env has two to five parts
+med = np.median(s_all[1, :, 2][s_all[1, :, 2] > 0])
+have_all = (s_all[:, :, 2] > 0) & (np.abs(s_all[:, :, 0] - med) < 35000) & (np.abs(s_all[:, :, 2] - med) < 35000)
+n_of = np.cumprod(have_all, axis=0).sum(axis=0)                        # gap-free run of parts from part 0
+ran_all = (n_of >= 2) & (have_all.sum(axis=0) == n_of)
+kinds = sorted(set(n_of[ran_all].tolist()))
+print("parts per env among the traced envs: %s" % ", ".join("%d parts: %d envs" % (k, (n_of[ran_all] == k).sum()) for k in kinds))
+# the tables of the uniform launch below follow the envs of the most common part count; the plan tables at the end take them all
+n_parts = int(np.bincount(n_of[ran_all]).argmax())
+s = s_all[:n_parts]
+ran = ran_all & (n_of == n_parts)
 us = 0.01                                            # 100 MHz
 t_first, t_hand, t_last = s[:, :, 0].astype(np.float64) * us, s[:, :, 1].astype(np.float64) * us, s[:, :, 2].astype(np.float64) * us
 slot = s[:, :, 3] >> 8
@@ -109,3 +127,56 @@ for lo, hi in zip(edges[:-1], edges[1:]):
         print("  key %4d..%-4s: %5d envs, part run time mean %5.1f  median %5.1f  p90 %5.1f us" % (
             lo, str(hi - 1) if hi < (1 << 30) else "", m.sum(), runs[:, m].mean(), np.median(runs[:, m]), np.percentile(runs[:, m], 90)))
 print("env 0: run time per part %s us" % " ".join("%.1f" % x for x in (t_last - np.vstack([t_first[:1], t_hand[1:]]))[:, 0]))
+
+# ---------------------------------------------------------------------------------------------------- the launch as a whole
+# every traced workgroup, whatever its env's part count: a = first instruction, h = hand-over in, b = last instruction (us from the
+# launch's first instruction)
+pp, ee = np.nonzero(have_all & ran_all[None, :])
+A = s_all[pp, ee, 0] * us
+H = s_all[pp, ee, 1] * us
+B = s_all[pp, ee, 2] * us
+H = np.where(pp == 0, A, H)
+z = A.min()
+A, H, B = A - z, H - z, B - z
+L = B.max()
+last_of = n_of[ee] - 1 == pp
+
+
+def busy(lo, hi):
+    """slot-time of resident workgroups inside [lo, hi)"""
+    return np.clip(np.minimum(B, hi) - np.maximum(A, lo), 0.0, None).sum()
+
+
+print()
+print("launch as a whole: %d workgroups of %d envs, %.1f us, slot-time resident %.1f %% (running %.1f %%, waiting %.1f %%), empty %.1f %%" % (
+    len(A), ran_all.sum(), L, 100 * busy(0, L) / (a.slots * L), 100 * (B - H).sum() / (a.slots * L), 100 * (H - A).sum() / (a.slots * L),
+    100 * (1 - busy(0, L) / (a.slots * L))))
+print("resident workgroups against time (5 us bins: mean resident, of %d slots):" % a.slots)
+edges5 = np.arange(0.0, L + 5.0, 5.0)
+occ = [busy(lo, lo + 5.0) / 5.0 for lo in edges5[:-1]]
+for i in range(0, len(occ), 8):
+    print("  %5.0f us: %s" % (edges5[i], " ".join("%4.0f" % x for x in occ[i:i + 8])))
+t_turn, t_disp = B.min(), A.max()
+print("empty slot-time in three stretches (slot-us; share of the launch's %d x %.1f):" % (a.slots, L))
+for name, lo, hi in (("until the first slot turns over", 0.0, t_turn), ("between", t_turn, t_disp), ("after the last workgroup is dispatched", t_disp, L)):
+    e = a.slots * (hi - lo) - busy(lo, hi)
+    print("  %-40s %6.1f .. %6.1f us: %9.0f  %5.2f %%  (= %.1f us of launch length at full occupancy)" % (name, lo, hi, e, 100 * e / (a.slots * L), e / a.slots))
+print("run time per part index and cost-key class (median us; count):")
+kk_all = keyv[ee]
+kedges = [0, 1, 41, 61, 81, 101, 141, 1 << 30]
+print("  part   " + " ".join("%13s" % ("key %d..%s" % (lo, hi - 1 if hi < (1 << 30) else "")) for lo, hi in zip(kedges[:-1], kedges[1:])) + "   all")
+for p in range(P_MAX):
+    for fin in (False, True):
+        m = (pp == p) & (last_of == fin)
+        if not m.any():
+            continue
+        cells = []
+        for lo, hi in zip(kedges[:-1], kedges[1:]):
+            mk = m & (kk_all >= lo) & (kk_all < hi)
+            cells.append("%6.1f (%4d)" % (np.median((B - H)[mk]), mk.sum()) if mk.any() else "      -      ")
+        print("  %d%s    %s  %6.1f" % (p, "F" if fin else " ", " ".join(cells), np.median((B - H)[m])))
+print("  (F: the env's final part -- final kinematics pass and write-back)")
+if a.dump:
+    np.savez(a.dump, env=ee, part=pp, n_parts=n_of[ee], key=keyv[ee], key_prev=np.array(key_prev[:], dtype=np.int64)[ee], first=A, handed=H, last=B,
+             rank=s_all[pp, ee, 3] >> 8, wg=wg_index[pp, ee], slots=a.slots, length=L)
+    print("stamps written to", a.dump)
