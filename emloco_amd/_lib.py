@@ -216,6 +216,8 @@ def load():
 
 
 def check(rc, what=""):
+    """The one place a status of the C ABI becomes an EmlocoError: `rc` is what the entry point `what` returned on this thread, just now.
+    The message carries the library's own text for that failure (emloco_last_error, every entry point of include/*.h sets it)."""
     if rc != 0:
         msg = load().emloco_last_error()
         raise EmlocoError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}")

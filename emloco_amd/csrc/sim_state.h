@@ -16,6 +16,8 @@ template <class T> struct DevBuf {
     void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
 };
 
+// workgroups of a launch over a list of n envs: the list kernels are grid-stride (reset_kernels.hip)
+inline unsigned list_grid(int n) { return (unsigned)(n < 256 ? n : 256); }
 
 struct EmlocoSim {
     int device = 0;

@@ -29,9 +29,7 @@ def _st(t):
     return current_stream_handle(t.device)
 
 
-def _chk(rc, what):
-    if rc != 0:
-        raise L.EmlocoError(f"{what} failed with code {rc}")
+_chk = L.check
 
 
 GEMM_BF16 = 16

@@ -278,8 +278,7 @@ class MotionLib(MotionLibBase):
                                      d_nfr32.data_ptr(), self._motion_fps.data_ptr(), d_skel.data_ptr(), start.ctypes.data, nfr.ctypes.data,
                                      skel_id.ctypes.data, d_lt.data_ptr(), parent.ctypes.data, taps.ctypes.data,
                                      *[st[k].data_ptr() for k in FRAME_KEYS], 0, torch.cuda.current_stream().cuda_stream)
-        if rc != 0:
-            raise _lib.EmlocoError(f"emloco_motion_build failed (code {rc})")
+        _lib.check(rc, "emloco_motion_build")
         ev[2].record()
         self._build_events = ev
         for k in FRAME_KEYS + ("_motion_aa",):

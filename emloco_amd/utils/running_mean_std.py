@@ -33,8 +33,7 @@ def obs_normalize(x, mean32, var32, eps, clip=5.0, split=None, out0=None, out1=N
                                   C.c_float(eps), C.c_float(clip), split, vp(out0.data_ptr()), out0.stride(0),
                                   vp(out1.data_ptr()) if out1 is not None else None,
                                   out1.stride(0) if out1 is not None else 0, current_stream_handle(x.device))
-    if rc != 0:
-        raise L.EmlocoError(f"emloco_obs_normalize failed with code {rc}")
+    L.check(rc, "emloco_obs_normalize")
     return out0, out1
 
 
@@ -54,8 +53,7 @@ def rms_update(x, mean64, var64, count64, first_col=0, scratch=None):
     else:
         rc = lib.emloco_rms_update(rows, cols, vp(x.data_ptr()), x.stride(0), vp(mean64.data_ptr()), vp(var64.data_ptr()), vp(count64.data_ptr()),
                                    vp(scratch.data_ptr()), int(first_col), current_stream_handle(x.device))
-    if rc != 0:
-        raise L.EmlocoError(f"emloco_rms_update failed with code {rc}")
+    L.check(rc, "emloco_rms_update")
     count64.copy_(scratch)
 
 

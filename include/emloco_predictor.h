@@ -5,7 +5,8 @@
  * pacer/pacer/learning/value_pose_net.py:10-159 ValuePoseNet) and calls these entry points from
  * torch.autograd.Function wrappers; PyTorch only carries the autograd graph and device memory.
  * All pointers are device memory, fp32, row-major; `stream` is a hipStream_t (0 = default).
- * Return 0 on success, negative on bad arguments / HIP errors (emloco_last_error()).
+ * Return 0 on success, a negative EMLOCO_E_* code (emloco_sim.h) on bad arguments / HIP errors.  emloco_last_error() then has the
+ * text, for every entry point of this header: per thread, meaningful only directly after the failing call; nothing is printed.
  */
 #ifndef EMLOCO_PREDICTOR_H
 #define EMLOCO_PREDICTOR_H

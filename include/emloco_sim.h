@@ -6,6 +6,9 @@
  * isaacgym/docs/api/python/gym_py.html; the Python shim maps codes back to that convention).
  * Device pointers belong to the HIP device the sim was created on.  `stream` is a hipStream_t
  * passed as void* (0 = the default stream); the library never synchronises unless asked to.
+ * Errors: emloco_last_error() returns the text of the last failed call of the calling thread, whichever of the three headers
+ * (this one, emloco_task.h, emloco_predictor.h) declares the entry point that failed.  The text is per thread and means something
+ * only directly after a call on that thread returned a negative code; the library prints nothing.
  *
  * Each entry point names the reference interface it stands behind (file:line under
  * /root/reference/); the reference-side binding is shown in INTEGRATION.md.
@@ -115,7 +118,7 @@ enum {
 
 typedef struct EmlocoSim EmlocoSim;
 
-const char *emloco_last_error(void);
+const char *emloco_last_error(void);      /* the calling thread's text (see the top of this file); "" before its first failure */
 int emloco_device_count(void);
 
 /* gym.create_sim(compute_device, graphics_device, type, params) -- base_task.py:238 */

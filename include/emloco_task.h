@@ -13,6 +13,8 @@
  *   reset / terminate masks (int64)      humanoid_pedestrain_terrain.py:883-905,1468-1530
  *   AMP history shift + new AMP row      humanoid_amp.py:585-657,917-971
  * Buffers are caller-owned device memory (the task object allocates them, base_task.py:96-111).
+ * Every entry point returns 0 or a negative EMLOCO_E_* code (emloco_sim.h); emloco_last_error() then has the text, for every entry
+ * point of this header: per thread, meaningful only directly after the failing call; nothing is printed.
  */
 #ifndef EMLOCO_TASK_H
 #define EMLOCO_TASK_H

@@ -191,7 +191,8 @@ def test_the_entry_points_refuse_bad_arguments(capfd):
     st.games_per_env = 0
     assert call() == -1
     st.games_per_env = 2
-    assert "emloco_locoval_eval_track" in capfd.readouterr().err
+    assert b"emloco_locoval_eval_track" in lib.emloco_last_error()
+    assert capfd.readouterr().err == ""                 # the text is returned, not printed
     mom = np.zeros(12)
     games = np.zeros(4, np.int32)
     red = lambda n=4, g=2, r=buf, gm=games, m=mom: lib.emloco_locoval_track_reduce(n, g, _ptr(r), _ptr(gm), 4.0, _ptr(m), None)
