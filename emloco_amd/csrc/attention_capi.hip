@@ -7,19 +7,21 @@
 #include "attention16_kernels.hip"      // (includes attention_kernels.hip)
 #include "../../include/emloco_predictor.h"
 #include "capi_error.h"
+#include "capi_knobs.h"
 
 using emloco::capi_fail;
 
 namespace {
 // EMLOCO_ATTN16_OLD=1: the bf16-in-memory mode on round 4's kernels (one block of 32 rows per wave, fp32 LDS tiles) -- A/B knob
-bool attn16_old() { static const bool v = [] { const char *e = getenv("EMLOCO_ATTN16_OLD"); return e && e[0] == '1'; }(); return v; }
+bool attn16_old() { return emloco::knob_attn16_old().value == 1; }
 // Pieces per operand in the split mode's BACKWARD kernels (round 6).  Default 2: every operand is the sum of two bf16 pieces and a product
 // the three piece products above 2^-16 of it -- gradients to ~2^-17 of their magnitude (measured on the shipped-depth model,
 // tools/exp/graderr.py: 2-3e-6 of a tensor's scale next to the loss, where three pieces give 6e-7 and the test bar is 2e-4; the early
 // layers' 3e-5 .. 1e-4 do not move: that is the ReLU / LayerNorm stack's own fp32 noise), half the matrix instructions and 40 % of the
 // piece arithmetic: dQ + dK/dV 5.99 -> 4.09 ms per launch pair at the train step's size.  The FORWARD stays on three pieces (logits to
 // 5e-7).  EMLOCO_ATTN_BWD_PIECES=3 restores the three-piece backward.
-int attn_bwd_pieces() { static const int v = [] { const char *e = getenv("EMLOCO_ATTN_BWD_PIECES"); return e && e[0] == '3' ? 3 : 2; }(); return v; }
+int attn_bwd_pieces() { return emloco::knob_attn_bwd_pieces().value; }
+// (both parsed in capi_knobs.h, which emloco_kernel_variants reports from; a launch that consults one checks it first: EMLOCO_KNOBCHK)
 }  // namespace
 
 extern "C" {
@@ -51,6 +53,7 @@ int emloco_attention_fwd_queries(int n_seq, int S, int n_query, int nhead, int d
     hipStream_t st = (hipStream_t)stream;
     if (flags & EMLOCO_ATTN_QKV_BF16MEM) {
         if (!bf) return capi_fail(EMLOCO_E_ARG, "emloco_attention_fwd: a bf16 q|k|v tensor needs EMLOCO_ATTN_BF16");
+        EMLOCO_KNOBCHK(emloco::knob_attn16_old());
         if (!attn16_old()) {                                 // round 5: two blocks of 32 queries per wave, bf16 tile images (attention16_kernels.hip)
             const dim3 grid16((unsigned)((n_query + 255) / 256), (unsigned)(n_seq * nhead));
             if (dr) hipLaunchKernelGGL((emloco::attn16_fwd_kernel<1, 2, 1, 1>), grid16, dim3(256), 0, st, a);
@@ -64,6 +67,7 @@ int emloco_attention_fwd_queries(int n_seq, int S, int n_query, int nhead, int d
         return 0;
     }
     const bool sp = !bf && (flags & EMLOCO_ATTN_SPLIT) != 0;
+    if (sp) EMLOCO_KNOBCHK(emloco::knob_attn16_old());
     if (sp && !attn16_old()) {                               // round 5: the split mode on the piece-plane tile images (attention16_kernels.hip, NP = 3)
 #ifndef A16_SPLIT_G_FWD
 #define A16_SPLIT_G_FWD 2                                    /* blocks of 32 queries per wave of the split-mode forward (measured: 2.006 -> 1.855 ms per launch) */
@@ -118,7 +122,10 @@ int emloco_attention_bwd_queries(int n_seq, int S, int n_query, int nhead, int d
     const size_t esz = q16 ? 2 : sizeof(float);
     // rows that do not attend get dQ = 0 (the Q third of every dqkv row; the live rows are overwritten below)
     // (round 5's dK / dV kernels write those zeros themselves: the memset is for round 4's kernels and the modes they still serve)
-    const bool new_kernels = !attn16_old() && (q16 || (!bf && (flags & EMLOCO_ATTN_SPLIT) != 0));
+    const bool served16 = q16 || (!bf && (flags & EMLOCO_ATTN_SPLIT) != 0);      // the modes the two knobs choose kernels for
+    if (served16) EMLOCO_KNOBCHK(emloco::knob_attn16_old());
+    if (served16 && !q16 && !attn16_old()) EMLOCO_KNOBCHK(emloco::knob_attn_bwd_pieces());
+    const bool new_kernels = served16 && !attn16_old();
     if (n_query < S && !new_kernels) EMLOCO_HIPCHK(hipMemset2DAsync(dqkv, 3 * (size_t)d_model * esz, 0, (size_t)d_model * esz, (size_t)n_seq * S, st));
     if (q16 && !attn16_old()) {
         const dim3 grid16((unsigned)((S + 255) / 256), (unsigned)(n_seq * nhead)), qgrid16((unsigned)((n_query + 255) / 256), (unsigned)(n_seq * nhead));

@@ -7,6 +7,7 @@
 #include "locoval_refine.h"            // the refinement loop (emloco_locoval_refine); not part of the CPU emulation's sources
 #include "../../include/emloco_predictor.h"
 #include "capi_error.h"
+#include "capi_knobs.h"
 
 using emloco::capi_fail;
 
@@ -98,7 +99,9 @@ int emloco_gemm_f32_ex(int batch, int m, int n, int k, float alpha, const float 
         g.flags &= ~EMLOCO_GEMM_B_SPLITIMG;
     }
     // 16-byte stores of whole output lines (the LDS-transposed epilogue): EMLOCO_GEMM_WIDE_STORES=0 keeps the per-register stores (A/B knob)
-    static const bool wide = !(getenv("EMLOCO_GEMM_WIDE_STORES") && getenv("EMLOCO_GEMM_WIDE_STORES")[0] == '0');
+    EMLOCO_KNOBCHK(emloco::knob_gemm_wide_stores());
+    EMLOCO_KNOBCHK(emloco::knob_gemm_bk());
+    const bool wide = emloco::knob_gemm_wide_stores().value == 1;
     g.vec_c = (wide && (uintptr_t)C % 16 == 0 && ldc % (g.c16 ? 8 : 4) == 0 && stride_c % (g.c16 ? 8 : 4) == 0) ? 1 : 0;
     if (g.a16 || g.b16 || g.c16) {
         if (!(flags & EMLOCO_GEMM_BF16) || !g.vec_a || !g.vec_b || n <= 32)
@@ -110,7 +113,7 @@ int emloco_gemm_f32_ex(int batch, int m, int n, int k, float alpha, const float 
     const int slot = g_head;
     if (g_timing) EMLOCO_HIPCHK(hipEventRecord(g_e0[slot], st));
     // stage depth: 32 for long reductions (covers the prefetch latency), 16 for short ones (less LDS, more workgroups / CU)
-    static const int force_bk = getenv("EMLOCO_GEMM_BK") ? atoi(getenv("EMLOCO_GEMM_BK")) : 0;
+    const int force_bk = emloco::knob_gemm_bk().value;        // EMLOCO_GEMM_BK: 0 (by launch shape), 16 or 32 (A/B knob)
     const bool split_ok = (flags & EMLOCO_GEMM_SPLIT) && !(flags & EMLOCO_GEMM_BF16) && g.vec_a && g.vec_b && n > 32;
     g.small = split_ok && (g_force_small >= 0 ? g_force_small == 1 : emloco::gemm_use_small_tile(batch, m, n, ksplit)) ? 1 : 0;
     const unsigned bn = n <= 32 ? 32 : (g.small ? 64 : 128), bm = g.small ? 64 : 128;
@@ -273,7 +276,8 @@ int emloco_gemm_relu_bwd(int m, int n, int k, const float *A, int lda, const flo
         return capi_fail(EMLOCO_E_ARG, "emloco_gemm_relu_bwd: a bf16 hidden layer needs EMLOCO_GEMM_BF16 and comes with a bf16 gradient (C and MASK flags together)");
     if (!g.vec_a || !g.vec_b) return capi_fail(EMLOCO_E_ARG, "emloco_gemm_relu_bwd: A and B must be 16-byte aligned with leading dimensions that are multiples of 4");
     {   // wide accesses of the fp32 epilogue (mask in, gradient out as whole lines); EMLOCO_GEMM_WIDE_STORES=0: per-register accesses
-        static const bool wide = !(getenv("EMLOCO_GEMM_WIDE_STORES") && getenv("EMLOCO_GEMM_WIDE_STORES")[0] == '0');
+        EMLOCO_KNOBCHK(emloco::knob_gemm_wide_stores());
+        const bool wide = emloco::knob_gemm_wide_stores().value == 1;
         g.vec_c = (wide && !g.c16 && (uintptr_t)C % 16 == 0 && (uintptr_t)y % 16 == 0 && n % 4 == 0) ? 1 : 0;
     }
     hipStream_t st = (hipStream_t)stream;
@@ -606,6 +610,15 @@ int emloco_adam_clip_flat_counted(int64_t n, float *params, float *grads, float 
     if (n < 1 || !params || !grads || !exp_avg || !exp_avg_sq || !workspace || !step_count)
         return capi_fail(EMLOCO_E_ARG, "emloco_adam_clip_flat_counted: bad argument (workspace = emloco_adam_clip_flat_workspace(n) floats, step_count = 1 device float)");
     return adam_clip_flat(n, params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, 1.0f, 1.0f, max_norm, workspace, step_count, stream);
+}
+
+int emloco_kernel_variants(int32_t *variants4) {
+    if (!variants4) return capi_fail(EMLOCO_E_ARG, "emloco_kernel_variants: null argument");
+    const emloco::Knob *knobs[4] = {&emloco::knob_attn_bwd_pieces(), &emloco::knob_attn16_old(), &emloco::knob_gemm_wide_stores(),
+                                    &emloco::knob_gemm_bk()};
+    for (int i = 0; i < 4; ++i) variants4[i] = knobs[i]->value;
+    for (int i = 0; i < 4; ++i) EMLOCO_KNOBCHK(*knobs[i]);
+    return 0;
 }
 
 int emloco_dropout_keep_mask(uint32_t seed, uint64_t first_index, int64_t n, float p, uint8_t *host_out) {

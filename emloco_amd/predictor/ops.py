@@ -46,8 +46,16 @@ GEMM_SPLIT2 = 4096      # EMLOCO_GEMM_SPLIT2: with GEMM_SPLIT, two pieces per op
 # reference's: 4-9e-6 of a tensor's scale next to the loss (6e-7 with three pieces; the tests' bar is 2e-4), unchanged in the early
 # layers (3e-5 .. 1.3e-4: the ReLU / LayerNorm stack's own fp32 noise, bar 1e-3).  EMLOCO_BWD_PIECES=3 (and EMLOCO_ATTN_BWD_PIECES=3)
 # restore round 5's backward.
-_BWD_PIECES = {"dx": int(os.environ.get("EMLOCO_BWD_PIECES_DX", os.environ.get("EMLOCO_BWD_PIECES", "2"))),
-               "dw": int(os.environ.get("EMLOCO_BWD_PIECES_DW", os.environ.get("EMLOCO_BWD_PIECES", "2")))}
+def _pieces_from_env(*names):
+    """2 or 3 from the first of the variables that is set (2 when none is); anything else is an error that names the variable and its value"""
+    found = [(name, os.environ[name]) for name in names if name in os.environ]
+    for name, value in found:                    # (a shadowed EMLOCO_BWD_PIECES is checked too)
+        if value not in ("2", "3"):
+            raise ValueError(f"{name}={value}: the pieces per operand of the backward products are 2 or 3")
+    return int(found[0][1]) if found else 2
+
+
+_BWD_PIECES = {"dx": _pieces_from_env("EMLOCO_BWD_PIECES_DX", "EMLOCO_BWD_PIECES"), "dw": _pieces_from_env("EMLOCO_BWD_PIECES_DW", "EMLOCO_BWD_PIECES")}
 
 
 _FFN_COLSUM = os.environ.get("EMLOCO_FFN_COLSUM", "1") != "0"      # the chained feed-forward's backward sums dz1's columns itself (round 6)

@@ -594,6 +594,16 @@ int emloco_gemm_split_pack(const float *W, int n, int k, int ld, int trans, uint
  * tiles: bit-equal, tests/test_emu_kernels.py); a tuning / A-B knob, also settable through EMLOCO_GEMM_SMALL. */
 int emloco_gemm_set_small_tile(int mode);
 
+/* The kernel variants selected by environment knobs, as this library parsed them (read-only; each knob is read once, the first time a
+ * launch or this call consults it, and the launchers read the very same values):
+ *   variants4[0]  EMLOCO_ATTN_BWD_PIECES   2 | 3    pieces per operand of the split-mode attention backward       unset: 2
+ *   variants4[1]  EMLOCO_ATTN16_OLD        0 | 1    round 4's attention kernels for the bf16-memory / split modes unset: 0
+ *   variants4[2]  EMLOCO_GEMM_WIDE_STORES  0 | 1    16-byte epilogue stores of whole output lines                 unset: 1
+ *   variants4[3]  EMLOCO_GEMM_BK           16 | 32  forced stage depth of emloco_gemm_f32_ex                      unset: 0 (by launch shape)
+ * Only the listed values are accepted.  A variable that holds anything else makes every launch that consults it -- and this call --
+ * return EMLOCO_E_ARG with a text that names the variable and its value; its entry of variants4 is then -1 (the others are filled). */
+int emloco_kernel_variants(int32_t *variants4);
+
 /* HIP-event timing of the GEMM launches (same protocol as emloco_sim_timing_stats) */
 int emloco_gemm_enable_timing(int on);
 int emloco_gemm_timing_stats(int *n_launches, float *total_ms, double *total_flops);

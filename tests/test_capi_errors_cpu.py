@@ -107,3 +107,57 @@ def test_no_device_is_reported_with_a_text(lib, capfd):
     text = lib.emloco_last_error().decode()
     assert text and "emloco_ffn_fwd" not in text
     assert capfd.readouterr().err == ""
+
+
+# a launch refused for a variant knob, in a process that starts with the knob set: (variable, value, entry point, arguments that pass every
+# argument check -- the pointers are never dereferenced: the knob is consulted ahead of the launch)
+_A = 4096                                # a 16-byte-aligned non-NULL "device address"
+KNOB_REFUSALS = (
+    ("EMLOCO_GEMM_BK", "7", "emloco_gemm_f32_ex", (1, 64, 64, 64, 1.0, _A, 64, 0, 0, _A, 64, 0, 0, _A, 64, 0, None, 0, 1, None, 0.0, 0, None)),
+    ("EMLOCO_GEMM_WIDE_STORES", "off", "emloco_gemm_f32_ex", (1, 64, 64, 64, 1.0, _A, 64, 0, 0, _A, 64, 0, 0, _A, 64, 0, None, 0, 1, None, 0.0, 0, None)),
+    ("EMLOCO_GEMM_WIDE_STORES", "2", "emloco_gemm_relu_bwd", (64, 64, 64, _A, 64, _A, 64, 0, _A, _A, 1.0, _A, _A, 0, None)),
+    ("EMLOCO_ATTN_BWD_PIECES", "30", "emloco_attention_bwd_queries", (1, 8, 8, 1, 32, 0.5, _A, None, _A, _A, _A, _A, _A, 64, 0.0, 0, None)),
+    ("EMLOCO_ATTN16_OLD", "yes", "emloco_attention_fwd_queries", (1, 8, 8, 1, 32, 0.5, _A, None, _A, _A, 64, 0.0, 0, None)),
+    ("EMLOCO_ATTN16_OLD", "", "emloco_attention_bwd_queries", (1, 8, 8, 1, 32, 0.5, _A, None, _A, _A, _A, _A, _A, 16 | 32, 0.0, 0, None)),
+)
+
+
+@pytest.mark.parametrize("knob,value,entry,args", KNOB_REFUSALS, ids=[f"{k[0]}={k[1]}" for k in KNOB_REFUSALS])
+def test_a_launch_refuses_a_knob_value_outside_its_list(knob, value, entry, args):
+    """csrc/capi_knobs.h: the variant knobs accept their documented values only; the first launch that consults one that holds anything
+    else returns EMLOCO_E_ARG with a text naming the variable and its value, and emloco_kernel_variants reports -1 for it"""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import ctypes as C, sys; from emloco_amd import _lib as L; lib = L.load(); "
+            f"rc = lib.{entry}(*{args!r}); print('launch', rc, lib.emloco_last_error().decode()); "
+            "v = (C.c_int32 * 4)(); rc = lib.emloco_kernel_variants(v); print('report', rc, list(v), lib.emloco_last_error().decode())")
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, PYTHONPATH=root, **{knob: value}), capture_output=True, text=True)
+    lines = {ln.split()[0]: ln for ln in r.stdout.splitlines() if ln.startswith(("launch", "report"))}
+    assert r.returncode == 0 and set(lines) == {"launch", "report"}, r.stderr[-2000:]
+    assert lines["launch"].startswith(f"launch {E_ARG} {entry}: {knob}={value}: "), lines["launch"]
+    slot = ("EMLOCO_ATTN_BWD_PIECES", "EMLOCO_ATTN16_OLD", "EMLOCO_GEMM_WIDE_STORES", "EMLOCO_GEMM_BK").index(knob)
+    want = [2, 0, 1, 0]
+    want[slot] = -1
+    assert lines["report"].startswith(f"report {E_ARG} {want} emloco_kernel_variants: {knob}={value}: "), lines["report"]
+
+
+def test_kernel_variants_reports_the_parsed_knobs():
+    """unset: the defaults; every documented value is accepted and reported (one child with all four set)"""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    names = ("EMLOCO_ATTN_BWD_PIECES", "EMLOCO_ATTN16_OLD", "EMLOCO_GEMM_WIDE_STORES", "EMLOCO_GEMM_BK")
+    env = {k: v for k, v in os.environ.items() if k not in names}
+    env["PYTHONPATH"] = root
+    code = ("import ctypes as C; from emloco_amd import _lib as L; lib = L.load(); v = (C.c_int32 * 4)(); "
+            "print('report', lib.emloco_kernel_variants(v), list(v))")
+    run = lambda **kw: subprocess.run([sys.executable, "-c", code], env=dict(env, **kw), capture_output=True, text=True).stdout.strip().splitlines()[-1]
+    assert run() == "report 0 [2, 0, 1, 0]"
+    assert run(EMLOCO_ATTN_BWD_PIECES="3", EMLOCO_ATTN16_OLD="1", EMLOCO_GEMM_WIDE_STORES="0", EMLOCO_GEMM_BK="32") == "report 0 [3, 1, 0, 32]"
+    assert run(EMLOCO_ATTN_BWD_PIECES="2", EMLOCO_ATTN16_OLD="0", EMLOCO_GEMM_WIDE_STORES="1", EMLOCO_GEMM_BK="16") == "report 0 [2, 0, 1, 16]"
+    from emloco_amd import _lib as L
+    lib = L.load()
+    assert lib.emloco_kernel_variants(None) == E_ARG and "emloco_kernel_variants: null argument" in lib.emloco_last_error().decode()

@@ -1388,6 +1388,96 @@ def test_split_mode_attention_on_piece_plane_tile_images():
         assert np.all(new[2][-1, S - 20:, d:] == 0)
 
 
+def _emu_attention_row(case, variants):
+    """One row of the device matrix (tests/kernel_matrix_cases.py: the same shapes, key bias, dropout and n_query; the operands from the
+    CPU generator) through the emulated kernels: {variant: worst |got - ref| / (BAR_FP32 mag) of out, dsum, dq, dk, dv}.  variants:
+    "fp32" (attn_*<0, DROP>), 5 / 3 (emu_attention16: the split mode with the three- / two-piece backward; they share the forward)."""
+    import torch
+    import kernel_matrix_cases as kmc
+    from emloco_amd import _lib as L
+    lib = emu.lib()
+    lib.emu_attention_set_dropout.argtypes = [C.c_float, C.c_uint]
+    mode, S, nq, H, kind, cut, p = case
+    n_seq, d = 2, 32 * H
+    qkv_t, kb_t, dout_t, seed = kmc.attn_inputs(case, n_seq, dev="cpu")
+    qkv, dout = qkv_t.numpy(), dout_t.numpy()
+    kb = kb_t.numpy() if kb_t is not None else None
+    keep = None
+    if p > 0:                                   # the library's host evaluation of the mask (the hash of attention_kernels.hip)
+        h = np.zeros(n_seq * H * S * S, np.uint8)
+        assert L.load().emloco_attention_keep_mask(seed, n_seq * H, S, C.c_float(p), h.ctypes.data_as(C.c_void_p)) == 0
+        keep = torch.from_numpy(h.reshape(n_seq, H, S, S)[:, :, :nq].astype(np.float64))
+    q64, do64 = qkv_t.double(), dout_t.double()
+    r_out, _, r_dqkv, r_D = kmc._attn_reference(q64, kb_t, H, nq, keep, p, do64)
+    mags = kmc.attn_mags(q64, kb_t, H, nq, keep, p, do64)
+    sc = C.c_float(kmc.SCALE)
+    res = {}
+    out = np.full((n_seq, nq, d), np.nan, np.float32)
+    lse = np.full((n_seq * H, nq), np.nan, np.float32)
+    VP = lambda a: a.ctypes.data_as(C.c_void_p)
+    if "fp32" in variants:
+        try:
+            lib.emu_attention_set_dropout(p, seed)
+            lib.emu_attention_fwd_queries(n_seq, S, nq, H, d, sc, P(qkv), P(kb), P(out), P(lse))
+            dqkv, dsum = np.full_like(qkv, np.nan), np.full((n_seq * H, nq), np.nan, np.float32)
+            lib.emu_attention_bwd_queries(n_seq, S, nq, H, d, sc, P(qkv), P(kb), P(out), P(lse), P(dout), P(dqkv), P(dsum))
+        finally:
+            lib.emu_attention_set_dropout(0.0, 0)
+        res["fp32"] = (out, dsum, dqkv)
+    else:
+        lib.emu_attention16(5, n_seq, S, nq, H, d, sc, VP(qkv), P(kb), P(out), P(lse), None, None, None, C.c_float(p), C.c_uint(seed))
+        for which in variants:
+            dqkv, dsum = np.full_like(qkv, np.nan), np.full((n_seq * H, nq), np.nan, np.float32)
+            lib.emu_attention16(which, n_seq, S, nq, H, d, sc, VP(qkv), P(kb), P(out), P(lse), P(dout), VP(dqkv), P(dsum), C.c_float(p), C.c_uint(seed))
+            res[which] = (out, dsum, dqkv)
+    t64 = lambda a: torch.from_numpy(a.astype(np.float64))
+    return {v: kmc.attn_bar_ratios(tuple(map(t64, g)), (r_out, r_D, r_dqkv), mags, d, kmc.BAR_FP32) for v, g in res.items()}
+
+
+def _attn_rows(mode):
+    import kernel_matrix_cases as kmc
+    return [pytest.param(c, id=kmc.attn_id(c)) for c in kmc.ATTN_CASES if c[0] == mode]
+
+
+@pytest.mark.parametrize("case", _attn_rows("fp32"))
+def test_attention_per_element_bars_hold_for_the_emulated_fp32_kernels(case):
+    """the per-element bars of tests/kernel_matrix_cases.py (|got - ref| <= eps mag, mag the first-order magnitude of each product
+    chain) on every fp32 row of the device matrix: the emulated fp32 kernels meet BAR_FP32 on out, dsum, dq, dk and dv -- a row that
+    does not would mean a term missing from mag (the bar is the header's, not tuned)"""
+    ratios = _emu_attention_row(case, ("fp32",))["fp32"]
+    assert all(v <= 1.0 for v in ratios.values()), (case, ratios)
+
+
+@pytest.mark.parametrize("case", _attn_rows("split"))
+def test_attention_per_element_bars_hold_for_the_emulated_split_kernels(case):
+    """... and on every split row: the three-piece backward (which = 5, EMLOCO_ATTN_BWD_PIECES=3) meets BAR_FP32, the two-piece one
+    (which = 3, the default launch) BAR_SPLIT2 on dq / dk / dv and BAR_FP32 on dsum (the same bits as with three pieces)"""
+    import kernel_matrix_cases as kmc
+    res = _emu_attention_row(case, (5, 3))
+    assert all(v <= 1.0 for v in res[5].values()), (case, "three pieces", res[5])
+    two = {k: v * (kmc.BAR_FP32 / kmc.BAR_SPLIT2 if k in ("dq", "dk", "dv") else 1.0) for k, v in res[3].items()}
+    assert all(v <= 1.0 for v in two.values()), (case, "two pieces", two)
+
+
+def test_attention_per_element_bars_tell_two_pieces_from_three():
+    """The power of the per-element bars.  On random operands the third pieces that a two-piece operand drops average away, so the matrix
+    rows cannot tell the two backwards apart; kernel_matrix_cases.ATTN_COHERENT (S = 129, 4 heads, no dropout, q | k | v and dO positive
+    with mantissas whose dropped remainder is +63 / 2^23 of every element, one heavy key per sequence) makes them add up.  The
+    three-piece backward (which = 5) must meet the BAR_FP32 bars, the two-piece one (which = 3) must exceed them at least 4 x -- so the
+    device run of this case under EMLOCO_ATTN_BWD_PIECES=3 (tests/test_gpu_kernel_knobs.py) proves which kernel ran.
+    Measured worst error / (BAR_FP32 mag) -- which = 5: out 0.53, dsum 0.33, dq 0.27, dk 0.19, dv 0.41 (worst 0.53); which = 3: dq 2.48,
+    dk 2.40, dv 7.65 (worst 7.65, the heavy key's dv rows; out and dsum as with three pieces).  On the device (MI355X): 0.12 and 7.7.
+    (Positive random operands with the low mantissa byte 0x60 -- the first construction tried -- reach 1.15 only: after two
+    round-to-nearest pieces such a value's remainder is -32 / 2^23 or 0, by its middle byte, and the log-sum-exp term of mag doubles
+    the room of the logits.  Hence the chosen bits, and the heavy key, whose logit stands above its row's log-sum-exp term.)"""
+    import kernel_matrix_cases as kmc
+    res = _emu_attention_row(kmc.ATTN_COHERENT, (5, 3))
+    print("worst ratios, three pieces:", res[5], "two pieces:", res[3])
+    assert all(v <= 1.0 for v in res[5].values()), ("three pieces", res[5])
+    assert max(res[3][k] for k in ("dq", "dk", "dv")) >= 4.0, ("two pieces are not told apart", res[3])
+    assert res[3]["out"] == res[5]["out"] and res[3]["dsum"] == res[5]["dsum"]          # (same forward, same row sums)
+
+
 def test_ppo_loss_heads_follow_the_torch_expressions():
     """csrc/ppo_kernels.hip (round 5): the PPO + AMP learner's loss heads -- actor (neglogp, clipped surrogate, entropy, bound loss, clip
     fraction, policy KL), critic (clipped value loss), discriminator (two binary cross entropies, accuracies) -- emulated against the

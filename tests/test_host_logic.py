@@ -199,6 +199,45 @@ def test_package_import_leaves_the_environment_alone_and_entry_points_opt_in():
         assert "configure_runtime()" in open(os.path.join(root, f)).read(), f
 
 
+def test_backward_piece_knobs_accept_two_and_three_only():
+    """ops.py reads EMLOCO_BWD_PIECES / _DX / _DW once, at import: 2 and 3 are the values, an unset variable means 2, the specific
+    variable wins over the common one -- and anything else (4 used to mean three pieces silently, `two` was a bare int() error) is a
+    ValueError that names the variable and its value"""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    names = ("EMLOCO_BWD_PIECES", "EMLOCO_BWD_PIECES_DX", "EMLOCO_BWD_PIECES_DW")
+    env = {k: v for k, v in os.environ.items() if k not in names}
+    env["PYTHONPATH"] = root
+    # one child: the module is imported, then re-imported under each setting (the knobs are read at import)
+    code = """
+import importlib, os, sys
+from emloco_amd.predictor import ops
+for spec in sys.argv[1:]:
+    for n in ("EMLOCO_BWD_PIECES", "EMLOCO_BWD_PIECES_DX", "EMLOCO_BWD_PIECES_DW"):
+        os.environ.pop(n, None)
+    os.environ.update(kv.split("=", 1) for kv in spec.split(",") if kv)
+    try:
+        p = importlib.reload(ops).backward_pieces()
+        print(spec, "->", p["dx"], p["dw"])
+    except ValueError as e:
+        print(spec, "-> ValueError:", e)
+"""
+    specs = ["", "EMLOCO_BWD_PIECES=2", "EMLOCO_BWD_PIECES=3", "EMLOCO_BWD_PIECES=3,EMLOCO_BWD_PIECES_DX=2", "EMLOCO_BWD_PIECES_DW=3",
+             "EMLOCO_BWD_PIECES=4", "EMLOCO_BWD_PIECES=two", "EMLOCO_BWD_PIECES_DX=4", "EMLOCO_BWD_PIECES_DW=two", "EMLOCO_BWD_PIECES=",
+             "EMLOCO_BWD_PIECES=4,EMLOCO_BWD_PIECES_DX=2,EMLOCO_BWD_PIECES_DW=2"]
+    r = subprocess.run([sys.executable, "-c", code] + specs, env=env, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    got = dict(ln.split(" -> ", 1) for ln in r.stdout.splitlines() if " -> " in ln)
+    assert [got[s] for s in specs[:5]] == ["2 2", "2 2", "3 3", "2 3", "2 3"]                # unset means 2; the specific variable wins
+    for s in specs[5:]:                                                                     # (the last: shadowed, still refused)
+        name, value = s.split(",")[0].split("=")
+        assert got[s].startswith(f"ValueError: {name}={value}: "), (s, got[s])
+    # ... and the import itself fails that way in a fresh process
+    r = subprocess.run([sys.executable, "-c", "from emloco_amd.predictor import ops"], env=dict(env, EMLOCO_BWD_PIECES="two"), capture_output=True, text=True)
+    assert r.returncode != 0 and "ValueError: EMLOCO_BWD_PIECES=two: " in r.stderr, r.stderr[-400:]
+
+
 def test_bench_summary_is_a_compact_digest_of_every_leg():
     """bench.summary_of: the numbers of every leg, no notes -- printed as the LAST key of the line (configs[2] was outside
     the tail of stdout the driver keeps)."""
