@@ -140,6 +140,27 @@ class GetupBufs(C.Structure):
                 ("split_ws", C.c_void_p), ("stats", C.c_void_p)]
 
 
+REC_WORDS, REC_POST_WORDS, REC_COUNTERS = 512, 892, 8          # EMLOCO_REC_*
+REC_NONFINITE, REC_SPEED, REC_ANG_SPEED, REC_EARLY_FALL, REC_REQUEST = 1, 2, 4, 8, 16
+
+
+def rec_slot_words(depth):
+    """EMLOCO_REC_SLOT_WORDS(R)"""
+    return 4 + int(depth) * REC_WORDS + REC_POST_WORDS
+
+
+class RecorderBufs(C.Structure):
+    """EmlocoRecorderBufs (include/emloco_task.h): the flight recorder's view of the simulator, the task's flags and its own buffers."""
+    _fields_ = [("n_env", C.c_int32), ("depth", C.c_int32), ("n_slots", C.c_int32), ("drive_mode", C.c_int32), ("t0", C.c_int32),
+                ("cause_mask", C.c_int32), ("early_fall_steps", C.c_int32), ("grid", C.c_int32),
+                ("speed2_limit", C.c_float), ("ang_speed2_limit", C.c_float),
+                ("root_state", C.c_void_p), ("dof_state", C.c_void_p), ("warm_start", C.c_void_p), ("drive", C.c_void_p),
+                ("rb_state", C.c_void_p), ("contact_force", C.c_void_p), ("dof_force", C.c_void_p),
+                ("progress_buf", C.c_void_p), ("reset_buf", C.c_void_p), ("terminate_buf", C.c_void_p),
+                ("ring", C.c_void_p), ("slots", C.c_void_p), ("counters", C.c_void_p), ("last_capture_step", C.c_void_p),
+                ("cause_ws", C.c_void_p), ("request", C.c_void_p)]
+
+
 class LocoValStep(C.Structure):
     """EmlocoLocoValStep (include/emloco_predictor.h)."""
     _fields_ = [("n_env", C.c_int32), ("step_to_pred", C.c_int32), ("gamma", C.c_float), ("inversion_penalty", C.c_float),

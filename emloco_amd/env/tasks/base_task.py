@@ -56,6 +56,9 @@ class BaseTask():
 
     def step(self, actions):                                   # base_task.py:245-265
         self.pre_physics_step(actions)
+        cb = getattr(self, "before_physics_launch", None)      # (the twin of the hook below: the step's drive input is in place, the
+        if cb is not None:                                      # rigid-body launch not yet issued -- the flight recorder's record())
+            cb()
         self._physics_step()
         cb = getattr(self, "after_physics_launch", None)       # (a rollout loop's hook: host work to issue WHILE the rigid-body launch
         if cb is not None:                                      # runs -- side-stream launches that want to start under it)

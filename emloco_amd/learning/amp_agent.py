@@ -301,6 +301,7 @@ class AMPAgent:
         self._idx_buf = torch.randperm(self.batch_size)
         self.epoch_num, self.frame = 0, 0
         self.episode_stats = None                             # learning/episode_stats.py: set by the driver (run.py --experiment / --stats)
+        self.flight_recorder = None                           # learning/flight_recorder.py: a bound FlightRecorder, set by the driver (--capture)
         self.train_result = {}
         self._init_amp_demo_buf()
 
@@ -378,6 +379,8 @@ class AMPAgent:
                 obs, rewards, dones, infos = self.vec_env.step(torch.clamp(res["actions"], -1.0, 1.0))
                 if self.episode_stats is not None:
                     self.episode_stats.step()                     # behind the step's flags, ahead of the next reset
+                if self.flight_recorder is not None:
+                    self.flight_recorder.check()
                 buf["rewards"][n] = rewards.unsqueeze(-1) if rewards.dim() == 1 else rewards
                 buf["next_obses"][n] = obs
                 buf["dones"][n] = dones.to(torch.uint8)

@@ -285,6 +285,7 @@ class LocoValEvaluator:
         env = vec_env.env if hasattr(vec_env, "env") else vec_env
         self.env, self.task = env, env.task
         task = self.task
+        self.flight_recorder = None               # learning/flight_recorder.py: a bound FlightRecorder, set by the driver (--capture)
         self.track = bool(track)
         if self.track:                            # refused by name before anything is allocated
             self.track_stride = track_stride(task._traj_sample_timestep, task.dt, task.max_episode_length)
@@ -398,6 +399,8 @@ class LocoValEvaluator:
                 self.env.reset(task.reset_buf.nonzero(as_tuple=False).flatten())
             actions = self.policy(task.obs_buf)
             _obs, _rew, dones, infos = self.vec_env.step(actions)
+            if self.flight_recorder is not None:
+                self.flight_recorder.check()                      # (a bound FlightRecorder, set by the driver: run.py --test --capture)
             disc = None if self.disc_reward is None else self.disc_reward(infos["amp_obs"]).contiguous().float()
             self._launch(task.reward_raw, disc, dones, infos.get("terminate", getattr(task, "_terminate_buf", None)), task.inverted)
         self.steps_run += 1

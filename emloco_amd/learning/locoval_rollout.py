@@ -121,6 +121,7 @@ class LocoValRollout:
         self._disc_halves = None
         # game statistics (learning/episode_stats.py): off unless attach_episode_stats() is called -- no launch, no allocation
         self.episode_stats = None
+        self.flight_recorder = None                         # learning/flight_recorder.py: off unless attach_flight_recorder() is called
         self._epoch_fit = None
         self.epoch_num = 0
         if self.fused:
@@ -443,6 +444,14 @@ class LocoValRollout:
         self._step_fit = None if stats is None else torch.zeros(2, device=self.device)
         self._epoch_base = None if stats is None else self._stats.detach().cpu().numpy().copy()
 
+    def attach_flight_recorder(self, recorder):
+        """Turn the flight recorder on (a `FlightRecorder` of this loop's task) or off (None).  On: its record() ahead of every
+        rigid-body launch (the task's `before_physics_launch` hook) and its check() where the statistics launch sits; nothing the loop
+        or the simulation computes changes.  The caller drains it once per epoch (`CaptureLog.end_epoch`)."""
+        if self.flight_recorder is not None:
+            self.flight_recorder.unbind()
+        self.flight_recorder = None if recorder is None else recorder.bind()
+
     def epoch_report(self):
         """After end_epoch(), with the statistics on: the game report of the epoch and the loop's own numbers of the per-epoch line
         (common_agent.py:205-207,236): `vnet_loss` = the epoch's loss sum / fitted episodes, `vnet_pred` / `combine_rwd` = the means of
@@ -491,6 +500,8 @@ class LocoValRollout:
             self.frames += self.num_actors
             if self.episode_stats is not None:
                 self.episode_stats.step()                         # behind the step's flags, ahead of the next reset_done()
+            if self.flight_recorder is not None:
+                self.flight_recorder.check()                      # the same place: the state after the step, no finished env reset yet
             if self._disc_halves is not None and getattr(task, "_returns_in_flags", False):
                 self._deferred_disc_step(infos["amp_obs"])
                 return

@@ -158,6 +158,44 @@ def pop_test_options(argv):
     return opt
 
 
+# ---------------------------------------------------------------------------------------------------------------- the flight recorder
+def capture_options(argv):
+    """Remove the flight recorder's options from argv (get_args does not know them): None without --capture, else the arguments of
+    `make_capture`.  Non-finite states are always a cause; the speed and early-fall causes are off unless their option is given."""
+    path = _pop_opt(argv, "--capture")
+    raw = {k: _pop_opt(argv, "--capture_" + k) for k in ("depth", "slots", "speed", "ang_speed", "early_fall")}
+    if path is None:
+        given = [k for k, v in raw.items() if v is not None]
+        if given:
+            raise SystemExit(f"run.py: --capture_{given[0]} sets up the flight recorder: turn it on with --capture PATH")
+        return None
+    try:
+        opt = dict(path=path, depth=int(raw["depth"] or 8), slots=int(raw["slots"] or 16),
+                   speed=None if raw["speed"] is None else float(raw["speed"]),
+                   ang_speed=None if raw["ang_speed"] is None else float(raw["ang_speed"]),
+                   early_fall=None if raw["early_fall"] is None else int(raw["early_fall"]))
+    except ValueError as e:
+        raise SystemExit(f"run.py: --capture_*: {e}")
+    if opt["depth"] < 1 or opt["slots"] < 1 or any(opt[k] is not None and not opt[k] >= 0 for k in ("speed", "ang_speed", "early_fall")):
+        raise SystemExit("run.py: --capture_depth / --capture_slots must be at least 1, the limits not negative")
+    return opt
+
+
+def make_capture(task, opt, rank=0, world=1):
+    """The run's flight recorder and its file (learning/flight_recorder.py): rank r of several writes PATH with _rank{r} ahead of the
+    extension.  To be called once the loop is built: a task whose launch arrangement the recorder cannot follow (overlap_reset, which
+    a loop's constructor switches on) stops the run by name here; switched on later still, it raises where the recorder is bound."""
+    from .learning.flight_recorder import CaptureLog, FlightRecorder, rank_path
+    try:
+        rec = FlightRecorder(task, depth=opt["depth"], slots=opt["slots"], speed=opt["speed"], ang_speed=opt["ang_speed"],
+                             early_fall=opt["early_fall"])
+    except RuntimeError as e:
+        raise SystemExit(f"run.py --capture: {e}")
+    path = rank_path(opt["path"], rank, world)
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    return CaptureLog(rec, path, per_file=opt.get("per_file", 256))
+
+
 # ---------------------------------------------------------------------------------------------------------------- the training driver
 def train_options(argv, args=None):
     """What the driver needs of the command line, checked before anything touches a device: `--steps N` is taken out of argv (get_args
@@ -285,11 +323,13 @@ class LocoValTrainee:
     """The LocoVal fit under run_training: an epoch is one horizon of `LocoValRollout.step_once` and `end_epoch`."""
     kind = "locoval"
 
-    def __init__(self, agent, world=1, rank=0, stats=None):
-        self.agent, self.world, self.rank, self.stats = agent, world, rank, stats
+    def __init__(self, agent, world=1, rank=0, stats=None, capture=None):
+        self.agent, self.world, self.rank, self.stats, self.capture = agent, world, rank, stats, capture
         self.horizon_length = agent.horizon_length
         if stats is not None:
             agent.attach_episode_stats(stats)
+        if capture is not None:
+            agent.attach_flight_recorder(capture.recorder)
 
     epoch_num = property(lambda self: self.agent.epoch_num)
     frame = property(lambda self: self.agent.frames * self.world)
@@ -310,6 +350,8 @@ class LocoValTrainee:
         dt = max(time.time() - t0, 1e-9)
         frames = a.num_actors * self.world * a.horizon_length
         info.update(fps_step=frames / dt, fps_total=frames / dt, ep_time=dt)     # the fit runs beside the rollout: one clock for both
+        if self.capture is not None:
+            info.update(self.capture.end_epoch())        # one read of the counters; the file grows only when captures were taken
         return info
 
     def save(self, mof, epoch=None):
@@ -330,10 +372,11 @@ class PolicyTrainee:
     """PPO + AMP under run_training: an epoch is one `AMPAgent.train_epoch`."""
     kind = "policy"
 
-    def __init__(self, agent, world=1, rank=0, stats=None):
-        self.agent, self.world, self.rank, self.stats = agent, world, rank, stats
+    def __init__(self, agent, world=1, rank=0, stats=None, capture=None):
+        self.agent, self.world, self.rank, self.stats, self.capture = agent, world, rank, stats, capture
         self.horizon_length = agent.horizon_length
         agent.episode_stats = stats
+        agent.flight_recorder = None if capture is None else capture.recorder.bind()
 
     epoch_num = property(lambda self: self.agent.epoch_num)
     frame = property(lambda self: self.agent.frame * self.world)
@@ -344,6 +387,8 @@ class PolicyTrainee:
         out.update(fps_step=info["fps_step"] * self.world, fps_total=info["fps_total"] * self.world, ep_time=info["total_time"])
         if self.stats is not None:
             out["games"] = self.stats.end_epoch()
+        if self.capture is not None:
+            out.update(self.capture.end_epoch())
         out["tail"] = (f"\ta_loss {info['actor_loss']:.4f} c_loss {info['critic_loss']:.4f} disc_loss {info['disc_loss']:.4f} "
                        f"kl {info['kl']:.5f}")
         task = getattr(self.agent, "task", None)
@@ -370,6 +415,9 @@ def main(argv=None):
     train_opt = train_options(argv)                      # (--steps leaves argv; a bad combination stops the run before any device call)
     # --test (the reference's player, amp_value_players.py): its own options, checked before anything touches a device
     opt = pop_test_options(argv)
+    cap_opt = capture_options(argv)
+    if cap_opt is not None and "--test" not in argv:
+        train_opt["driver"] = True                       # the recorder is drained once per epoch: the run goes through the driver
     games_num, eval_out, eval_records, max_steps = opt["games_num"], opt["eval_out"], opt["eval_records"], opt["max_steps"]
     compare, eval_tracks = opt["compare"], opt["eval_tracks"]
     if "--test" in argv:
@@ -423,7 +471,8 @@ def main(argv=None):
     env = RLGPUEnv(create_rlgpu_env(args, cfg, cfg_train, rank=rank))
     say = print if rank == 0 else (lambda *a, **k: None)
     if args.test:
-        _run_test(args, env, policy_ckpt, games_num, max_steps, eval_out, eval_records, rank, world, say, compare, eval_tracks)
+        capture = None if cap_opt is None else make_capture(env.env.task, cap_opt, rank, world)
+        _run_test(args, env, policy_ckpt, games_num, max_steps, eval_out, eval_records, rank, world, say, compare, eval_tracks, capture)
         return
     if train_policy:
         import yaml
@@ -432,10 +481,11 @@ def main(argv=None):
         agent = AMPAgent(env, yaml.safe_load(open(DEFAULT_CFG)))
         if policy_ckpt:
             agent.restore(policy_ckpt)
+        capture = None if cap_opt is None else make_capture(env.env.task, cap_opt, rank, world)
         if train_opt["driver"]:
             from .learning.episode_stats import EpisodeStats
             stats = EpisodeStats(env.env.task) if train_opt["stats"] else None           # the policy trainer's rewards carry no penalty
-            run_training(PolicyTrainee(agent, world, rank, stats), train_opt, say, rank)
+            run_training(PolicyTrainee(agent, world, rank, stats, capture), train_opt, say, rank)
         else:
             policy_loop(agent, steps, say)
         return
@@ -447,12 +497,14 @@ def main(argv=None):
         kw = dict(policy=bundle.policy, disc_reward=bundle.disc_reward,
                   inversion_penalty_scale=float(bundle.config.get("inversion_penalty_scale", 0.3)))
     agent = LocoValRollout(env, use_pose=args.input_init_pose, use_vel=args.input_init_vel, **kw)
+    # (behind the loop's constructor, which is where a launch arrangement is switched on: EMLOCO_OVERLAP_RESET=1 stops the run here)
+    capture = None if cap_opt is None else make_capture(env.env.task, cap_opt, rank, world)
     if train_opt["driver"]:
         stats = None
         if train_opt["stats"]:
             from .learning.episode_stats import EpisodeStats
             stats = EpisodeStats(env.env.task, inverted_penalty=agent.inversion_penalty_scale)
-        run_training(LocoValTrainee(agent, world, rank, stats), train_opt, say, rank)
+        run_training(LocoValTrainee(agent, world, rank, stats, capture), train_opt, say, rank)
     else:
         locoval_loop(agent, env.env.num_envs, world, steps, say)
     if world > 1:
@@ -478,7 +530,8 @@ def _gather_track_columns(ev, world):
     return {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
 
 
-def _run_test(args, env, policy_ckpt, games_num, max_steps, eval_out, eval_records, rank, world, say, compare=(), eval_tracks=False):
+def _run_test(args, env, policy_ckpt, games_num, max_steps, eval_out, eval_records, rank, world, say, compare=(), eval_tracks=False,
+              capture=None):
     """--test: LocoValEvaluator with the frozen policy (deterministic actions) and the LocoVal network of --valuenet_path."""
     import json
     import yaml
@@ -508,18 +561,23 @@ def _run_test(args, env, policy_ckpt, games_num, max_steps, eval_out, eval_recor
     if compare:
         _run_compare(args, env, bundle, valuenet, compare, int(games_num) if games_num else int(player.get("games_num", 200)),
                      int(max_steps) if max_steps else 27000, float(config.get("gamma", 0.99)), eval_out, eval_records, rank, world, say,
-                     eval_tracks)
+                     eval_tracks, capture)
         return
     try:
         ev = LocoValEvaluator(env, bundle, valuenet, int(games_num) if games_num else int(player.get("games_num", 200)),
                               max_steps=int(max_steps) if max_steps else 27000, gamma=float(config.get("gamma", 0.99)), track=eval_tracks)
     except TrackRefusal as e:                    # --eval_tracks on a task it cannot sample: a message, no traceback
         raise SystemExit(f"run.py --test: {e}")
+    if capture is not None:
+        ev.flight_recorder = capture.recorder.bind()
     t0 = time.time()
     rep = ev.run(say=say)
     torch.cuda.synchronize()
     rep["seconds"] = time.time() - t0
     say(f"{rep['steps']} steps of {ev.envs_total} envs in {rep['seconds']:.2f} s")
+    if capture is not None:                  # --test: one drain at the end of the run
+        rep.update(capture.end_epoch())
+        say(f"flight recorder: {rep['captures']} captures in {capture.path}")
     recs = ev.records()
     pred_row = ev.pred_rows(recs)
     if pred_row is not None:                 # --pred_path: the table row every game walked joins a record to its sample / mode
@@ -555,7 +613,7 @@ def compare_columns(recs):
 
 
 def _run_compare(args, env, bundle, valuenet, compare, games_num, max_steps, gamma, eval_out, eval_records, rank, world, say,
-                 eval_tracks=False):
+                 eval_tracks=False, capture=None):
     """--test with --compare_valuenet: the network of --valuenet_path and the added ones on the same games, played once."""
     import json
     from .learning.locoval_eval import LocoValEvaluator, TrackRefusal
@@ -575,11 +633,15 @@ def _run_compare(args, env, bundle, valuenet, compare, games_num, max_steps, gam
         ev = LocoValEvaluator(env, bundle, nets, games_num, max_steps=max_steps, gamma=gamma, track=eval_tracks)
     except TrackRefusal as e:                    # --eval_tracks on a task it cannot sample: a message, no traceback
         raise SystemExit(f"run.py --test: {e}")
+    if capture is not None:
+        ev.flight_recorder = capture.recorder.bind()
     t0 = time.time()
     rep = ev.run(say=say)
     torch.cuda.synchronize()
     seconds = time.time() - t0
     say(f"{ev.steps_run} steps of {ev.envs_total} envs in {seconds:.2f} s, {len(nets)} networks on the same games")
+    if capture is not None:                  # one drain at the end of the run
+        say(f"flight recorder: {capture.end_epoch()['captures']} captures in {capture.path}")
     if eval_records:
         parts = [compare_columns(ev.records())]
         pred_row = ev.pred_rows(ev.records(0))

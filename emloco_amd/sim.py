@@ -135,6 +135,7 @@ class NativeSim:
         self.pd_target = self._tensor(L.T_PD_TARGET)
         self.warm_start = self._tensor(L.T_WARM_START)
         self._plan_spec, self._plan_parts, self._plan_calls = None, 4, 0       # set_plan_spec
+        self.drive_mode = int(self.params.drive_mode)      # the live mode: that of the last drive upload (include/emloco_sim.h)
 
     def _tensor(self, kind):
         ptr = C.c_void_p()
@@ -148,12 +149,14 @@ class NativeSim:
     # ------------------------------------------------------------------ gym-level operations
     def set_pd_targets(self, targets):
         L.check(self.lib.emloco_sim_set_pd_targets(self._h, dptr(targets), self._stream()), "emloco_sim_set_pd_targets")
+        self.drive_mode = 0
 
     def set_dof_actuation_force(self, forces):
         """Joint torques [n_env][69] for effort drives (emloco_sim_set_dof_actuation_force); set_pd_targets switches back."""
         if forces.dtype != torch.float32 or forces.numel() != self.num_envs * 69:
             raise L.EmlocoError("actuation forces must be a float32 [n_env][69] tensor")
         L.check(self.lib.emloco_sim_set_dof_actuation_force(self._h, dptr(forces), self._stream()), "emloco_sim_set_dof_actuation_force")
+        self.drive_mode = 1
 
     def step(self, n_calls=1):
         if self._plan_spec is not None and self._plan_calls != n_calls:

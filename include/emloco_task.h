@@ -370,6 +370,74 @@ int emloco_episode_stats_step(int n_envs, const float *dev_rew_buf, const float 
 int emloco_episode_stats_reduce(int n_envs, double *dev_totals, double *dev_moments, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Flight recorder: a ring on the device holds the rigid-body step's per-env INPUTS of the last R control steps of every env; an env
+ * that trips a trigger has its ring frozen into a capture slot, with the state after the step, without the host being involved.  The
+ * recorder only reads the simulation.  A capture replays through the CPU oracle bit for bit (tools/replay_capture.py).
+ *
+ * Record, EMLOCO_REC_WORDS 32-bit words, one (env, control step), taken ahead of the rigid-body launch:
+ *   [0] progress_buf as int32   [1] the step counter t   [2] drive_mode   [3] 0
+ *   [4 ..) root_state [13] | dof_state [69][2] | warm start [EMLOCO_MAXCAND * 3] | drive input [69]  (508 floats, copied bit for bit)
+ * Ring [n_env][R][EMLOCO_REC_WORDS]; step t of every env lies in ring row t % R.
+ * Slot, EMLOCO_REC_SLOT_WORDS(R) words:
+ *   [0] env   [1] t of the trigger   [2] cause bits   [3] n_valid = min(t - t0 + 1, R) records
+ *   [4 ..) R records, oldest first: the steps t - n_valid + 1 .. t, the records behind them zero
+ *   then EMLOCO_REC_POST_WORDS floats, the state after step t: root_state [13] | dof_state [69][2] | warm start [96 * 3] |
+ *   rigid-body state [24][13] | contact force [24][3] | dof force [69]
+ * Causes (cause_mask selects which are looked at):
+ *   NONFINITE   any of the env's 24 x 13 body-state values is NaN or +-Inf (the test of EMLOCO_EPM_NONFINITE_STEPS)
+ *   SPEED       for some body (vx vx + vy vy) + vz vz > speed2_limit, float32 in this order, strictly; a NaN is not greater
+ *   ANG_SPEED   the same on the angular velocity against ang_speed2_limit
+ *   EARLY_FALL  terminate_buf != 0 and progress_buf < early_fall_steps
+ *   REQUEST     request[env] != 0 (request may be NULL: never)
+ * An env whose last capture is less than R steps back (t - last_capture_step[env] < R) is suppressed: no cause, no count, and a
+ * request byte it carries is cleared.  The triggered envs of a step take the free slots in ascending env index; one that finds none
+ * adds one to the overflow counter of each of its causes and keeps last_capture_step -- and its request byte, which is cleared only
+ * when the request is served or suppressed.  Nothing of this depends on grid sizes, dispatch order or timing: the claim is one
+ * workgroup, everything else writes per-env or per-slot words.
+ * counters [EMLOCO_REC_COUNTERS] int32: [0] slots in use (the host reads it, copies that many slots and clears it), [1 + k] envs that
+ * found no slot, per cause bit k. */
+#define EMLOCO_REC_WORDS 512
+#define EMLOCO_REC_POST_WORDS 892
+#define EMLOCO_REC_SLOT_WORDS(R) (4 + (R) * EMLOCO_REC_WORDS + EMLOCO_REC_POST_WORDS)
+#define EMLOCO_REC_COUNTERS 8
+enum {
+    EMLOCO_REC_NONFINITE = 1, EMLOCO_REC_SPEED = 2, EMLOCO_REC_ANG_SPEED = 4, EMLOCO_REC_EARLY_FALL = 8, EMLOCO_REC_REQUEST = 16
+};
+typedef struct EmlocoRecorderBufs {
+    int32_t n_env, depth, n_slots;  /* E, R (>= 1), C (>= 1) */
+    int32_t drive_mode;             /* the simulator's live drive mode (EmlocoSimParams), written into every record */
+    int32_t t0;                     /* t of the first emloco_recorder_record call */
+    int32_t cause_mask;             /* EMLOCO_REC_* bits */
+    int32_t early_fall_steps;
+    int32_t grid;                   /* workgroups of the grid-stride launches, 0: one per env (record, cause bits) / per slot, at most 1024; no result depends on it */
+    float speed2_limit, ang_speed2_limit;   /* squared limits, >= 0 (+Inf: never) */
+    const float *root_state;        /* [E][13]        EMLOCO_T_ROOT_STATE */
+    const float *dof_state;         /* [E][69][2]     EMLOCO_T_DOF_STATE */
+    const float *warm_start;        /* [E][96 * 3]    EMLOCO_T_WARM_START */
+    const float *drive;             /* [E][69]        EMLOCO_T_PD_TARGET: the position targets, or under drive_mode 1 the torques (one buffer) */
+    const float *rb_state;          /* [E][24][13]    EMLOCO_T_RIGID_BODY */
+    const float *contact_force;     /* [E][24][3]     EMLOCO_T_CONTACT_FORCE */
+    const float *dof_force;         /* [E][69]        EMLOCO_T_DOF_FORCE */
+    const int64_t *progress_buf, *reset_buf, *terminate_buf;       /* [E] the task's buffers */
+    uint32_t *ring;                 /* [E][R][EMLOCO_REC_WORDS], 16-byte aligned */
+    uint32_t *slots;                /* [C][EMLOCO_REC_SLOT_WORDS(R)], 16-byte aligned */
+    int32_t *counters;              /* [EMLOCO_REC_COUNTERS], zeroed by the caller */
+    int32_t *last_capture_step;     /* [E], initialised by the caller to a value <= t0 - R */
+    int32_t *cause_ws;              /* [E] scratch: the step's cause bits */
+    uint8_t *request;               /* [E] or NULL */
+} EmlocoRecorderBufs;
+
+/* One launch, a pure copy: every env's record of step t into ring row t % R.  To be issued when the drive input of the step is in
+ * place and before the rigid-body launch, on the stream every writer of the env state is ordered on.  (The pieces of a record lie
+ * back to back, so only its 16-byte stores are wide: of the sources a root row is 52 bytes, a drive row 276.) */
+int emloco_recorder_record(const EmlocoRecorderBufs *rec, int t, void *stream);
+/* Three launches on the one stream: cause bits per env | the claim (one workgroup) | the copies into the slots claimed at this step.
+ * To be issued where emloco_episode_stats_step is: behind the step's post-physics pass, ahead of any reset.
+ * Both: a NULL structure or required pointer, n_env <= 0, depth < 1, n_slots < 1, t < t0, a misaligned ring or slot array, a limit
+ * that is negative or NaN: -1 with the argument named in emloco_last_error(), nothing is written. */
+int emloco_recorder_check(const EmlocoRecorderBufs *rec, int t, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * The motion library's clip cache from raw clip frames: what utils/motion_lib_smpl.py `clip_cache` (the reference's
  * load_motion_with_skeleton + poselib, motion_lib_smpl.py:84-131, skeleton3d.py:1249-1272) builds per (clip, skeleton) pair on the host
  * in float64, for n_clips pairs in one launch in float32.  The frames of all clips lie in rows [0, n_frames_total) of every array;
