@@ -161,6 +161,20 @@ class RecorderBufs(C.Structure):
                 ("cause_ws", C.c_void_p), ("request", C.c_void_p)]
 
 
+CROWD_ROOT_X, CROWD_ROOT_Y, CROWD_MAX_RES = 10, 20, 64          # EMLOCO_CROWD_*
+
+
+class CrowdBufs(C.Structure):
+    """EmlocoCrowdBufs (include/emloco_task.h): the crowd-aware terrain sensor's inputs, owner map and observation rows."""
+    _fields_ = [("n_env", C.c_int32), ("group_size", C.c_int32), ("hf_rows", C.c_int32), ("hf_cols", C.c_int32), ("head_body", C.c_int32),
+                ("res", C.c_int32), ("channels", C.c_int32), ("stamps", C.c_int32), ("stamp_units", C.c_int32),
+                ("src_width", C.c_int32), ("dst_width", C.c_int32), ("n_copy", C.c_int32), ("tag_shift", C.c_int32), ("tag", C.c_uint32),
+                ("hscale", C.c_float), ("vscale", C.c_float),
+                ("rb_state", C.c_void_p), ("heightfield", C.c_void_p), ("probe_xy", C.c_void_p), ("root_x", C.c_void_p),
+                ("root_y", C.c_void_p), ("owner", C.c_void_p), ("src_obs", C.c_void_p), ("src_flip_obs", C.c_void_p),
+                ("obs", C.c_void_p), ("flip_obs", C.c_void_p)]
+
+
 class LocoValStep(C.Structure):
     """EmlocoLocoValStep (include/emloco_predictor.h)."""
     _fields_ = [("n_env", C.c_int32), ("step_to_pred", C.c_int32), ("gamma", C.c_float), ("inversion_penalty", C.c_float),

@@ -20,7 +20,27 @@ from ...utils.flags import flags
 from . import humanoid_traj
 
 
+def _sequential_only(name):
+    """a launch-arrangement switch that stays off: reading gives False, switching it on raises"""
+    def fget(self):
+        return False
+
+    def fset(self, value):
+        if value:
+            raise RuntimeError(f"HumanoidPedestrianTerrain with a crowd sensor configuration runs the sequential launch arrangement: {name} "
+                               "launches observation passes that no crowd-sensor call follows")
+    return property(fget, fset)
+
+
 class HumanoidPedestrianTerrain(humanoid_traj.HumanoidTraj):
+    def __new__(cls, cfg=None, *args, **kwargs):
+        # a crowd sensor configuration is served by the subclass below; with any other the task is this class, line for line as before
+        # (cfg None: `T.__new__(T)`, an object without a configuration, as object.__new__ gives it)
+        from ...crowd_sensor import is_crowd_config
+        if cls is HumanoidPedestrianTerrain and cfg is not None and is_crowd_config(cfg["env"]):
+            cls = HumanoidPedestrianTerrainCrowd
+        return object.__new__(cls)
+
     def __init__(self, cfg, sim_params, physics_engine, device_type, device_id, headless):
         self.real_mesh = getattr(cfg.get('args', None), "real_mesh", False)
         if self.real_mesh:
@@ -38,11 +58,27 @@ class HumanoidPedestrianTerrain(humanoid_traj.HumanoidTraj):
         self.terrain_obs_type = cfg['env'].get("terrain_obs_type", "square")
         self.terrain_obs = cfg['env'].get("terrain_obs", False)
         self.terrain_obs_root = cfg['env'].get("terrain_obs_root", "pelvis")
-        self.velocity_map = cfg["env"].get("velocity_map", False)
+        self.velocity_map = bool(cfg["env"].get("velocity_map", False))
+        self._divide_group = bool(cfg["env"].get("divide_group", False))                         # humanoid.py:221-226
+        self._group_num_people = min(int(cfg["env"].get("num_env_group", 128)), self.num_envs)
+        if cfg["env"].get("group_obs", False):
+            raise NotImplementedError("group_obs: True (the point-net observation of the other members' joints) is not built")
         if not (self.terrain_obs and self.terrain_obs_type == "square" and self.terrain_obs_root == "head" and
-                self.sensor_res == 32 and self.sensor_extent == 2 and cfg['env'].get("use_center_height", False) and
-                self.power_reward and self.location_coefficient == 1 and not self.velocity_map):
+                cfg['env'].get("use_center_height", False) and self.power_reward and self.location_coefficient == 1):
             raise NotImplementedError("emloco fused kernels cover pacer.yaml's terrain observation / reward settings")
+        if not (isinstance(self.sensor_res, int) and 1 <= self.sensor_res <= L.CROWD_MAX_RES):
+            raise ValueError(f"sensor_res: {self.sensor_res!r} is not an integer in 1 .. {L.CROWD_MAX_RES}")
+        if not float(self.sensor_extent) > 0:
+            raise ValueError(f"sensor_extent: {self.sensor_extent!r} is not a positive length")
+        # crowd mode: any departure from the 32 x 32, +-2 m, one-channel grid without groups.  The fused kernel keeps its row; a
+        # crowd-sensor call behind every observation launch fills the rows of the reference's width (emloco_amd/crowd_sensor.py)
+        from ...crowd_sensor import group_layout, is_crowd_config
+        self._crowd_mode = is_crowd_config(cfg["env"])
+        if self._crowd_mode and not isinstance(self, HumanoidPedestrianTerrainCrowd):
+            raise NotImplementedError(f"{type(self).__name__}: a crowd sensor configuration is served by HumanoidPedestrianTerrainCrowd only")
+        if self._crowd_mode and self._divide_group:
+            group_layout(self.num_envs, self._group_num_people)               # refuses numEnvs that is no multiple, by name
+        self._crowd = None
         self.num_height_points = self.sensor_res * self.sensor_res
         self.num_center_height_points = 9
         self.center_height_points = self.init_center_height_points()
@@ -58,6 +94,8 @@ class HumanoidPedestrianTerrain(humanoid_traj.HumanoidTraj):
         self._fused_reset = bool(cfg["env"].get("fused_reset", True)) and self._state_init == self.StateInit.Random \
             and not flags.vru and not flags.add_noise and not flags.fixed_path and not flags.slow \
             and not flags.pred_path                  # predicted paths are placed by the host reset (TrajGenerator.reset), which knows the row
+        if self._crowd_mode:                         # the fused reset's observation launches are not followed by a crowd-sensor call
+            self._fused_reset = False
         self._reset_bufs = None
         return
 
@@ -67,7 +105,7 @@ class HumanoidPedestrianTerrain(humanoid_traj.HumanoidTraj):
         if (self._enable_task_obs):
             obs_size = 2 * self._num_traj_samples
             if self.terrain_obs:
-                obs_size += self.num_height_points
+                obs_size += self.num_height_points * (3 if self.velocity_map else 1)     # :306-310
         return obs_size
 
     def get_task_obs_size_detail(self):
@@ -76,7 +114,10 @@ class HumanoidPedestrianTerrain(humanoid_traj.HumanoidTraj):
         if (self._enable_task_obs):
             d['traj'] = 2 * self._num_traj_samples
         if self.terrain_obs:
-            d['heightmap'] = self.num_height_points
+            if self.velocity_map:                                                          # :326-330
+                d['heightmap_velocity'] = self.num_height_points * 3
+            else:
+                d['heightmap'] = self.num_height_points
         return d
 
     def get_head_pose(self, env_ids=None):
@@ -127,6 +168,9 @@ class HumanoidPedestrianTerrain(humanoid_traj.HumanoidTraj):
 
     # ------------------------------------------------------------------ fused step plumbing
     def _make_post_bufs(self):
+        return self._make_post_bufs_on(self.obs_buf, self._flip_obs_buf)
+
+    def _make_post_bufs_on(self, obs_buf, flip_obs_buf):
         return self._post.make_bufs(
             n_env=self.num_envs, heightfield=self.height_samples.contiguous(), dt=self.dt,
             traj_dur=self._traj_gen.get_traj_duration(), sample_dt=self._traj_sample_timestep,
@@ -135,7 +179,7 @@ class HumanoidPedestrianTerrain(humanoid_traj.HumanoidTraj):
             rb_state=self._rigid_body_state, dof_state=self._dof_state, dof_force=self.dof_force_tensor,
             contact_force=self._contact_forces, betas=self.humanoid_betas, traj_verts=self._traj_gen._verts,
             progress_buf=self.progress_buf, reset_buf=self.reset_buf, terminate_buf=self._terminate_buf,
-            obs_buf=self.obs_buf, flip_obs_buf=self._flip_obs_buf, rew_buf=self.rew_buf, reward_raw=self.reward_raw,
+            obs_buf=obs_buf, flip_obs_buf=flip_obs_buf, rew_buf=self.rew_buf, reward_raw=self.reward_raw,
             amp_obs_buf=self._amp_obs_buf)
 
     # ------------------------------------------------------------------ fused device reset (include/emloco_task.h)
@@ -461,6 +505,37 @@ class HumanoidPedestrianTerrain(humanoid_traj.HumanoidTraj):
         self._motion_start_times[env_ids] = motion_times
         self._sampled_motion_ids[env_ids] = motion_ids
         return
+
+
+class HumanoidPedestrianTerrainCrowd(HumanoidPedestrianTerrain):
+    """HumanoidPedestrianTerrain with a crowd sensor configuration (divide_group / num_env_group / velocity_map / sensor_res /
+    sensor_extent: `HumanoidPedestrianTerrain(cfg, ...)` returns this class for one).  The fused post-physics kernel keeps its
+    1422-wide row and writes into two scratch buffers; a crowd-sensor call behind every observation launch copies the self and
+    location columns of the rows it is asked for into the task's buffers, which have the reference's width, and fills the sensor block
+    beside them (emloco_amd/crowd_sensor.py).  Sequential launch arrangement, host reset path."""
+    fused_chain = _sequential_only("fused_chain")
+    overlap_obs = _sequential_only("overlap_obs")
+    overlap_reset = _sequential_only("overlap_reset")
+
+    def _make_post_bufs(self):
+        from ...crowd_sensor import CrowdSensor
+        n_copy = L.SELF_OBS + 2 * self._num_traj_samples
+        assert self._num_traj_samples == L.TRAJ_SAMPLES and self.obs_buf.shape[1] == L.SELF_OBS + self.get_task_obs_size()
+        self._crowd_src_obs = torch.zeros((self.num_envs, L.OBS), device=self.device)
+        self._crowd_src_flip = torch.zeros((self.num_envs, L.OBS), device=self.device)
+        self._crowd = CrowdSensor(
+            rb_state=self._rigid_body_state, heightfield=self.height_samples.contiguous(), hscale=self.terrain.horizontal_scale,
+            vscale=self.terrain.vertical_scale, head_body=self._post.head_body, n_env=self.num_envs,
+            num_env_group=self._group_num_people, stamps=self._divide_group, velocity_map=self.velocity_map, res=self.sensor_res,
+            extent=float(self.sensor_extent), obs=self.obs_buf, flip_obs=self._flip_obs_buf, src_obs=self._crowd_src_obs,
+            src_flip_obs=self._crowd_src_flip, n_copy=n_copy)
+        return self._make_post_bufs_on(self._crowd_src_obs, self._crowd_src_flip)
+
+    def _launch_post(self, mode, env_ids=None):
+        super()._launch_post(mode, env_ids)
+        if mode & L.POST_OBS:
+            ids = None if env_ids is None else self._humanoid_actor_ids[env_ids.to(self.device)].contiguous()
+            self._crowd.run(ids)
 
 
 def poles_terrain(terrain, difficulty=1):                           # :937-993

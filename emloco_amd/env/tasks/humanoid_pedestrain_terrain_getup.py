@@ -64,6 +64,10 @@ class HumanoidPedestrianTerrainGetup(HumanoidPedestrianTerrain):
 
     def __init__(self, cfg, sim_params, physics_engine, device_type, device_id, headless):
         env = cfg["env"]
+        from ...crowd_sensor import is_crowd_config
+        if is_crowd_config(env):
+            raise NotImplementedError("HumanoidPedestrianTerrainGetup: the crowd sensor (divide_group / velocity_map / sensor_res / sensor_extent) "
+                                      "is built for HumanoidPedestrianTerrain only")
         self._recovery_episode_prob_tgt = self._recovery_episode_prob = float(env["recoveryEpisodeProb"])       # :24-26
         self._recovery_steps_tgt = self._recovery_steps = int(env["recoverySteps"])
         self._fall_init_prob_tgt = self._fall_init_prob = float(env["fallInitProb"])

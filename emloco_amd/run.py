@@ -461,6 +461,12 @@ def main(argv=None):
         args.num_envs = shard_range(int(args.num_envs), rank, world)[1]
     cfg, cfg_train, _ = load_cfg(args)
     fill_flags(args)
+    from .crowd_sensor import is_crowd_config
+    if is_crowd_config(cfg["env"]) and (use_policy or train_policy or args.test):
+        raise SystemExit("run.py: the configuration asks for the crowd sensor (divide_group / velocity_map / sensor_res / sensor_extent), whose "
+                         "observations the policy network here cannot read: the reference's CNN trunk (amp_network_sept_cnn_builder.py) is "
+                         "not built.  Without --policy_checkpoint, --policy_random_init, --train_policy and --test the run is the LocoVal "
+                         "loop under noise actions")
     if flags.pred_path:                                  # a missing table stops the run here, by name, before the simulator is built
         from .env.util.traj_generator import PRED_TRAJ_FILE
         import os

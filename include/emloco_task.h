@@ -540,6 +540,55 @@ int emloco_getup_amp_default(const EmlocoTaskBufs *bufs, const int32_t *dev_env_
  * counter in between.)  NULL structure, n_env < 1, a missing buffer: -1, nothing is written. */
 int emloco_getup_flags(const EmlocoGetupBufs *getup, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * The crowd-aware terrain sensor (pacer_group_cnn.yaml: divide_group, num_env_group, velocity_map, sensor_res, sensor_extent;
+ * humanoid_pedestrain_terrain.py:400-452,455-492,650-702,761-815,1212-1297, humanoid.py:221-226).  Env e belongs to group
+ * e / group_size.  With `stamps` every env marks the map cells under its 10 x 20 root points (root_x x root_y, meshgrid 'ij', rotated
+ * by the root's heading, world_points_to_map) in the owner map of its group; a marked cell reads int16(height + stamp_units).  The
+ * res x res probes (probe_xy x probe_xy, 'ij', rotated by the heading of body head_body about its position) read
+ *   channel 0      clip(centre_mean - vscale * min(cell(px, py), cell(px + 1, py + 1)), -3, 3) * 5, centre_mean as EMLOCO_POST_OBS has it
+ *   channels 1, 2  (channels == 3) x, y of quat_rotate(inverse root heading, v_cell - v_own), clipped and scaled the same way; v_cell is
+ *                  the root linear velocity of the member that marked (px, py), zero for an unmarked cell and without stamps
+ * into obs[env][n_copy + (i * res + j) * channels + c]; flip_obs takes the same values at j' = res - 1 - j (no sign changes: the
+ * reference's :471 discards its result).  The first n_copy columns of both rows are copied from src_obs / src_flip_obs (rows of
+ * src_width floats; n_copy 0: nothing is copied, the two may be NULL).
+ * Two members on one cell: the one with the highest member_in_group * 200 + point owns it (the reference's duplicate-index
+ * assignment on one thread).  An owner word is (tag << tag_shift) | (that index + 1), written with atomicMax; only words whose tag
+ * equals `tag` count, so the map is never cleared between calls as long as the caller raises `tag` by one per call (>= 1; it clears
+ * the map before it starts over).  The root is body 0 of rb_state.  A non-finite root lands on cell (0, 0). */
+#define EMLOCO_CROWD_ROOT_X 10
+#define EMLOCO_CROWD_ROOT_Y 20
+#define EMLOCO_CROWD_MAX_RES 64
+typedef struct EmlocoCrowdBufs {
+    int32_t n_env, group_size;      /* n_env a multiple of group_size (no groups: group_size = n_env) */
+    int32_t hf_rows, hf_cols;       /* >= 2 each */
+    int32_t head_body;
+    int32_t res, channels;          /* 1 .. EMLOCO_CROWD_MAX_RES; 1 or 3 */
+    int32_t stamps;                 /* 0 | 1 */
+    int32_t stamp_units;            /* int16(1.7 / vertical_scale), the division in double precision */
+    int32_t src_width, dst_width;   /* floats per row of src_obs / obs; dst_width >= n_copy + channels * res * res */
+    int32_t n_copy;                 /* <= src_width */
+    int32_t tag_shift;              /* group_size * 200 < 2^tag_shift <= 2^30, 1 <= tag < 2^(32 - tag_shift) */
+    uint32_t tag;
+    float hscale, vscale;
+    const float *rb_state;          /* [E][24][13] */
+    const int16_t *heightfield;     /* [hf_rows][hf_cols] */
+    const float *probe_xy;          /* [res] float32(np.linspace(-extent, extent, res)) */
+    const float *root_x;            /* [10] float32(np.linspace(-0.25, 0.25, 10)); stamps only */
+    const float *root_y;            /* [20] float32(np.linspace(-0.5, 0.5, 20)); stamps only */
+    uint32_t *owner;                /* [n_env / group_size][hf_rows * hf_cols]; stamps only */
+    const float *src_obs;           /* [E][src_width] */
+    const float *src_flip_obs;      /* [E][src_width] */
+    float *obs;                     /* [E][dst_width] */
+    float *flip_obs;                /* [E][dst_width] */
+} EmlocoCrowdBufs;
+
+/* Two launches on the one stream: the stamps of ALL n_env members (with `stamps`), then the rows of every env (dev_env_ids == NULL)
+ * or of the n listed envs (entries of -1 are skipped).  A NULL structure or required pointer, n_env not a positive multiple of
+ * group_size, res outside 1 .. 64, channels not 1 or 3, a map smaller than 2 x 2, a row too narrow, a tag or tag_shift outside the
+ * ranges above, n < 0: -1 with the argument named in emloco_last_error(), nothing is written. */
+int emloco_task_crowd_sensor(const EmlocoCrowdBufs *bufs, const int32_t *dev_env_ids, int n, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
