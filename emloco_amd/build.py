@@ -33,10 +33,11 @@ UNITS = [
     ("getup_capi.hip", ["-ffp-contract=off"]),           # the get-up task's resets: the task unit's reset device functions, same arithmetic
     ("recorder_capi.hip", ["-ffp-contract=off"]),        # the flight recorder: copies, and the cause test's squared speeds in the stated fp32 order
     ("crowd_capi.hip", ["-ffp-contract=off"]),           # the crowd-aware terrain sensor: the task unit's probe arithmetic, same bytes
+    ("cnn_capi.hip", ["-ffp-contract=off"]),             # the crowd policy's convolution trunk: explicit fmaf in one fixed order, as its CPU emulation
 ]
 # EMLOCO_HIPCC_EXTRA="-DFOO=1 ..." appends flags to every unit, EMLOCO_HIPCC_EXTRA_SIM / _TASK / _PREDICTOR to one (A/B experiments)
 EXTRA = os.environ.get("EMLOCO_HIPCC_EXTRA", "").split()
-UNIT_EXTRA = {u: os.environ.get("EMLOCO_HIPCC_EXTRA_" + u.split("_")[0].upper(), "").split() for u in ("sim_capi.hip", "task_capi.hip", "predictor_capi.hip", "attention_capi.hip", "ffn_capi.hip", "ppo_capi.hip", "eval_capi.hip", "motion_capi.hip", "getup_capi.hip", "recorder_capi.hip", "crowd_capi.hip")}
+UNIT_EXTRA = {u: os.environ.get("EMLOCO_HIPCC_EXTRA_" + u.split("_")[0].upper(), "").split() for u in ("sim_capi.hip", "task_capi.hip", "predictor_capi.hip", "attention_capi.hip", "ffn_capi.hip", "ppo_capi.hip", "eval_capi.hip", "motion_capi.hip", "getup_capi.hip", "recorder_capi.hip", "crowd_capi.hip", "cnn_capi.hip")}
 COMMON = EXTRA + ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
           "-Wno-unused-variable", "-Wno-unused-but-set-variable"]
 

@@ -1,0 +1,30 @@
+// cnn_capi.hip -- C ABI (include/emloco_predictor.h) over the crowd policy's convolution trunk.
+#include <hip/hip_runtime.h>
+#include "cnn_kernels.hip"
+#include "capi_error.h"
+
+using emloco::capi_fail;
+
+namespace {
+constexpr int kCnnMaxGrid = 4096;
+}  // namespace
+
+extern "C" {
+
+int emloco_cnn_trunk(int rows, int res, int channels, int layers, int f0, int f1, int f2, int f3, const float *x, int ldx,
+                     const float *mean, const float *var, float eps, float clip, int normalize, const float *params, float *out, int ldo,
+                     int out_off, void *stream) {
+    emloco::CnnTrunk a;
+    a.rows = rows, a.res = res, a.channels = channels, a.layers = layers;
+    a.filters[0] = f0, a.filters[1] = f1, a.filters[2] = f2, a.filters[3] = f3;
+    a.ldx = ldx, a.ldo = ldo, a.out_off = out_off, a.normalize = normalize ? 1 : 0;
+    a.eps = eps, a.clip = clip;
+    a.x = x, a.mean = mean, a.var = var, a.params = params, a.out = out;
+    if (const char *why = emloco::cnn_refusal(a)) return capi_fail(EMLOCO_E_ARG, "emloco_cnn_trunk", why);
+    hipLaunchKernelGGL(emloco::cnn_trunk_kernel, dim3((unsigned)(rows < kCnnMaxGrid ? rows : kCnnMaxGrid)), dim3(emloco::kCnnThreads), 0,
+                       (hipStream_t)stream, a, x, mean, var, params, out);
+    EMLOCO_HIPCHK(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"

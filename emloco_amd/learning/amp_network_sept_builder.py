@@ -95,7 +95,7 @@ class AMPSeptBuilder:
             self.load(params)
             actions_num = kwargs["actions_num"]
             self.value_size = kwargs.get("value_size", 1)
-            in_size = self.self_obs_size + self._task_units[-1]          # amp_network_sept_builder.py:35
+            in_size = self._mlp_input_size()
             out_size = self.units[-1] if len(self.units) else in_size
             self.actor_cnn = nn.Sequential()
             self.critic_cnn = nn.Sequential()
@@ -142,6 +142,9 @@ class AMPSeptBuilder:
             self._task_units = params["task_mlp"]["units"]
             self._task_activation = params["task_mlp"]["activation"]
             self._task_initializer = params["task_mlp"]["initializer"]
+
+        def _mlp_input_size(self):
+            return self.self_obs_size + self._task_units[-1]             # amp_network_sept_builder.py:35
 
         def is_separate_critic(self):
             return False

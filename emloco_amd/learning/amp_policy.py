@@ -15,10 +15,22 @@ import yaml
 
 from ..utils.running_mean_std import RunningMeanStd
 from .amp_network_sept_builder import AMPSeptBuilder
-from .policy_runner import FrozenDisc, FrozenPolicy
+from .amp_network_sept_cnn_builder import AMPSeptCNNBuilder
+from .policy_runner import CnnFrozenPolicy, FrozenDisc, FrozenPolicy
 
 DEFAULT_CFG = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "data", "cfg", "train", "rlg",
                            "amp_humanoid_smpl_sept_task.yaml")
+CNN_CFG = os.path.join(os.path.dirname(DEFAULT_CFG), "amp_humanoid_smpl_cnn_task.yaml")
+# params.network.name -> (network builder, frozen runner).  `amp_sept_value` is the name the shipped sept config carries (the reference's
+# registration of the same builder for its value agent)
+NETWORKS = {"amp_sept": (AMPSeptBuilder, FrozenPolicy), "amp_sept_value": (AMPSeptBuilder, FrozenPolicy),
+            "amp_sept_cnn": (AMPSeptCNNBuilder, CnnFrozenPolicy)}
+
+
+def network_classes(name):
+    if name not in NETWORKS:
+        raise NotImplementedError(f"network '{name}' is not built (params.network.name: one of {', '.join(NETWORKS)})")
+    return NETWORKS[name]
 
 
 class AMPPolicyBundle:
@@ -35,7 +47,8 @@ class AMPPolicyBundle:
         amp_size = task.get_num_amp_obs()
         self.running_mean_std = RunningMeanStd((obs_size,)).to(self.device).eval()
         self.amp_input_mean_std = RunningMeanStd((amp_size,)).to(self.device).eval()
-        builder = AMPSeptBuilder()
+        builder_cls, runner_cls = network_classes(params["network"].get("name", "amp_sept"))
+        builder = builder_cls()
         builder.load(params["network"])
         self.a2c_network = builder.build(
             "amp", actions_num=task.num_actions, input_shape=(obs_size,), num_seqs=1, value_size=1, amp_input_shape=(amp_size,),
@@ -49,8 +62,8 @@ class AMPPolicyBundle:
                 self.running_mean_std.load_state_dict(ck["running_mean_std"])
             if "amp_input_mean_std" in ck:
                 self.amp_input_mean_std.load_state_dict(ck["amp_input_mean_std"])
-        self.frozen = FrozenPolicy(self.a2c_network, self.running_mean_std, self.num_envs, self.device,
-                                   clip_actions=float(self.config.get("clip_actions", 1.0)))
+        self.frozen = runner_cls(self.a2c_network, self.running_mean_std, self.num_envs, self.device,
+                                 clip_actions=float(self.config.get("clip_actions", 1.0)))
         self.deterministic = deterministic
         self.disc_reward_scale = float(self.config.get("disc_reward_scale", 2.0))
         self.frozen_disc = FrozenDisc(self.a2c_network, self.amp_input_mean_std, self.num_envs, self.device,

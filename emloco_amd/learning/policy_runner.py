@@ -117,6 +117,97 @@ class FrozenPolicy:
         return torch.addcmul(mu, self.exp_sigma, noise).clamp_(-self.clip, self.clip)       # three launches on the chain, not five
 
 
+class CnnFrozenPolicy(FrozenPolicy):
+    """The frozen forward of the CNN policy (amp_network_sept_cnn_builder.py: AMPSeptCNNBuilder.Network.eval_actor behind
+    `running_mean_std(obs)`) for the crowd sensor's rows [self 368 | path 30 | map res x res x C]; `act`, `_linear` and
+    `from_checkpoint` are FrozenPolicy's.  Launches per step, on the caller's stream, no torch.cat and no intermediate copy:
+      1. `emloco_obs_normalize` over the first self + path columns (ldx = the full row): self -> columns [0, 368) of the actor
+         operand, path -> its columns [368 + 256, ...) (out1 is a view at that column, ld1 the operand's width);
+      2. `emloco_cnn_trunk` on the raw map columns, normalising as it loads: at res 32 the features land in the operand's columns
+         [368, 624) directly, otherwise in the (E, features) operand of `_cnn_mlp`;
+      3. where res != 32, `_cnn_mlp`: two GEMMs with the bias / ReLU epilogue, the second into columns [368, 624) (ldc, c_off);
+      4. actor MLP and `mu` head as FrozenPolicy.
+    The actor operand is self + 256 + path = 654 wide with 15 path samples: padded to a multiple of 4 with zero columns, and
+    `actor_mlp.0.weight` with zero K columns, so every GEMM keeps its 16-byte path."""
+
+    def __init__(self, network, mean_std, num_envs, device, clip_actions=1.0):
+        from .amp_network_sept_cnn_builder import pack_trunk
+        self.E, self.device, self.clip = num_envs, torch.device(device), float(clip_actions)
+        self.self_size, self.task_size = network.self_obs_size, network.task_obs_size
+        self.traj = int(network.task_obs_size_detail["traj"])
+        self.res, self.channels, self.filters, self.features = network.res, network.channels, list(network._filters), network.features
+        self.map_col = self.self_size + self.traj
+        assert self.task_size == self.traj + self.channels * self.res * self.res
+        sd = {k: v.detach().to(self.device, torch.float32).clone().contiguous() for k, v in network.state_dict().items()}      # private copies: frozen for good (the piece images below are cut from them once)
+        f = dict(dtype=torch.float32, device=self.device)
+
+        def layers(prefix):
+            idx = sorted({int(k.split(".")[1]) for k in sd if k.startswith(prefix + ".") and k.endswith(".weight")})
+            return [(sd[f"{prefix}.{i}.weight"], sd[f"{prefix}.{i}.bias"]) for i in idx]
+
+        def pad_k(w):
+            k = (w.shape[1] + _PAD - 1) // _PAD * _PAD
+            wp = torch.zeros((w.shape[0], k), **f)
+            wp[:, :w.shape[1]] = w
+            return wp
+
+        self.trunk_params = pack_trunk(network._task_actor_cnn).to(self.device)          # (a copy: torch.cat)
+        self.cnn_layers, self.actor_layers = layers("_cnn_mlp"), layers("actor_mlp")
+        self.mu_w, self.mu_b, self.sigma = sd["mu.weight"], sd["mu.bias"], sd["sigma"]
+        self.trunk_out = self.cnn_layers[-1][0].shape[0] if self.cnn_layers else self.features
+        self.actor_in_size = self.self_size + self.trunk_out + self.traj
+        assert self.actor_layers[0][0].shape[1] == self.actor_in_size and self.self_size % _PAD == 0 and self.trunk_out % _PAD == 0
+        self.actor_layers[0] = (pad_k(self.actor_layers[0][0]), self.actor_layers[0][1])
+        self.actor_k = self.actor_layers[0][0].shape[1]
+        if self.cnn_layers:
+            self.cnn_layers[0] = (pad_k(self.cnn_layers[0][0]), self.cnn_layers[0][1])
+        self.mean32 = mean_std.running_mean.to(self.device).float().contiguous()
+        self.var32 = mean_std.running_var.to(self.device).float().contiguous()
+        self.map_mean, self.map_var = self.mean32[self.map_col:], self.var32[self.map_col:]
+        self.eps = float(mean_std.epsilon)
+        self.exp_sigma = torch.exp(self.sigma)
+        E = num_envs
+        self.actor_in = torch.zeros((E, self.actor_k), **f)           # pad columns stay zero
+        self.path_in = self.actor_in[:, self.self_size + self.trunk_out:]
+        self.cnn_feat = torch.zeros((E, self.cnn_layers[0][0].shape[1]), **f) if self.cnn_layers else None        # pad columns stay zero
+        self.cnn_h = [torch.empty((E, w.shape[0]), **f) for w, _ in self.cnn_layers[:-1]]
+        self.actor_h = [torch.empty((E, w.shape[0]), **f) for w, _ in self.actor_layers]
+        self.mu = torch.empty((E, self.mu_w.shape[0]), **f)
+        side, cin, self.trunk_macs = self.res, self.channels, 0
+        for nf in self.filters:
+            side //= 2
+            self.trunk_macs += side * side * nf * cin * 16
+            cin = nf
+        self.flops_per_env = 2 * (self.trunk_macs + sum(w.shape[0] * w.shape[1] for w, _ in self.cnn_layers + self.actor_layers)
+                                  + self.mu_w.numel())
+
+    def trunk(self, obs):
+        """launch 2 alone (tools/cnn_policy_overhead.py times it)"""
+        from .amp_network_sept_cnn_builder import cnn_trunk
+        out, off = (self.cnn_feat, 0) if self.cnn_layers else (self.actor_in, self.self_size)
+        cnn_trunk(obs, self.map_col, self.res, self.channels, self.filters, self.trunk_params, out, off, mean=self.map_mean,
+                  var=self.map_var, eps=self.eps, clip=5.0)
+
+    def act_mean(self, obs):
+        """obs (E, self + path + map) fp32 on the device -> mu (E, actions); the returned tensor is reused by the next call."""
+        assert obs.shape == (self.E, self.self_size + self.task_size) and obs.dtype == torch.float32 and obs.stride(1) == 1
+        obs_normalize(obs[:, :self.map_col], self.mean32, self.var32, self.eps, 5.0, split=self.self_size, out0=self.actor_in, out1=self.path_in)
+        self.trunk(obs)
+        x = self.cnn_feat
+        for i, (w, b) in enumerate(self.cnn_layers):
+            if i == len(self.cnn_layers) - 1:           # last layer lands in the actor input, columns [self_size, self_size + 256)
+                self._linear(x, x.shape[1], w, b, self.actor_in, ldc=self.actor_k, c_off=self.self_size)
+            else:
+                self._linear(x, x.shape[1], w, b, self.cnn_h[i])
+                x = self.cnn_h[i]
+        x, k = self.actor_in, self.actor_k
+        for i, (w, b) in enumerate(self.actor_layers):
+            self._linear(x, k, w, b, self.actor_h[i])
+            x, k = self.actor_h[i], w.shape[0]
+        self._linear(x, k, self.mu_w, self.mu_b, self.mu, relu=False)
+        return self.mu
+
+
 class FrozenDisc:
     """The AMP discriminator's style reward for the LocoVal rollout (config 2), as the frozen policy above: what the reference
     computes per step with `_amp_input_mean_std(amp_obs)`, `a2c_network.eval_disc` (amp_network_builder.py:81-84: MLP 3090 -> 1024

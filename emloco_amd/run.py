@@ -410,6 +410,42 @@ class PolicyTrainee:
         return None
 
 
+def load_policy_cfg(args):
+    """The policy's training configuration (network, algorithm settings): the file of --cfg_train, the shipped sept configuration
+    without one."""
+    import yaml
+    from .learning.amp_policy import DEFAULT_CFG
+    path = args.cfg_train or DEFAULT_CFG
+    try:
+        with open(path) as f:
+            return yaml.safe_load(f)
+    except OSError as e:
+        raise SystemExit(f"run.py --cfg_train: cannot read {path}: {e}")
+
+
+def crowd_policy_refusal(env_cfg, network, use_policy, train_policy, test):
+    """Why this combination of environment configuration, policy network (`params.network.name` of the training configuration) and
+    flags cannot run, or None.  No device is touched."""
+    from .crowd_sensor import is_crowd_config
+    if not (use_policy or train_policy or test):
+        return None
+    from .learning.amp_policy import NETWORKS
+    if network not in NETWORKS:
+        return f"run.py --cfg_train: network '{network}' is not built (params.network.name: one of {', '.join(NETWORKS)})"
+    crowd = is_crowd_config(env_cfg)
+    if train_policy and (crowd or network == "amp_sept_cnn"):
+        return ("run.py --train_policy: the CNN policy of the crowd sensor (amp_network_sept_cnn_builder.py, network amp_sept_cnn) runs as "
+                "inference only -- the CNN trunk's backward is not built, so it cannot be trained here.  A frozen policy "
+                "(--policy_checkpoint / --policy_random_init) and --test take --cfg_train "
+                "emloco_amd/data/cfg/train/rlg/amp_humanoid_smpl_cnn_task.yaml")
+    if crowd and network != "amp_sept_cnn":
+        return ("run.py: the configuration asks for the crowd sensor (divide_group / velocity_map / sensor_res / sensor_extent), whose "
+                f"observations the policy network '{network}' cannot read: they need the CNN trunk (amp_network_sept_cnn_builder.py).  Pass "
+                "--cfg_train emloco_amd/data/cfg/train/rlg/amp_humanoid_smpl_cnn_task.yaml (network amp_sept_cnn) with --policy_checkpoint, "
+                "--policy_random_init or --test.  Without a policy flag the run is the LocoVal loop under noise actions")
+    return None
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     train_opt = train_options(argv)                      # (--steps leaves argv; a bad combination stops the run before any device call)
@@ -461,12 +497,11 @@ def main(argv=None):
         args.num_envs = shard_range(int(args.num_envs), rank, world)[1]
     cfg, cfg_train, _ = load_cfg(args)
     fill_flags(args)
-    from .crowd_sensor import is_crowd_config
-    if is_crowd_config(cfg["env"]) and (use_policy or train_policy or args.test):
-        raise SystemExit("run.py: the configuration asks for the crowd sensor (divide_group / velocity_map / sensor_res / sensor_extent), whose "
-                         "observations the policy network here cannot read: the reference's CNN trunk (amp_network_sept_cnn_builder.py) is "
-                         "not built.  Without --policy_checkpoint, --policy_random_init, --train_policy and --test the run is the LocoVal "
-                         "loop under noise actions")
+    policy_cfg = load_policy_cfg(args) if (use_policy or train_policy or args.test) else None
+    network = policy_cfg["params"]["network"].get("name", "amp_sept") if policy_cfg else None
+    refusal = crowd_policy_refusal(cfg["env"], network, use_policy, train_policy, args.test)
+    if refusal:
+        raise SystemExit(refusal)
     if flags.pred_path:                                  # a missing table stops the run here, by name, before the simulator is built
         from .env.util.traj_generator import PRED_TRAJ_FILE
         import os
@@ -478,13 +513,12 @@ def main(argv=None):
     say = print if rank == 0 else (lambda *a, **k: None)
     if args.test:
         capture = None if cap_opt is None else make_capture(env.env.task, cap_opt, rank, world)
-        _run_test(args, env, policy_ckpt, games_num, max_steps, eval_out, eval_records, rank, world, say, compare, eval_tracks, capture)
+        _run_test(args, env, policy_ckpt, games_num, max_steps, eval_out, eval_records, rank, world, say, compare, eval_tracks, capture,
+                  policy_cfg)
         return
     if train_policy:
-        import yaml
         from .learning.amp_agent import AMPAgent
-        from .learning.amp_policy import DEFAULT_CFG
-        agent = AMPAgent(env, yaml.safe_load(open(DEFAULT_CFG)))
+        agent = AMPAgent(env, policy_cfg)
         if policy_ckpt:
             agent.restore(policy_ckpt)
         capture = None if cap_opt is None else make_capture(env.env.task, cap_opt, rank, world)
@@ -499,7 +533,7 @@ def main(argv=None):
     kw = {}
     if use_policy:
         from .learning.amp_policy import AMPPolicyBundle
-        bundle = AMPPolicyBundle(env.env.task, checkpoint=policy_ckpt)
+        bundle = AMPPolicyBundle(env.env.task, cfg_train=policy_cfg, checkpoint=policy_ckpt)
         kw = dict(policy=bundle.policy, disc_reward=bundle.disc_reward,
                   inversion_penalty_scale=float(bundle.config.get("inversion_penalty_scale", 0.3)))
     agent = LocoValRollout(env, use_pose=args.input_init_pose, use_vel=args.input_init_vel, **kw)
@@ -537,14 +571,15 @@ def _gather_track_columns(ev, world):
 
 
 def _run_test(args, env, policy_ckpt, games_num, max_steps, eval_out, eval_records, rank, world, say, compare=(), eval_tracks=False,
-              capture=None):
-    """--test: LocoValEvaluator with the frozen policy (deterministic actions) and the LocoVal network of --valuenet_path."""
+              capture=None, cfg_train=None):
+    """--test: LocoValEvaluator with the frozen policy (deterministic actions) and the LocoVal network of --valuenet_path.
+    cfg_train: the policy's training configuration (load_policy_cfg)."""
     import json
-    import yaml
-    from .learning.amp_policy import DEFAULT_CFG, AMPPolicyBundle
+    from .learning.amp_policy import AMPPolicyBundle
     from .learning.locoval_eval import LocoValEvaluator, TrackRefusal
     from .learning.value_pose_net import ValuePoseNet
-    cfg_train = yaml.safe_load(open(DEFAULT_CFG))
+    if cfg_train is None:
+        cfg_train = load_policy_cfg(args)
     config = cfg_train["params"]["config"]
     player = config.get("player", {})
     task = env.env.task

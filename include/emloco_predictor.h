@@ -230,6 +230,21 @@ int emloco_disc_reward(int n, const float *logits, float scale, float *reward, v
 int emloco_obs_normalize(int rows, int cols, const float *x, int ldx, const float *mean, const float *var, float eps,
                          float clip, int split, float *out0, int ld0, float *out1, int ld1, void *stream);
 
+/* Convolution trunk of the crowd sensor's policy: `_task_actor_cnn` of AMPSeptCNNBuilder.Network.eval_task
+ * (pacer/pacer/learning/amp_network_sept_cnn_builder.py:49-67; the layers are network_builder.py:125-148 `_build_conv`: Conv2d +
+ * activation per entry of `convs`), fused with the map columns' share of RunningMeanStd.forward (running_mean_std.py:81-83).
+ * One launch: x points at the first map column of the observation rows [rows][ldx], read as (res, res, channels) channel last;
+ * with normalize != 0 every value becomes clamp((x - mean) / sqrt(var + eps), -clip, clip) as it is loaded (mean / var: the float32
+ * casts of the running buffers, offset to the map's first column, [channels * res * res]; with normalize == 0 they are not read).
+ * Then `layers` (1..4) times Conv2d(kernel 4, stride 2, padding 1) + ReLU with f0..f3 filters (1..16 each; those past `layers`
+ * are ignored), fp32 fmaf in one fixed order (cnn_kernels.hip), no MFMA.  params: for every layer its weights [F][Cin][4][4] then
+ * its bias [F], back to back.  The features, flattened (channel, row, column), land in out[row * ldo + out_off ...]; nothing else is
+ * written, neither the normalised map nor any activation.  res: a multiple of 8 up to 64 that halves cleanly `layers` times;
+ * channels 1 or 3.  Any rows >= 1: the launch covers at most 4096 rows at a time and strides over the rest. */
+int emloco_cnn_trunk(int rows, int res, int channels, int layers, int f0, int f1, int f2, int f3, const float *x, int ldx,
+                     const float *mean, const float *var, float eps, float clip, int normalize, const float *params, float *out, int ldo,
+                     int out_off, void *stream);
+
 /* Statistics update of the same normaliser (RunningMeanStd.forward in training mode, running_mean_std.py:85-95, called once per
  * rollout step by the PPO / AMP learner on the observation and AMP-observation batches): merges the per-column mean and unbiased
  * variance of x [rows][ldx] into the float64 running moments mean / var [cols] with the parallel-variance rule (count_in [1] rows
