@@ -175,6 +175,35 @@ class CrowdBufs(C.Structure):
                 ("obs", C.c_void_p), ("flip_obs", C.c_void_p)]
 
 
+CROWD_CONTACT_WS, CROWD_CONTACT_TOTALS, CROWD_CONTACT_MOMENTS = 16, 13, 13          # EMLOCO_CROWD_CONTACT_*
+(CCT_STEPS, CCT_NONFINITE_STEPS, CCT_CONTACT_STEPS, CCT_CONTACTS, CCT_NEAR_STEPS, CCT_SUM_NEAREST, CCT_SUM_PEN, CCT_MAX_PEN,
+ CCT_MIN_NEAREST, CCT_GAMES, CCT_GAMES_CONTACT, CCT_GAMES_START_CONTACT, CCT_NEIGHBOUR_STEPS) = range(13)       # EMLOCO_CCT_*
+(CCM_GAMES, CCM_GAMES_CONTACT, CCM_GAMES_START_CONTACT, CCM_STEPS, CCM_CONTACT_STEPS, CCM_NEAR_STEPS, CCM_CONTACTS,
+ CCM_NONFINITE_STEPS, CCM_SUM_MAX_PEN, CCM_SUM_MAX_PEN2, CCM_SUM_MIN_NEAREST, CCM_SUM_MEAN_NEAREST, CCM_GAMES_NEIGHBOUR) = range(13)   # EMLOCO_CCM_*
+
+
+class CrowdContactNow(C.Structure):
+    """EmlocoCrowdContactNow (include/emloco_task.h): one env's distances and overlaps at one step."""
+    _fields_ = [("nearest", C.c_float), ("pen", C.c_float), ("nearest_member", C.c_int32), ("pen_member", C.c_int32),
+                ("pen_segs", C.c_int32), ("n_pen", C.c_int32), ("n_near", C.c_int32), ("flags", C.c_int32)]
+
+
+class CrowdContactRecord(C.Structure):
+    """EmlocoCrowdContactRecord (include/emloco_task.h): one finished game of the crowd contact audit."""
+    _fields_ = [("min_nearest", C.c_float), ("mean_nearest", C.c_float), ("max_pen", C.c_float), ("steps", C.c_int32),
+                ("nonfinite_steps", C.c_int32), ("near_steps", C.c_int32), ("contact_steps", C.c_int32), ("contacts", C.c_int32),
+                ("pen_member", C.c_int32), ("pen_segs", C.c_int32), ("pen_step", C.c_int32), ("first_contact_step", C.c_int32)]
+
+
+class CrowdContacts(C.Structure):
+    """EmlocoCrowdContacts (include/emloco_task.h): inputs, workspaces and game state of the crowd contact audit."""
+    _fields_ = [("n_env", C.c_int32), ("group_size", C.c_int32), ("n_seg", C.c_int32), ("games_per_env", C.c_int32),
+                ("near_dist", C.c_float), ("_pad", C.c_int32),
+                ("rb_state", C.c_void_p), ("cap_a", C.c_void_p), ("cap_b", C.c_void_p), ("cap_r", C.c_void_p), ("seg_body", C.c_void_p),
+                ("caps_ws", C.c_void_p), ("roots_ws", C.c_void_p), ("done8", C.c_void_p), ("done64", C.c_void_p), ("slot", C.c_void_p),
+                ("game_ws", C.c_void_p), ("records", C.c_void_p), ("totals", C.c_void_p)]
+
+
 class LocoValStep(C.Structure):
     """EmlocoLocoValStep (include/emloco_predictor.h)."""
     _fields_ = [("n_env", C.c_int32), ("step_to_pred", C.c_int32), ("gamma", C.c_float), ("inversion_penalty", C.c_float),

@@ -32,7 +32,8 @@ UNITS = [
     ("motion_capi.hip", ["-ffp-contract=off"]),          # the motion library's clip build: fixed fp32 order, as its CPU emulation
     ("getup_capi.hip", ["-ffp-contract=off"]),           # the get-up task's resets: the task unit's reset device functions, same arithmetic
     ("recorder_capi.hip", ["-ffp-contract=off"]),        # the flight recorder: copies, and the cause test's squared speeds in the stated fp32 order
-    ("crowd_capi.hip", ["-ffp-contract=off"]),           # the crowd-aware terrain sensor: the task unit's probe arithmetic, same bytes
+    ("crowd_capi.hip", ["-ffp-contract=off"]),           # the crowd-aware terrain sensor: the task unit's probe arithmetic, same bytes;
+                                                         # + crowd_contact_kernels.hip (the crowd contact audit): plain fp32 in the header's order
     ("cnn_capi.hip", ["-ffp-contract=off"]),             # the crowd policy's convolution trunk: explicit fmaf in one fixed order, as its CPU emulation
 ]
 # EMLOCO_HIPCC_EXTRA="-DFOO=1 ..." appends flags to every unit, EMLOCO_HIPCC_EXTRA_SIM / _TASK / _PREDICTOR to one (A/B experiments)

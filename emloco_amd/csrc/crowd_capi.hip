@@ -1,6 +1,7 @@
-// crowd_capi.hip -- C ABI (include/emloco_task.h) over the crowd-aware terrain sensor's kernels.
+// crowd_capi.hip -- C ABI (include/emloco_task.h) over the crowd-aware terrain sensor's kernels and the crowd contact audit's.
 #include <hip/hip_runtime.h>
 #include "crowd_kernels.hip"
+#include "crowd_contact_kernels.hip"
 #include "capi_error.h"
 
 using emloco::capi_fail;
@@ -23,6 +24,46 @@ int emloco_task_crowd_sensor(const EmlocoCrowdBufs *bufs, const int32_t *dev_env
         EMLOCO_HIPCHK(hipGetLastError());
     }
     hipLaunchKernelGGL(emloco::crowd_gather_kernel, dim3(crowd_grid(rows)), dim3(emloco::kCrowdThreads), 0, st, *bufs, dev_env_ids, rows);
+    EMLOCO_HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int emloco_crowd_contacts(const EmlocoCrowdContacts *c, EmlocoCrowdContactNow *now, void *stream) {
+    const char *who = "emloco_crowd_contacts";
+    if (const char *why = emloco::crowd_contacts_refusal(c, now, false)) return capi_fail(EMLOCO_E_ARG, who, why);
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned grid = crowd_grid((c->n_env + emloco::kContactWaves - 1) / emloco::kContactWaves);
+    hipLaunchKernelGGL(emloco::crowd_contact_prep_kernel, dim3(grid), dim3(emloco::kContactThreads), 0, st, *c);
+    EMLOCO_HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(emloco::crowd_contact_kernel, dim3(grid), dim3(emloco::kContactThreads), 0, st, *c, now);
+    EMLOCO_HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int emloco_crowd_contacts_accumulate(const EmlocoCrowdContacts *c, const EmlocoCrowdContactNow *now, void *stream) {
+    const char *who = "emloco_crowd_contacts_accumulate";
+    if (const char *why = emloco::crowd_contacts_refusal(c, now, true)) return capi_fail(EMLOCO_E_ARG, who, why);
+    hipLaunchKernelGGL(emloco::crowd_contact_accumulate_kernel, dim3((unsigned)((c->n_env + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *c, now);
+    EMLOCO_HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int emloco_crowd_contacts_reduce(int n_env, int games_per_env, const EmlocoCrowdContactRecord *records, const int32_t *games,
+                                 double *moments, void *stream) {
+    const char *who = "emloco_crowd_contacts_reduce";
+    if (const char *why = emloco::crowd_contacts_reduce_refusal(n_env, games_per_env, records, games, moments)) return capi_fail(EMLOCO_E_ARG, who, why);
+    hipLaunchKernelGGL(emloco::crowd_contact_reduce_kernel, dim3(1), dim3(emloco::kContactReduceThreads), 0, (hipStream_t)stream, n_env,
+                       games_per_env, records, games, moments);
+    EMLOCO_HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int emloco_crowd_contacts_epoch_reduce(int n_env, double *totals, double *epoch, void *stream) {
+    const char *who = "emloco_crowd_contacts_epoch_reduce";
+    if (n_env < 1) return capi_fail(EMLOCO_E_ARG, who, "n_env < 1");
+    if (!totals) return capi_fail(EMLOCO_E_ARG, who, "null totals");
+    if (!epoch) return capi_fail(EMLOCO_E_ARG, who, "null epoch");
+    hipLaunchKernelGGL(emloco::crowd_contact_epoch_kernel, dim3(1), dim3(emloco::kContactReduceThreads), 0, (hipStream_t)stream, n_env, totals, epoch);
     EMLOCO_HIPCHK(hipGetLastError());
     return 0;
 }

@@ -29,6 +29,11 @@ walked, and the walked and target xy at those frames in the origin-relative fram
 `real_traj` / `ideal_traj` for its video (amp_value_players.py:105,126,239) and computes no number from them: these metrics are this
 project's.  Their moments are reduced and all-reduced on their own (`track_moments_from_records` / `tracking_from_moments`); the report
 gains a `tracking` block, nothing else in it changes, and without `track` there is no launch, no buffer and no block.
+
+Crowd contacts (`crowd=True`; `run.py --eval_crowd`): on a configuration with groups the crowd contact audit (emloco_amd/crowd_contacts.py)
+rides in the same place -- its geometry and bookkeeping launches once per step between the first and the last of the three, whatever
+the number of networks, on this step's `done` flags and the games' slots.  Members whose quota is met keep walking and keep counting
+as neighbours; they write no record.  The report gains a `crowd` block; without `crowd` there is no launch, no buffer and no block.
 """
 import ctypes as C
 import math
@@ -275,10 +280,13 @@ class LocoValEvaluator:
     max_steps: the step cap of the reference's player (rl_games BasePlayer: 27 000); a run whose games never finish stops there and
       the report states the shortfall.
     track: also record per game how closely the root followed its path (module docstring): `report` gains a `tracking` block,
-      `track_records` / `track_samples` answer per game."""
+      `track_records` / `track_samples` answer per game.
+    crowd: also audit per game how close the env came to the other members of its group (crowd_contacts.CrowdContactAudit, `near_dist`
+      = crowd_near_dist): `report` gains a `crowd` block, `crowd_records` answers per game.  A task without groups or without a
+      capsule table is a CrowdContactRefusal (a ValueError) before anything is allocated."""
 
     def __init__(self, vec_env, policy_bundle, valuenet, games_num, max_steps=27000, poll_every=16, gamma=0.99, disc_reward=None,
-                 track=False):
+                 track=False, crowd=False, crowd_near_dist=1.0):
         from ..predictor import ops
         from .value_pose_net import ValuePoseNet
         self.vec_env = vec_env
@@ -290,6 +298,12 @@ class LocoValEvaluator:
         if self.track:                            # refused by name before anything is allocated
             self.track_stride = track_stride(task._traj_sample_timestep, task.dt, task.max_episode_length)
             self.fail_dist = float(getattr(task, "_fail_dist", FAIL_DIST))
+        self.crowd = None
+        if crowd:                                 # refused by name before anything is allocated
+            from ..crowd_contacts import CrowdContactRefusal
+            if not getattr(task, "_divide_group", False):
+                raise CrowdContactRefusal("LocoValEvaluator(crowd=True): the task has divide_group: False -- without groups there is "
+                                          "nobody to measure against")
         self.device = torch.device(task.device)
         self.multi = isinstance(valuenet, (list, tuple))
         nets = list(valuenet) if self.multi else [valuenet]
@@ -351,6 +365,9 @@ class LocoValEvaluator:
             self._track_records = torch.zeros(E * G * TRACK_WORDS, dtype=torch.int32, device=dev)
             self._track_samples = f(E, G, ops.TRACK_SAMPLES, 4)
             self._track_moments = torch.zeros(ops.TRACK_MOMENTS, dtype=torch.float64, device=dev)
+        if crowd:
+            from ..crowd_contacts import CrowdContactAudit
+            self.crowd = CrowdContactAudit(task, near_dist=crowd_near_dist, games_per_env=G)
         self.steps_run = 0
         self.started = False
         # --pred_path: the host reset knows which row of the predicted-path table every game walks; logged from the first reset on
@@ -422,6 +439,8 @@ class LocoValEvaluator:
         if self.track:                              # once per step, whatever the number of networks: nothing tracked depends on them
             ops._chk(lib.emloco_locoval_eval_track(C.byref(self._s), C.byref(self._track_inputs()), _p(self._track_records),
                                                    _p(self._track_samples), st), "emloco_locoval_eval_track")
+        if self.crowd is not None:                  # likewise: this step's done flags, the slots of the games in progress
+            self.crowd.step(done=self._b["done"], slot=self._b["games"])
         if self.multi:
             self._check_nets()
             ops._chk(lib.emloco_locoval_eval_fwd_multi(C.byref(self._s), C.byref(self._nets), st), "emloco_locoval_eval_fwd_multi")
@@ -534,6 +553,36 @@ class LocoValEvaluator:
                 say(ln)
         return trk
 
+    def crowd_records(self):
+        """This rank's crowd contact records (crowd_contacts.RECORD_DTYPE columns plus `env` and `game`), in the order of `records`."""
+        return self.crowd.records()
+
+    def _crowd(self, values, say):
+        """The `crowd` block: the all-reduced moments, and from all ranks' records the deepest penetration and the Pearson r of every
+        network's value against it."""
+        from ..crowd_contacts import crowd_from_moments, crowd_from_records
+        m = self.crowd.moments()
+        blk = crowd_from_moments(m, self.crowd.near_dist, self.crowd.group_size)
+        rec = self.crowd_records()
+        if D.is_distributed():
+            parts = [None] * D.world_size()
+            torch.distributed.all_gather_object(parts, (values, rec))
+            values = [np.concatenate([p[0][k] for p in parts]) for k in range(len(values))]
+            rec = np.concatenate([p[1] for p in parts])
+        assert blk["games"] == len(rec), "the crowd records and their moments cover the same games"
+        extra = crowd_from_records(values, rec)
+        if not self.multi:
+            extra["corr_value_max_pen"], extra["corr_value_contact"] = extra["corr_value_max_pen"][0], extra["corr_value_contact"][0]
+        blk.update(extra, moments=[float(x) for x in m])
+        if blk["games"] > 0:
+            fmt = lambda c: ", ".join(f"{x:.3f}" for x in (c if self.multi else [c]))
+            blk["lines"] = blk["lines"] + [f"deepest penetration of all games: {blk['max_pen']:.4f}; correlation of value with max_pen: "
+                                           f"{fmt(blk['corr_value_max_pen'])}, with a contact: {fmt(blk['corr_value_contact'])}"]
+        if say is not None:
+            for ln in blk["lines"]:
+                say(ln)
+        return blk
+
     def report(self, say=print):
         """One network: the report dict.  A list of networks: {"networks": [the report of each, as a single run of it gives],
         "paired": paired_from_records of all ranks' records}; the lines of every network are said under a `network k` heading.
@@ -542,6 +591,8 @@ class LocoValEvaluator:
             rep = self._report(self.moments(), say)
             if self.track:
                 rep["tracking"] = self._tracking([self.records()["value"]], say)
+            if self.crowd is not None:
+                rep["crowd"] = self._crowd([self.records()["value"]], say)
             return rep
         reps = []
         for k, m in enumerate(self.moments()):
@@ -558,9 +609,12 @@ class LocoValEvaluator:
         if say is not None:
             for pr in paired["pairs"]:
                 say(f"network {pr['b']} - network {pr['a']}: MSE {pr['d_mse']:+.6f}, Pearson r (total) {pr['d_corr_total']:+.4f}")
+        out = {"networks": reps, "paired": paired}
         if self.track:
-            return {"networks": reps, "paired": paired, "tracking": self._tracking([r["value"] for r in self.records()], say)}
-        return {"networks": reps, "paired": paired}
+            out["tracking"] = self._tracking([r["value"] for r in self.records()], say)
+        if self.crowd is not None:
+            out["crowd"] = self._crowd([r["value"] for r in self.records()], say)
+        return out
 
     def _report(self, m, say):
         rep = report_from_moments(m)

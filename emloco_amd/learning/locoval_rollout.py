@@ -122,6 +122,7 @@ class LocoValRollout:
         # game statistics (learning/episode_stats.py): off unless attach_episode_stats() is called -- no launch, no allocation
         self.episode_stats = None
         self.flight_recorder = None                         # learning/flight_recorder.py: off unless attach_flight_recorder() is called
+        self.crowd_audit = None                             # crowd_contacts.py: off unless attach_crowd_audit() is called
         self._epoch_fit = None
         self.epoch_num = 0
         if self.fused:
@@ -452,6 +453,17 @@ class LocoValRollout:
             self.flight_recorder.unbind()
         self.flight_recorder = None if recorder is None else recorder.bind()
 
+    def attach_crowd_audit(self, audit):
+        """Turn the crowd contact audit on (a `CrowdContactAudit` of this loop's task, built with totals) or off (None).  On: its
+        launches where the statistics launch sits -- the state after the step, no finished env reset yet -- on the step's reset flags;
+        nothing the loop computes changes.  The caller reads it once per epoch (`CrowdContactAudit.end_epoch`).  With `overlap_reset`
+        the reset chain writes env state on a second stream beside the step, and the audit needs every writer of the body state ordered
+        on the caller's stream: refused, the flight recorder's rule."""
+        if audit is not None and getattr(self.task, "overlap_reset", False):
+            raise RuntimeError("LocoValRollout.attach_crowd_audit: the task has overlap_reset on (EMLOCO_OVERLAP_RESET=1) -- the reset chain "
+                               "writes env state on a second stream beside the step, and the audit reads the body state on the caller's")
+        self.crowd_audit = audit
+
     def epoch_report(self):
         """After end_epoch(), with the statistics on: the game report of the epoch and the loop's own numbers of the per-epoch line
         (common_agent.py:205-207,236): `vnet_loss` = the epoch's loss sum / fitted episodes, `vnet_pred` / `combine_rwd` = the means of
@@ -502,6 +514,8 @@ class LocoValRollout:
                 self.episode_stats.step()                         # behind the step's flags, ahead of the next reset_done()
             if self.flight_recorder is not None:
                 self.flight_recorder.check()                      # the same place: the state after the step, no finished env reset yet
+            if self.crowd_audit is not None:
+                self.crowd_audit.step(done=task.reset_buf)        # likewise; done64 = the step's reset flags
             if self._disc_halves is not None and getattr(task, "_returns_in_flags", False):
                 self._deferred_disc_step(infos["amp_obs"])
                 return

@@ -9,7 +9,7 @@ frozen random-init policy, and prints the reference's `fps_step` counter (common
 
     python -m emloco_amd.run --test --num_envs 4096 --policy_checkpoint policy.pth --valuenet_path LocoVal.pth \
         [--games_num N] [--eval_out report.json] [--eval_records games.npz] [--compare_valuenet Other.pth ...]
-        [--pred_path [--pred_traj_file preds.pkl]] [--eval_tracks]
+        [--pred_path [--pred_traj_file preds.pkl]] [--eval_tracks] [--eval_crowd [--crowd_near_dist M]]
 
 is the reference's `pacer/run.py --test --valuenet_path ...` (AMPPlayerContinuousValue.run): the frozen policy plays
 deterministically and LocoVal is scored against the discounted returns of the games (`learning/locoval_eval.py`).  Every `--compare_valuenet` adds a network (its input configuration read off its fc1 width) that is
@@ -153,6 +153,19 @@ def pop_test_options(argv):
         argv.remove("--eval_tracks")
         if "--test" not in argv:
             raise SystemExit("run.py: --eval_tracks records the path tracking of the games of --test")
+    opt["eval_crowd"] = "--eval_crowd" in argv
+    near = _pop_opt(argv, "--crowd_near_dist")
+    if opt["eval_crowd"]:
+        argv.remove("--eval_crowd")
+        if "--test" not in argv:
+            raise SystemExit("run.py: --eval_crowd audits the crowd contacts of the games of --test (training runs take --crowd_audit)")
+    opt["crowd_near_dist_given"] = near is not None      # (main checks it against --crowd_audit, which train_options took out of argv)
+    try:
+        opt["crowd_near_dist"] = 1.0 if near is None else float(near)
+    except ValueError as e:
+        raise SystemExit(f"run.py: --crowd_near_dist: {e}")
+    if not (0.0 < opt["crowd_near_dist"] < float("inf")):
+        raise SystemExit("run.py: --crowd_near_dist must be a finite positive length [m]")
     if opt["compare"] and "--test" not in argv:
         raise SystemExit("run.py: --compare_valuenet adds networks to the evaluation of --test")
     return opt
@@ -211,7 +224,15 @@ def train_options(argv, args=None):
     val = lambda name, default, conv: (conv(_pop_opt(list(argv), name, default)) if args is None else conv(getattr(args, name[2:])))
     opt = dict(steps=steps, experiment=val("--experiment", "", str), network_path=val("--network_path", "output/", str),
                max_iterations=val("--max_iterations", 0, int), save_freq=val("--save_freq", 200, int), resume=flag("--resume"),
-               stats=flag("--stats"))
+               stats=flag("--stats"), crowd_audit="--crowd_audit" in argv)
+    if opt["crowd_audit"]:
+        argv.remove("--crowd_audit")                     # (get_args does not know it)
+        if "--test" in argv:
+            raise SystemExit("run.py: --crowd_audit belongs to training (--stats / --experiment); --test takes --eval_crowd")
+        if not (opt["stats"] or opt["experiment"]):
+            raise SystemExit("run.py: --crowd_audit adds to the epoch statistics: give it with --stats or --experiment NAME")
+        if "--train_policy" in argv:
+            raise SystemExit("run.py: --crowd_audit rides in the LocoVal rollout; --train_policy is refused on crowd configurations")
     if steps is not None and opt["max_iterations"] > 0:
         raise SystemExit("run.py: --steps and --max_iterations both say how long to train: give one of them")
     if opt["max_iterations"] < 0 or (steps is not None and steps < 0):
@@ -323,9 +344,11 @@ class LocoValTrainee:
     """The LocoVal fit under run_training: an epoch is one horizon of `LocoValRollout.step_once` and `end_epoch`."""
     kind = "locoval"
 
-    def __init__(self, agent, world=1, rank=0, stats=None, capture=None):
-        self.agent, self.world, self.rank, self.stats, self.capture = agent, world, rank, stats, capture
+    def __init__(self, agent, world=1, rank=0, stats=None, capture=None, crowd=None):
+        self.agent, self.world, self.rank, self.stats, self.capture, self.crowd = agent, world, rank, stats, capture, crowd
         self.horizon_length = agent.horizon_length
+        if crowd is not None:
+            agent.attach_crowd_audit(crowd)
         if stats is not None:
             agent.attach_episode_stats(stats)
         if capture is not None:
@@ -352,6 +375,10 @@ class LocoValTrainee:
         info.update(fps_step=frames / dt, fps_total=frames / dt, ep_time=dt)     # the fit runs beside the rollout: one clock for both
         if self.capture is not None:
             info.update(self.capture.end_epoch())        # one read of the counters; the file grows only when captures were taken
+        if self.crowd is not None:                       # one reduction and one read per epoch (this rank's envs)
+            from .crowd_contacts import epoch_tail
+            info["crowd"] = self.crowd.end_epoch()
+            info["tail"] = info.get("tail", "") + epoch_tail(info["crowd"])
         return info
 
     def save(self, mof, epoch=None):
@@ -456,6 +483,9 @@ def main(argv=None):
         train_opt["driver"] = True                       # the recorder is drained once per epoch: the run goes through the driver
     games_num, eval_out, eval_records, max_steps = opt["games_num"], opt["eval_out"], opt["eval_records"], opt["max_steps"]
     compare, eval_tracks = opt["compare"], opt["eval_tracks"]
+    eval_crowd = (opt["crowd_near_dist"],) if opt["eval_crowd"] else None
+    if opt["crowd_near_dist_given"] and not (opt["eval_crowd"] or train_opt["crowd_audit"]):
+        raise SystemExit("run.py: --crowd_near_dist sets up the crowd contact audit: turn it on with --eval_crowd (--test) or --crowd_audit")
     if "--test" in argv:
         vp = _pop_opt(list(argv), "--valuenet_path", "")
         if not vp:
@@ -502,6 +532,11 @@ def main(argv=None):
     refusal = crowd_policy_refusal(cfg["env"], network, use_policy, train_policy, args.test)
     if refusal:
         raise SystemExit(refusal)
+    if eval_crowd is not None or train_opt["crowd_audit"]:      # a configuration the audit cannot run on stops here, before the simulator is built
+        from .crowd_contacts import config_refusal
+        why = config_refusal(cfg["env"])
+        if why:
+            raise SystemExit(f"run.py {'--eval_crowd' if eval_crowd is not None else '--crowd_audit'}: {why}")
     if flags.pred_path:                                  # a missing table stops the run here, by name, before the simulator is built
         from .env.util.traj_generator import PRED_TRAJ_FILE
         import os
@@ -514,7 +549,7 @@ def main(argv=None):
     if args.test:
         capture = None if cap_opt is None else make_capture(env.env.task, cap_opt, rank, world)
         _run_test(args, env, policy_ckpt, games_num, max_steps, eval_out, eval_records, rank, world, say, compare, eval_tracks, capture,
-                  policy_cfg)
+                  policy_cfg, eval_crowd)
         return
     if train_policy:
         from .learning.amp_agent import AMPAgent
@@ -544,7 +579,20 @@ def main(argv=None):
         if train_opt["stats"]:
             from .learning.episode_stats import EpisodeStats
             stats = EpisodeStats(env.env.task, inverted_penalty=agent.inversion_penalty_scale)
-        run_training(LocoValTrainee(agent, world, rank, stats, capture), train_opt, say, rank)
+        crowd = None
+        if train_opt["crowd_audit"]:
+            from .crowd_contacts import CrowdContactAudit, CrowdContactRefusal
+            try:
+                crowd = CrowdContactAudit(env.env.task, near_dist=opt["crowd_near_dist"], totals=True)
+            except CrowdContactRefusal as e:
+                raise SystemExit(f"run.py --crowd_audit: {e}")
+        try:
+            trainee = LocoValTrainee(agent, world, rank, stats, capture, crowd)
+        except RuntimeError as e:
+            if crowd is None:
+                raise
+            raise SystemExit(f"run.py --crowd_audit: {e}")
+        run_training(trainee, train_opt, say, rank)
     else:
         locoval_loop(agent, env.env.num_envs, world, steps, say)
     if world > 1:
@@ -570,10 +618,27 @@ def _gather_track_columns(ev, world):
     return {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
 
 
+def _crowd_columns(ev, world):
+    """--eval_crowd: the `crowd` column set of --eval_records, the record fields of every rank's games in the order of the records
+    (collective)."""
+    from numpy.lib import recfunctions
+    rec = ev.crowd_records()
+    parts = [recfunctions.repack_fields(rec[[k for k in rec.dtype.names if k not in ("env", "game")]])]      # env / game are columns already
+    if world > 1:
+        gathered = [None] * world
+        torch.distributed.all_gather_object(gathered, parts[0])
+        parts = gathered
+    return dict(crowd=np.concatenate(parts))
+
+
+def _crowd_kw(eval_crowd):
+    return {} if eval_crowd is None else dict(crowd=True, crowd_near_dist=eval_crowd[0])
+
+
 def _run_test(args, env, policy_ckpt, games_num, max_steps, eval_out, eval_records, rank, world, say, compare=(), eval_tracks=False,
-              capture=None, cfg_train=None):
+              capture=None, cfg_train=None, eval_crowd=None):
     """--test: LocoValEvaluator with the frozen policy (deterministic actions) and the LocoVal network of --valuenet_path.
-    cfg_train: the policy's training configuration (load_policy_cfg)."""
+    cfg_train: the policy's training configuration (load_policy_cfg).  eval_crowd: None, or (near_dist,) of --eval_crowd."""
     import json
     from .learning.amp_policy import AMPPolicyBundle
     from .learning.locoval_eval import LocoValEvaluator, TrackRefusal
@@ -602,12 +667,14 @@ def _run_test(args, env, policy_ckpt, games_num, max_steps, eval_out, eval_recor
     if compare:
         _run_compare(args, env, bundle, valuenet, compare, int(games_num) if games_num else int(player.get("games_num", 200)),
                      int(max_steps) if max_steps else 27000, float(config.get("gamma", 0.99)), eval_out, eval_records, rank, world, say,
-                     eval_tracks, capture)
+                     eval_tracks, capture, eval_crowd)
         return
+    from .crowd_contacts import CrowdContactRefusal
     try:
         ev = LocoValEvaluator(env, bundle, valuenet, int(games_num) if games_num else int(player.get("games_num", 200)),
-                              max_steps=int(max_steps) if max_steps else 27000, gamma=float(config.get("gamma", 0.99)), track=eval_tracks)
-    except TrackRefusal as e:                    # --eval_tracks on a task it cannot sample: a message, no traceback
+                              max_steps=int(max_steps) if max_steps else 27000, gamma=float(config.get("gamma", 0.99)), track=eval_tracks,
+                              **_crowd_kw(eval_crowd))
+    except (TrackRefusal, CrowdContactRefusal) as e:      # --eval_tracks / --eval_crowd on a task they cannot run on: a message, no traceback
         raise SystemExit(f"run.py --test: {e}")
     if capture is not None:
         ev.flight_recorder = capture.recorder.bind()
@@ -632,6 +699,8 @@ def _run_test(args, env, policy_ckpt, games_num, max_steps, eval_out, eval_recor
             torch.distributed.all_gather_object(gathered, recs)
             parts = gathered
         tcols = _gather_track_columns(ev, world) if eval_tracks else {}
+        if eval_crowd is not None:
+            tcols.update(_crowd_columns(ev, world))
         if rank == 0:
             cols = {k: np.concatenate([p[k] for p in parts]) for k in recs.dtype.names}
             cols["rank"] = np.concatenate([np.full(len(p), r, np.int32) for r, p in enumerate(parts)])
@@ -654,7 +723,7 @@ def compare_columns(recs):
 
 
 def _run_compare(args, env, bundle, valuenet, compare, games_num, max_steps, gamma, eval_out, eval_records, rank, world, say,
-                 eval_tracks=False, capture=None):
+                 eval_tracks=False, capture=None, eval_crowd=None):
     """--test with --compare_valuenet: the network of --valuenet_path and the added ones on the same games, played once."""
     import json
     from .learning.locoval_eval import LocoValEvaluator, TrackRefusal
@@ -670,9 +739,10 @@ def _run_compare(args, env, bundle, valuenet, compare, games_num, max_steps, gam
             raise SystemExit(f"run.py --test: --compare_valuenet {path} does not load as the network its fc1 width names: {e}")
         nets.append(net.eval())
         paths.append(path)
+    from .crowd_contacts import CrowdContactRefusal
     try:
-        ev = LocoValEvaluator(env, bundle, nets, games_num, max_steps=max_steps, gamma=gamma, track=eval_tracks)
-    except TrackRefusal as e:                    # --eval_tracks on a task it cannot sample: a message, no traceback
+        ev = LocoValEvaluator(env, bundle, nets, games_num, max_steps=max_steps, gamma=gamma, track=eval_tracks, **_crowd_kw(eval_crowd))
+    except (TrackRefusal, CrowdContactRefusal) as e:      # --eval_tracks / --eval_crowd on a task they cannot run on: a message, no traceback
         raise SystemExit(f"run.py --test: {e}")
     if capture is not None:
         ev.flight_recorder = capture.recorder.bind()
@@ -693,6 +763,8 @@ def _run_compare(args, env, bundle, valuenet, compare, games_num, max_steps, gam
             torch.distributed.all_gather_object(gathered, parts[0])
             parts = gathered
         tcols = _gather_track_columns(ev, world) if eval_tracks else {}
+        if eval_crowd is not None:
+            tcols.update(_crowd_columns(ev, world))
         if rank == 0:
             cols = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
             cols["rank"] = np.concatenate([np.full(len(p["env"]), r, np.int32) for r, p in enumerate(parts)])
@@ -706,6 +778,8 @@ def _run_compare(args, env, bundle, valuenet, compare, games_num, max_steps, gam
                    "paired": rep["paired"]}
             if eval_tracks:
                 out["tracking"] = rep["tracking"]
+            if eval_crowd is not None:
+                out["crowd"] = rep["crowd"]
             json.dump(out, f, indent=1, default=float)
     if world > 1:
         torch.distributed.destroy_process_group()

@@ -589,6 +589,105 @@ typedef struct EmlocoCrowdBufs {
  * ranges above, n < 0: -1 with the argument named in emloco_last_error(), nothing is written. */
 int emloco_task_crowd_sensor(const EmlocoCrowdBufs *bufs, const int32_t *dev_env_ids, int n, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * The crowd contact audit: how close the members of a group come to each other.  The members of a group do not collide (every env is
+ * its own rigid-body problem); this measures, once per control step and without a host read, the capsule overlaps BETWEEN the
+ * humanoids of a group from the collision segments the self-collision step uses (EmlocoSelfCollisionDesc: cap_a, cap_b, cap_r,
+ * seg_body).  Env e belongs to group e / group_size, as in the crowd sensor.  All arithmetic is fp32 in the stated order, no
+ * contraction, sums left to right:
+ *   segment i of env e on body b = seg_body[i]:  R = q2mat(quat_b) (the stored quaternion, not normalised), o = p_b - p_root(e),
+ *       A_i = o + R cap_a[e][i], B_i = o + R cap_b[e][i], r_i = cap_r[e][i] -- relative to the env's OWN root (body 0), so the rounding
+ *       is that of a body, not of the terrain's extent
+ *   bound_e = max_i(max(|A_i|, |B_i|) + r_i), |v| = sqrtf((x x + y y) + z z)
+ *   env e is finite when the 24 x 7 position and quaternion values of its bodies are; a non-finite env gets flags = 1, zeros and -1
+ *       in its other fields, and is nobody's neighbour.  No index is derived from a state value.
+ *   ordered pair (e, m), m != e of the same group, both finite:  s = p_root(m) - p_root(e), d_xy = sqrtf(s.x s.x + s.y s.y);
+ *       for every (i, j): seg_seg_closest(A_i, B_i, A_j(m) + s, B_j(m) + s) -> c1, c2; dv = c1 - c2; dist2 = (dv.x dv.x + dv.y dv.y) +
+ *       dv.z dv.z; rs = r_i + r_j; dist2 < rs rs: pen_ij = rs - sqrtf(dist2).  pen(e, m) = max pen_ij, 0 if none.
+ * The kernels skip a member whose root is farther than bound_e + bound_m + 1e-3 and a segment pair whose midpoints are farther apart
+ * than the half lengths and radii allow; both follow from the triangle inequality, and the result is that of the full sweep.  Maxima,
+ * minima and counts do not depend on the visiting order: the same bytes from run to run. */
+typedef struct EmlocoCrowdContactNow {
+    float nearest;          /* horizontal (xy) root distance to the nearest finite member of the group, 0 if none */
+    float pen;              /* deepest capsule penetration against any member [m], 0 if none */
+    int32_t nearest_member; /* env id (the lowest at that distance), -1 if none */
+    int32_t pen_member;     /* env id of the member at `pen`, -1 if pen == 0 */
+    int32_t pen_segs;       /* own segment | (other segment << 8), -1 if pen == 0; of the lowest (member, own, other) at `pen` */
+    int32_t n_pen;          /* members with penetration > 0 */
+    int32_t n_near;         /* members with root distance < near_dist */
+    int32_t flags;          /* bit 0: this env's state is non-finite */
+} EmlocoCrowdContactNow;
+
+/* One finished game.  A step counts as finite when flags == 0; the distances only look at steps with a finite neighbour. */
+typedef struct EmlocoCrowdContactRecord {
+    float min_nearest;      /* -1: no step of the game had a finite neighbour */
+    float mean_nearest;     /* (float)(double sum in step order / steps with a neighbour), 0 if none */
+    float max_pen;          /* deepest `pen` of the game, 0 if none */
+    int32_t steps, nonfinite_steps;         /* finite / non-finite steps */
+    int32_t near_steps, contact_steps;      /* steps with n_near > 0 / n_pen > 0 */
+    int32_t contacts;                       /* sum of n_pen */
+    int32_t pen_member, pen_segs, pen_step; /* of the first step at max_pen (1-based, counting every call of the game); -1 if none */
+    int32_t first_contact_step;             /* 1-based, -1 if none */
+} EmlocoCrowdContactRecord;
+
+#define EMLOCO_CROWD_CONTACT_WS 16          /* 32-bit words of game_ws per env */
+#define EMLOCO_CROWD_CONTACT_TOTALS 13
+#define EMLOCO_CROWD_CONTACT_MOMENTS 13
+enum {                                      /* totals[e][k] and the epoch vector */
+    EMLOCO_CCT_STEPS = 0, EMLOCO_CCT_NONFINITE_STEPS = 1, EMLOCO_CCT_CONTACT_STEPS = 2, EMLOCO_CCT_CONTACTS = 3,
+    EMLOCO_CCT_NEAR_STEPS = 4, EMLOCO_CCT_SUM_NEAREST = 5, EMLOCO_CCT_SUM_PEN = 6,
+    EMLOCO_CCT_MAX_PEN = 7,                 /* maximum */
+    EMLOCO_CCT_MIN_NEAREST = 8,             /* minimum over the steps with a neighbour, 0 if there was none */
+    EMLOCO_CCT_GAMES = 9, EMLOCO_CCT_GAMES_CONTACT = 10, EMLOCO_CCT_GAMES_START_CONTACT = 11,
+    EMLOCO_CCT_NEIGHBOUR_STEPS = 12         /* steps with a finite neighbour: what SUM_NEAREST is a sum over */
+};
+enum {                                      /* moments of emloco_crowd_contacts_reduce: sums and counts only */
+    EMLOCO_CCM_GAMES = 0, EMLOCO_CCM_GAMES_CONTACT = 1, EMLOCO_CCM_GAMES_START_CONTACT = 2, EMLOCO_CCM_STEPS = 3,
+    EMLOCO_CCM_CONTACT_STEPS = 4, EMLOCO_CCM_NEAR_STEPS = 5, EMLOCO_CCM_CONTACTS = 6, EMLOCO_CCM_NONFINITE_STEPS = 7,
+    EMLOCO_CCM_SUM_MAX_PEN = 8, EMLOCO_CCM_SUM_MAX_PEN2 = 9,       /* over the games with a contact */
+    EMLOCO_CCM_SUM_MIN_NEAREST = 10, EMLOCO_CCM_SUM_MEAN_NEAREST = 11, EMLOCO_CCM_GAMES_NEIGHBOUR = 12   /* over the games with min_nearest >= 0 */
+};
+typedef struct EmlocoCrowdContacts {
+    int32_t n_env, group_size;      /* group_size >= 2 divides n_env */
+    int32_t n_seg;                  /* 24 .. EMLOCO_SC_MAXSEG (include/emloco_sim.h) */
+    int32_t games_per_env;          /* slots per env of `records` */
+    float near_dist;                /* finite, > 0 */
+    int32_t _pad;
+    const float *rb_state;          /* [E][24][13] */
+    const float *cap_a, *cap_b;     /* [E][n_seg][3] body frame */
+    const float *cap_r;             /* [E][n_seg] */
+    const uint8_t *seg_body;        /* [n_seg], every entry < 24 (checked on the device: a larger one reads body 23) */
+    float *caps_ws;                 /* [E][EMLOCO_SC_MAXSEG][8] workspace: A, r, B, half length + r per segment */
+    float *roots_ws;                /* [E][4] workspace: root position, bound (-1: non-finite) */
+    /* emloco_crowd_contacts_accumulate only */
+    const uint8_t *done8;           /* [E] this step's end-of-game flags, or */
+    const int64_t *done64;          /* [E] the same as int64; at most one of the two, neither: no game ever ends */
+    const int32_t *slot;            /* [E] slot of the game in progress; records only */
+    uint32_t *game_ws;              /* [E][EMLOCO_CROWD_CONTACT_WS] the games' accumulators, zeros to start */
+    EmlocoCrowdContactRecord *records;      /* [E][games_per_env] or NULL */
+    double *totals;                 /* [E][EMLOCO_CROWD_CONTACT_TOTALS] or NULL; zeros to start, cleared by the epoch reduction */
+} EmlocoCrowdContacts;
+
+/* Two launches: the root-relative segments and bounds of every env, then now[E] (one wave per env).  A NULL structure, rb_state,
+ * capsule array, workspace or now, n_env < 1, group_size < 2 or not dividing n_env, n_seg outside 24 .. EMLOCO_SC_MAXSEG, near_dist
+ * not finite and positive: -1 with the argument named in emloco_last_error(), nothing is launched. */
+int emloco_crowd_contacts(const EmlocoCrowdContacts *c, EmlocoCrowdContactNow *now, void *stream);
+
+/* One launch, one thread per env, behind emloco_crowd_contacts on the same stream: now[e] joins the accumulators of env e's game; with
+ * `totals` it also adds to the epoch totals.  Where this step's flag is set the game ends: with `records` and 0 <= slot[e] <
+ * games_per_env its record goes to records[e][slot[e]], and the accumulators start over.  A NULL structure, now or game_ws, n_env < 1,
+ * both done arrays, records without slot or with games_per_env < 1: -1, nothing is launched. */
+int emloco_crowd_contacts_accumulate(const EmlocoCrowdContacts *c, const EmlocoCrowdContactNow *now, void *stream);
+
+/* records[e][g], g < games[e], to moments[EMLOCO_CROWD_CONTACT_MOMENTS] on one workgroup, in double, in a fixed tree order; sums and
+ * counts only, so one all-reduce(sum) over ranks is correct.  A NULL pointer, n_env < 1, games_per_env < 1: -1. */
+int emloco_crowd_contacts_reduce(int n_env, int games_per_env, const EmlocoCrowdContactRecord *records, const int32_t *games,
+                                 double *moments, void *stream);
+
+/* totals[E][EMLOCO_CROWD_CONTACT_TOTALS] to epoch[EMLOCO_CROWD_CONTACT_TOTALS] the same way (MAX_PEN as maximum, MIN_NEAREST as
+ * minimum over the envs with a neighbour step), then totals is cleared.  A NULL pointer, n_env < 1: -1. */
+int emloco_crowd_contacts_epoch_reduce(int n_env, double *totals, double *epoch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
