@@ -14,6 +14,10 @@ autograd Functions the input gradient is written out as its own small network (R
 result is identical):  dD/dx = W1^T (m1 o (W2^T (m2 o w3)))  -- three more GEMMs whose autograd reaches W1, W2, w3.
 Multi-GPU: one flat gradient bucket all-reduced (averaged) per minibatch over RCCL, KL averaged, as the reference does
 with Horovod (amp_continuous.py:436-444, common_agent.py:179-180).
+
+The network is the one `params.network.name` names (`amp_policy.network_classes`).  For `amp_sept_cnn` (the crowd sensor's policy) the
+convolution trunk's backward is switched on (`enable_trunk_backward`, `emloco_cnn_trunk_backward`); for the sept networks nothing
+changes in any launch.
 """
 import contextlib
 import os
@@ -232,11 +236,17 @@ class AMPAgent:
         self.value_mean_std = RunningMeanStd((1,)).to(self.device)
         self._amp_input_mean_std = RunningMeanStd((amp_size,)).to(self.device)
         torch.manual_seed(seed)
-        b = AMPSeptBuilder()
+        from .amp_policy import network_classes
+        b = network_classes(params["network"].get("name", "amp_sept"))[0]()
         b.load(params["network"])
         self.a2c_network = b.build("amp", actions_num=self.actions_num, input_shape=(obs_size,), num_seqs=self.num_actors, value_size=1,
                                    amp_input_shape=(amp_size,), self_obs_size=self_size, task_obs_size=obs_size - self_size,
                                    task_obs_size_detail=task.get_task_obs_size_detail(), mean_std=self.running_mean_std).to(self.device)
+        if hasattr(self.a2c_network, "enable_trunk_backward"):
+            # amp_sept_cnn: the convolution trunk through CnnTrunkFn (emloco_cnn_trunk_backward).  Its gradients reach the bucket through
+            # autograd's accumulation -- the trunk runs on the actor's stream and on the critic's -- and `_task_critic_cnn`, which no
+            # evaluation reads (as in the reference), never gets one: its slice of the zeroed bucket stays zero and Adam leaves it alone
+            self.a2c_network.enable_trunk_backward()
         # hvd.setup_algo (common_agent.py:165-166): every rank starts from rank 0's networks and (initial) statistics
         broadcast_parameters(self.a2c_network, self.running_mean_std, self.value_mean_std, self._amp_input_mean_std)
         # The optimiser step as ONE HIP graph (use_graph): an update step is ~650 launches of 4 - 80 us each -- 8 ms of kernel time that

@@ -1,5 +1,6 @@
 """AMPSeptCNNBuilder -- the PACER policy / critic / discriminator network that reads the crowd sensor's rows, its convolution
-trunk on the fused gfx950 kernel `emloco_cnn_trunk` (csrc/cnn_kernels.hip).  Inference only.
+trunk on the fused gfx950 kernel `emloco_cnn_trunk` (csrc/cnn_kernels.hip) and, where asked for, its backward
+`emloco_cnn_trunk_backward` (csrc/cnn_backward_kernels.hip).
 
 Mirror of /root/reference/pacer/pacer/learning/amp_network_sept_cnn_builder.py:17-164 (AMPSeptCNNBuilder.Network) over
 amp_network_builder.py:16-124 and network_builder.py:125-148 / 165-277 for `amp_humanoid_smpl_cnn_task.yaml` (network `amp_sept_cnn`).
@@ -21,9 +22,13 @@ its 10 path samples written as a literal (:32).  Here the width is `self_obs + t
 `task_mlp.units[-1]` is refused at construction.
 
 Where it runs: on a CUDA tensor the trunk is one `emloco_cnn_trunk` launch (normalisation switched off: like the reference's, the
-module takes normalised observations) and every Linear one `emloco_gemm_f32` launch (`ops.linear`); the trunk has no backward, so
-with grad enabled it raises.  On a CPU tensor, where no kernel of this package can run, the same layers are evaluated by torch (host
-tests build the module and compare it with the reference's fixtures that way)."""
+module takes normalised observations) and every Linear one `emloco_gemm_f32` launch (`ops.linear`).  With grad enabled the device
+trunk raises unless `enable_trunk_backward()` was called (AMPAgent does, run.py --train_policy --cnn_backward); then it goes through
+`CnnTrunkFn`: the forward saves the map and the packed parameters and nothing else, the backward recomputes the activations on chip
+and returns the weight and bias gradients (none for the map: observations are data).  In train mode RunningMeanStd updates its
+statistics, so the training module keeps taking normalised rows (the fused normalisation is the frozen runner's).  On a CPU tensor,
+where no kernel of this package can run, the same layers are evaluated by torch (host tests build the module and compare it with the
+reference's fixtures that way)."""
 import ctypes as C
 import math
 
@@ -88,6 +93,58 @@ def cnn_trunk(x, col0, res, channels, filters, params, out, out_off=0, mean=None
     return out
 
 
+def cnn_trunk_backward(x, col0, res, channels, filters, params, dout, dout_off=0, mean=None, var=None, eps=1e-5, clip=5.0):
+    """One emloco_cnn_trunk_backward call (two launches on x's current stream): the operands of `cnn_trunk` and `dout`, the gradient of
+    the features at columns [dout_off, ...) of its rows -> `dparams`, laid out like `params`: every weight and bias gradient summed
+    over the rows.  The workspace is a fresh tensor per call (the trunk is evaluated on the actor's stream and on the critic's); no
+    host synchronisation, so it may run inside a captured graph."""
+    lib = ops._lib()
+    assert x.dtype == torch.float32 and x.stride(1) == 1 and dout.dtype == torch.float32 and dout.stride(1) == 1 and x.shape[0] == dout.shape[0]
+    assert params.dtype == torch.float32 and params.is_contiguous()
+    f4 = list(filters) + [0] * (4 - len(filters))
+    norm = mean is not None
+    n_ws = lib.emloco_cnn_trunk_backward_workspace(x.shape[0], res, channels, len(filters), *f4)
+    ops._chk(-1 if n_ws < 0 else 0, "emloco_cnn_trunk_backward_workspace")
+    workspace = torch.empty(n_ws, dtype=torch.float32, device=x.device)
+    dparams = torch.empty_like(params)
+    rc = lib.emloco_cnn_trunk_backward(x.shape[0], res, channels, len(filters), *f4, ops._p(x, col0), x.stride(0), ops._p(mean) if norm else None,
+                                       ops._p(var) if norm else None, C.c_float(eps), C.c_float(clip), int(norm), ops._p(params), ops._p(dout),
+                                       dout.stride(0), dout_off, ops._p(dparams), ops._p(workspace), n_ws, ops._st(x))
+    ops._chk(rc, "emloco_cnn_trunk_backward")
+    return dparams
+
+
+class CnnTrunkFn(torch.autograd.Function):
+    """features = trunk(maps; w1, b1, w2, b2, ...) on the device, differentiable in the weights and biases: forward one `emloco_cnn_trunk`
+    launch, backward one `emloco_cnn_trunk_backward` call that recomputes the activations on chip (nothing but the map and the packed
+    parameters is saved).  The map gets no gradient -- the observations are data -- and one that asks for it is refused."""
+
+    @staticmethod
+    def forward(ctx, maps, res, channels, filters, *wb):
+        if maps.requires_grad:
+            raise NotImplementedError("CnnTrunkFn: `maps` requires grad, and the trunk's backward produces no gradient with respect to the map")
+        assert len(wb) == 2 * len(filters)
+        params = torch.cat([t.detach().reshape(-1).float() for t in wb]).contiguous()
+        side = res >> len(filters)
+        out = torch.empty((maps.shape[0], filters[-1] * side * side), dtype=torch.float32, device=maps.device)
+        cnn_trunk(maps, 0, res, channels, filters, params, out)
+        ctx.save_for_backward(maps, params)
+        ctx.shape = (res, channels, tuple(filters))
+        ctx.sizes = [(t.numel(), t.shape) for t in wb]
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        maps, params = ctx.saved_tensors
+        res, channels, filters = ctx.shape
+        dparams = cnn_trunk_backward(maps, 0, res, channels, filters, params, dout if dout.stride(1) == 1 else dout.contiguous())
+        grads, at = [], 0
+        for i, (n, shape) in enumerate(ctx.sizes):
+            grads.append(dparams[at:at + n].view(shape) if ctx.needs_input_grad[4 + i] else None)
+            at += n
+        return (None, None, None, None, *grads)
+
+
 class AMPSeptCNNBuilder:
     def __init__(self, **kwargs):
         self.params = None
@@ -145,6 +202,15 @@ class AMPSeptCNNBuilder:
                 cin = f
             return nn.Sequential(*layers)
 
+        _trunk_backward = False                                             # (a class default: `load` / `_build_task_mlp` run inside __init__)
+
+        def enable_trunk_backward(self, on=True):
+            """Opt in to (or out of) differentiating the device trunk: with grad enabled `_trunk` then goes through `CnnTrunkFn`
+            instead of raising.  Off at construction.  The trunk's gradients reach the parameters through autograd's accumulation
+            (not `ops.mark_direct_grad`): the trunk is evaluated on the actor's stream and on the critic's."""
+            self._trunk_backward = bool(on)
+            return self
+
         # ------------------------------------------------------------------ forward pieces
         def _trunk(self, maps):
             """(B, channels * res^2) normalised map columns, channel last -> (B, features), flattened (channel, row, column)"""
@@ -152,7 +218,11 @@ class AMPSeptCNNBuilder:
                 x = maps.reshape(maps.shape[0], self.res, self.res, self.channels).permute(0, 3, 1, 2)
                 return self._task_actor_cnn(x).reshape(maps.shape[0], -1)
             if torch.is_grad_enabled():
-                raise NotImplementedError("the CNN trunk's backward is not built")
+                if not self._trunk_backward:
+                    raise NotImplementedError("the CNN trunk's backward is not built into this module's default path: call "
+                                              "enable_trunk_backward() to differentiate the device trunk (emloco_cnn_trunk_backward)")
+                convs = [m for m in self._task_actor_cnn if isinstance(m, nn.Conv2d)]
+                return CnnTrunkFn.apply(maps, self.res, self.channels, tuple(self._filters), *[t for m in convs for t in (m.weight, m.bias)])
             out = torch.empty((maps.shape[0], self.features), dtype=torch.float32, device=maps.device)
             return cnn_trunk(maps, 0, self.res, self.channels, self._filters, pack_trunk(self._task_actor_cnn), out)
 

@@ -450,9 +450,10 @@ def load_policy_cfg(args):
         raise SystemExit(f"run.py --cfg_train: cannot read {path}: {e}")
 
 
-def crowd_policy_refusal(env_cfg, network, use_policy, train_policy, test):
+def crowd_policy_refusal(env_cfg, network, use_policy, train_policy, test, cnn_backward=False):
     """Why this combination of environment configuration, policy network (`params.network.name` of the training configuration) and
-    flags cannot run, or None.  No device is touched."""
+    flags cannot run, or None.  `cnn_backward`: --cnn_backward was given, which lets --train_policy through for the amp_sept_cnn
+    network (the trunk's backward kernel, emloco_cnn_trunk_backward).  No device is touched."""
     from .crowd_sensor import is_crowd_config
     if not (use_policy or train_policy or test):
         return None
@@ -460,10 +461,12 @@ def crowd_policy_refusal(env_cfg, network, use_policy, train_policy, test):
     if network not in NETWORKS:
         return f"run.py --cfg_train: network '{network}' is not built (params.network.name: one of {', '.join(NETWORKS)})"
     crowd = is_crowd_config(env_cfg)
-    if train_policy and (crowd or network == "amp_sept_cnn"):
+    if train_policy and (crowd or network == "amp_sept_cnn") and not (cnn_backward and network == "amp_sept_cnn"):
         return ("run.py --train_policy: the CNN policy of the crowd sensor (amp_network_sept_cnn_builder.py, network amp_sept_cnn) runs as "
-                "inference only -- the CNN trunk's backward is not built, so it cannot be trained here.  A frozen policy "
-                "(--policy_checkpoint / --policy_random_init) and --test take --cfg_train "
+                "inference only by default -- the CNN trunk's backward is not built into the default run, so it cannot be trained without "
+                "asking: add --cnn_backward (with --cfg_train emloco_amd/data/cfg/train/rlg/amp_humanoid_smpl_cnn_task.yaml) to train it "
+                "through emloco_cnn_trunk_backward; an opt-in, the device path is unmeasured and nobody has shown that this network learns "
+                "on this physics.  A frozen policy (--policy_checkpoint / --policy_random_init) and --test take --cfg_train "
                 "emloco_amd/data/cfg/train/rlg/amp_humanoid_smpl_cnn_task.yaml")
     if crowd and network != "amp_sept_cnn":
         return ("run.py: the configuration asks for the crowd sensor (divide_group / velocity_map / sensor_res / sensor_extent), whose "
@@ -510,6 +513,12 @@ def main(argv=None):
     train_policy = "--train_policy" in argv        # configs[1]: PPO + AMP pretraining of the policy (pacer/run.py without --test)
     if train_policy:
         argv.remove("--train_policy")
+    cnn_backward = "--cnn_backward" in argv        # opt-in: PPO on the amp_sept_cnn network through the trunk's backward kernel
+    if cnn_backward:
+        argv.remove("--cnn_backward")
+        if not train_policy:
+            raise SystemExit("run.py --cnn_backward: the flag switches on the CNN trunk's backward for --train_policy and means nothing "
+                             "without it (a frozen policy and --test never differentiate the trunk)")
     # one process per GPU (torch.distributed.run): the reference's --horovod launch (run.py:57-66, common_agent.py:165-180).
     # num_envs is the GLOBAL count: rank r simulates the contiguous shard [r * E / W, (r + 1) * E / W) on cuda:LOCAL_RANK with
     # seed + rank; the learners exchange gradients / statistics through emloco_amd.dist
@@ -529,9 +538,12 @@ def main(argv=None):
     fill_flags(args)
     policy_cfg = load_policy_cfg(args) if (use_policy or train_policy or args.test) else None
     network = policy_cfg["params"]["network"].get("name", "amp_sept") if policy_cfg else None
-    refusal = crowd_policy_refusal(cfg["env"], network, use_policy, train_policy, args.test)
+    refusal = crowd_policy_refusal(cfg["env"], network, use_policy, train_policy, args.test, cnn_backward=cnn_backward)
     if refusal:
         raise SystemExit(refusal)
+    if cnn_backward and network != "amp_sept_cnn":
+        raise SystemExit(f"run.py --cnn_backward: the policy network '{network}' has no CNN trunk to differentiate; the flag goes with "
+                         "--cfg_train emloco_amd/data/cfg/train/rlg/amp_humanoid_smpl_cnn_task.yaml (network amp_sept_cnn)")
     if eval_crowd is not None or train_opt["crowd_audit"]:      # a configuration the audit cannot run on stops here, before the simulator is built
         from .crowd_contacts import config_refusal
         why = config_refusal(cfg["env"])

@@ -245,6 +245,23 @@ int emloco_cnn_trunk(int rows, int res, int channels, int layers, int f0, int f1
                      const float *mean, const float *var, float eps, float clip, int normalize, const float *params, float *out, int ldo,
                      int out_off, void *stream);
 
+/* The trunk under autograd: what torch's backward through `_task_actor_cnn` (amp_network_sept_cnn_builder.py:49-67 with grad enabled)
+ * leaves in the `.grad` of every Conv2d weight and bias.  The operands rows .. params are emloco_cnn_trunk's; dout [rows][lddo] holds
+ * the gradient of the flattened features at dout[row * lddo + dout_off ...] (columns outside them are not read).  dparams, laid out
+ * like params, is OVERWRITTEN with the sum over all rows of every weight and bias gradient; the ReLU passes the gradient where the
+ * output is > 0 (torch's rule).  No gradient with respect to the map is produced: the observations are data.  Nothing is saved by the
+ * forward: the activations are recomputed from x and params in the forward's arithmetic and kept in LDS, so the masks are the
+ * forward's bit for bit, and neither an activation nor an activation gradient goes to memory.  Two launches: per workgroup a partial
+ * [P] vector into workspace (P = the length of params), then an in-order sum over the workgroups; the grid is a function of rows alone
+ * and no float atomics are used, so equal inputs give equal bits.  workspace: emloco_cnn_trunk_backward_workspace(...) floats of
+ * device memory (that call returns -1 where emloco_cnn_trunk would refuse the shape); workspace_floats is what the caller allocated.
+ * Shapes: exactly emloco_cnn_trunk's. */
+int64_t emloco_cnn_trunk_backward_workspace(int rows, int res, int channels, int layers, int f0, int f1, int f2, int f3);
+int emloco_cnn_trunk_backward(int rows, int res, int channels, int layers, int f0, int f1, int f2, int f3, const float *x, int ldx,
+                              const float *mean, const float *var, float eps, float clip, int normalize, const float *params,
+                              const float *dout, int lddo, int dout_off, float *dparams, float *workspace, int64_t workspace_floats,
+                              void *stream);
+
 /* Statistics update of the same normaliser (RunningMeanStd.forward in training mode, running_mean_std.py:85-95, called once per
  * rollout step by the PPO / AMP learner on the observation and AMP-observation batches): merges the per-column mean and unbiased
  * variance of x [rows][ldx] into the float64 running moments mean / var [cols] with the parallel-variance rule (count_in [1] rows
