@@ -204,6 +204,18 @@ class CrowdContacts(C.Structure):
                 ("game_ws", C.c_void_p), ("records", C.c_void_p), ("totals", C.c_void_p)]
 
 
+PEOPLE_TOPK, PEOPLE_JOINTS, PEOPLE_WIDTH = 5, 10, 165          # EMLOCO_PEOPLE_*
+PEOPLE_FAR = 10.0                                               # EMLOCO_PEOPLE_FAR
+PEOPLE_BODIES = (0, 1, 5, 9, 3, 7, 16, 21, 18, 23)              # EMLOCO_PEOPLE_BODIES
+
+
+class CrowdPeople(C.Structure):
+    """EmlocoCrowdPeople (include/emloco_task.h): the group observation's inputs, workspace and observation rows."""
+    _fields_ = [("n_env", C.c_int32), ("group_size", C.c_int32), ("obs_stride", C.c_int32), ("col", C.c_int32),
+                ("rb_state", C.c_void_p), ("roots_ws", C.c_void_p), ("obs", C.c_void_p), ("flip_obs", C.c_void_p),
+                ("neighbours", C.c_void_p)]
+
+
 class LocoValStep(C.Structure):
     """EmlocoLocoValStep (include/emloco_predictor.h)."""
     _fields_ = [("n_env", C.c_int32), ("step_to_pred", C.c_int32), ("gamma", C.c_float), ("inversion_penalty", C.c_float),

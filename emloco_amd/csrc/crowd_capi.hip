@@ -1,7 +1,9 @@
-// crowd_capi.hip -- C ABI (include/emloco_task.h) over the crowd-aware terrain sensor's kernels and the crowd contact audit's.
+// crowd_capi.hip -- C ABI (include/emloco_task.h) over the crowd-aware terrain sensor's kernels, the crowd contact audit's and the
+// group observation's.
 #include <hip/hip_runtime.h>
 #include "crowd_kernels.hip"
 #include "crowd_contact_kernels.hip"
+#include "crowd_people_kernels.hip"
 #include "capi_error.h"
 
 using emloco::capi_fail;
@@ -64,6 +66,20 @@ int emloco_crowd_contacts_epoch_reduce(int n_env, double *totals, double *epoch,
     if (!totals) return capi_fail(EMLOCO_E_ARG, who, "null totals");
     if (!epoch) return capi_fail(EMLOCO_E_ARG, who, "null epoch");
     hipLaunchKernelGGL(emloco::crowd_contact_epoch_kernel, dim3(1), dim3(emloco::kContactReduceThreads), 0, (hipStream_t)stream, n_env, totals, epoch);
+    EMLOCO_HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int emloco_task_crowd_people(const EmlocoCrowdPeople *p, const int32_t *dev_env_ids, int n, void *stream) {
+    const char *who = "emloco_task_crowd_people";
+    if (const char *why = emloco::crowd_people_refusal(p, n)) return capi_fail(EMLOCO_E_ARG, who, why);
+    hipStream_t st = (hipStream_t)stream;
+    const int rows = dev_env_ids ? n : p->n_env;
+    if (rows == 0) return 0;
+    hipLaunchKernelGGL(emloco::crowd_people_roots_kernel, dim3((unsigned)((p->n_env + 255) / 256)), dim3(256), 0, st, *p);
+    EMLOCO_HIPCHK(hipGetLastError());
+    const unsigned grid = crowd_grid((rows + emloco::kPeopleWaves - 1) / emloco::kPeopleWaves);
+    hipLaunchKernelGGL(emloco::crowd_people_kernel, dim3(grid), dim3(emloco::kPeopleThreads), 0, st, *p, dev_env_ids, rows);
     EMLOCO_HIPCHK(hipGetLastError());
     return 0;
 }

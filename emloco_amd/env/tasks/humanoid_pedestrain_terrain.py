@@ -61,8 +61,15 @@ class HumanoidPedestrianTerrain(humanoid_traj.HumanoidTraj):
         self.velocity_map = bool(cfg["env"].get("velocity_map", False))
         self._divide_group = bool(cfg["env"].get("divide_group", False))                         # humanoid.py:221-226
         self._group_num_people = min(int(cfg["env"].get("num_env_group", 128)), self.num_envs)
-        if cfg["env"].get("group_obs", False):
-            raise NotImplementedError("group_obs: True (the point-net observation of the other members' joints) is not built")
+        # group_obs (humanoid.py:222-223): the 165-wide `people` block behind the map, and no group stamps on it (:792).  Without
+        # divide_group it adds nothing, as in the reference; disable_group_obs switches stamps and block off
+        from ...crowd_people import config_block, group_refusal
+        self._disable_group_obs = bool(cfg["env"].get("disable_group_obs", False))
+        self._group_obs = config_block(cfg["env"])
+        self._group_stamps = self._divide_group and not cfg["env"].get("group_obs", False) and not self._disable_group_obs
+        why = group_refusal(self._group_num_people) if self._group_obs else None
+        if why:
+            raise NotImplementedError(why)
         if not (self.terrain_obs and self.terrain_obs_type == "square" and self.terrain_obs_root == "head" and
                 cfg['env'].get("use_center_height", False) and self.power_reward and self.location_coefficient == 1):
             raise NotImplementedError("emloco fused kernels cover pacer.yaml's terrain observation / reward settings")
@@ -106,6 +113,8 @@ class HumanoidPedestrianTerrain(humanoid_traj.HumanoidTraj):
             obs_size = 2 * self._num_traj_samples
             if self.terrain_obs:
                 obs_size += self.num_height_points * (3 if self.velocity_map else 1)     # :306-310
+            if self._group_obs:
+                obs_size += L.PEOPLE_WIDTH                                               # :312-313
         return obs_size
 
     def get_task_obs_size_detail(self):
@@ -118,6 +127,8 @@ class HumanoidPedestrianTerrain(humanoid_traj.HumanoidTraj):
                 d['heightmap_velocity'] = self.num_height_points * 3
             else:
                 d['heightmap'] = self.num_height_points
+        if self._group_obs:                                                                # :332-333
+            d['people'] = L.PEOPLE_WIDTH
         return d
 
     def get_head_pose(self, env_ids=None):
@@ -512,7 +523,8 @@ class HumanoidPedestrianTerrainCrowd(HumanoidPedestrianTerrain):
     sensor_extent: `HumanoidPedestrianTerrain(cfg, ...)` returns this class for one).  The fused post-physics kernel keeps its
     1422-wide row and writes into two scratch buffers; a crowd-sensor call behind every observation launch copies the self and
     location columns of the rows it is asked for into the task's buffers, which have the reference's width, and fills the sensor block
-    beside them (emloco_amd/crowd_sensor.py).  Sequential launch arrangement, host reset path."""
+    beside them (emloco_amd/crowd_sensor.py).  With group_obs the map carries no group stamps and a crowd-people call behind the sensor's
+    fills the 165 columns behind the map (emloco_amd/crowd_people.py).  Sequential launch arrangement, host reset path."""
     fused_chain = _sequential_only("fused_chain")
     overlap_obs = _sequential_only("overlap_obs")
     overlap_reset = _sequential_only("overlap_reset")
@@ -526,9 +538,13 @@ class HumanoidPedestrianTerrainCrowd(HumanoidPedestrianTerrain):
         self._crowd = CrowdSensor(
             rb_state=self._rigid_body_state, heightfield=self.height_samples.contiguous(), hscale=self.terrain.horizontal_scale,
             vscale=self.terrain.vertical_scale, head_body=self._post.head_body, n_env=self.num_envs,
-            num_env_group=self._group_num_people, stamps=self._divide_group, velocity_map=self.velocity_map, res=self.sensor_res,
+            num_env_group=self._group_num_people, stamps=self._group_stamps, velocity_map=self.velocity_map, res=self.sensor_res,
             extent=float(self.sensor_extent), obs=self.obs_buf, flip_obs=self._flip_obs_buf, src_obs=self._crowd_src_obs,
             src_flip_obs=self._crowd_src_flip, n_copy=n_copy)
+        if self._group_obs:
+            from ...crowd_people import CrowdPeople
+            self._people = CrowdPeople(rb_state=self._rigid_body_state, n_env=self.num_envs, group_size=self._group_num_people,
+                                       obs=self.obs_buf, flip_obs=self._flip_obs_buf, col=self.obs_buf.shape[1] - L.PEOPLE_WIDTH)
         return self._make_post_bufs_on(self._crowd_src_obs, self._crowd_src_flip)
 
     def _launch_post(self, mode, env_ids=None):
@@ -536,6 +552,8 @@ class HumanoidPedestrianTerrainCrowd(HumanoidPedestrianTerrain):
         if mode & L.POST_OBS:
             ids = None if env_ids is None else self._humanoid_actor_ids[env_ids.to(self.device)].contiguous()
             self._crowd.run(ids)
+            if self._group_obs:
+                self._people.run(ids)
 
 
 def poles_terrain(terrain, difficulty=1):                           # :937-993

@@ -176,6 +176,9 @@ class AMPSeptCNNBuilder:
         def _build_task_mlp(self):
             detail = self.task_obs_size_detail
             assert "traj" in detail
+            if "people" in detail:
+                raise NotImplementedError("the amp_sept_cnn network does not read a 'people' block (group_obs): its map slice assumes the map "
+                                          "ends the row.  The people block is read by the amp_sept network's point-net branch")
             self.res, self.channels = map_shape(detail, len(self._filters))
             side = self.res >> len(self._filters)
             self.features = self._filters[-1] * side * side
@@ -226,14 +229,7 @@ class AMPSeptCNNBuilder:
             out = torch.empty((maps.shape[0], self.features), dtype=torch.float32, device=maps.device)
             return cnn_trunk(maps, 0, self.res, self.channels, self._filters, pack_trunk(self._task_actor_cnn), out)
 
-        @staticmethod
-        def _on(x, module, y):
-            """`module(y)`: the GEMM kernels on the device; plain torch layers on the host, where those kernels cannot run"""
-            if x.is_cuda:
-                return module(y)
-            return nn.Sequential.forward(module, y) if isinstance(module, nn.Sequential) else nn.Linear.forward(module, y)
-
-        def eval_task(self, task_obs):
+        def eval_task(self, task_obs):                                      # (`_on`: the parent's)
             traj = int(self.task_obs_size_detail["traj"])
             maps = task_obs[:, traj:]
             feat = self._trunk(maps if maps.stride(1) == 1 else maps.contiguous())

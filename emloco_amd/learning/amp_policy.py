@@ -16,7 +16,7 @@ import yaml
 from ..utils.running_mean_std import RunningMeanStd
 from .amp_network_sept_builder import AMPSeptBuilder
 from .amp_network_sept_cnn_builder import AMPSeptCNNBuilder
-from .policy_runner import CnnFrozenPolicy, FrozenDisc, FrozenPolicy
+from .policy_runner import CnnFrozenPolicy, FrozenDisc, FrozenPolicy, PeopleFrozenPolicy
 
 DEFAULT_CFG = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "data", "cfg", "train", "rlg",
                            "amp_humanoid_smpl_sept_task.yaml")
@@ -33,6 +33,15 @@ def network_classes(name):
     return NETWORKS[name]
 
 
+def runner_class(name, network):
+    """The frozen runner of a built network: the table's, or PeopleFrozenPolicy where the sept network carries the people branch
+    (a `people` block in the task observation: group_obs)."""
+    runner_cls = network_classes(name)[1]
+    if runner_cls is FrozenPolicy and getattr(network, "has_people", False):
+        return PeopleFrozenPolicy
+    return runner_cls
+
+
 class AMPPolicyBundle:
     def __init__(self, task, cfg_train=None, checkpoint=None, deterministic=False, seed=0):
         if cfg_train is None:
@@ -47,7 +56,7 @@ class AMPPolicyBundle:
         amp_size = task.get_num_amp_obs()
         self.running_mean_std = RunningMeanStd((obs_size,)).to(self.device).eval()
         self.amp_input_mean_std = RunningMeanStd((amp_size,)).to(self.device).eval()
-        builder_cls, runner_cls = network_classes(params["network"].get("name", "amp_sept"))
+        builder_cls, _ = network_classes(params["network"].get("name", "amp_sept"))
         builder = builder_cls()
         builder.load(params["network"])
         self.a2c_network = builder.build(
@@ -62,6 +71,7 @@ class AMPPolicyBundle:
                 self.running_mean_std.load_state_dict(ck["running_mean_std"])
             if "amp_input_mean_std" in ck:
                 self.amp_input_mean_std.load_state_dict(ck["amp_input_mean_std"])
+        runner_cls = runner_class(params["network"].get("name", "amp_sept"), self.a2c_network)
         self.frozen = runner_cls(self.a2c_network, self.running_mean_std, self.num_envs, self.device,
                                  clip_actions=float(self.config.get("clip_actions", 1.0)))
         self.deterministic = deterministic

@@ -43,6 +43,8 @@ def _frozen_image(owner, w, n, k):
 
 
 class FrozenPolicy:
+    extra_actor_in = 0          # columns of the actor operand behind the task MLP's (PeopleFrozenPolicy: the point-net embedding)
+
     def __init__(self, network, mean_std, num_envs, device, clip_actions=1.0):
         self.E, self.device, self.clip = num_envs, torch.device(device), float(clip_actions)
         self.self_size, self.task_size = network.self_obs_size, network.task_obs_size
@@ -58,13 +60,13 @@ class FrozenPolicy:
         w0, b0 = self.task_layers[0]
         self.task_k = (self.task_size + _PAD - 1) // _PAD * _PAD
         w0p = torch.zeros((w0.shape[0], self.task_k), dtype=torch.float32, device=self.device)
-        w0p[:, :self.task_size] = w0
+        w0p[:, :w0.shape[1]] = w0                               # (PeopleFrozenPolicy: zeros over the people columns as well)
         self.task_layers[0] = (w0p, b0)
         self.mean32 = mean_std.running_mean.to(self.device).float().contiguous()
         self.var32 = mean_std.running_var.to(self.device).float().contiguous()
         self.eps = float(mean_std.epsilon)
         self.exp_sigma = torch.exp(self.sigma)                 # the frozen policy's standard deviation: constant
-        self.actor_in_size = self.self_size + self.task_layers[-1][0].shape[0]
+        self.actor_in_size = self.self_size + self.task_layers[-1][0].shape[0] + self.extra_actor_in
         assert self.actor_layers[0][0].shape[1] == self.actor_in_size and self.actor_in_size % _PAD == 0
         E = num_envs
         f = dict(dtype=torch.float32, device=self.device)
@@ -201,6 +203,73 @@ class CnnFrozenPolicy(FrozenPolicy):
                 self._linear(x, x.shape[1], w, b, self.cnn_h[i])
                 x = self.cnn_h[i]
         x, k = self.actor_in, self.actor_k
+        for i, (w, b) in enumerate(self.actor_layers):
+            self._linear(x, k, w, b, self.actor_h[i])
+            x, k = self.actor_h[i], w.shape[0]
+        self._linear(x, k, self.mu_w, self.mu_b, self.mu, relu=False)
+        return self.mu
+
+
+class PeopleFrozenPolicy(FrozenPolicy):
+    """The frozen forward of the sept network with the people branch (amp_network_sept_builder.py: eval_actor with `_point_net`) for
+    rows [self 368 | path 30 | map 1024 | people 165]; `act`, `_linear` and `from_checkpoint` are FrozenPolicy's.  FrozenPolicy's
+    launches stay as they are: the first task layer's K is zero-padded over the people columns, so the task MLP reads the whole
+    normalised task part and sees path and map only.  Behind them, on the caller's stream:
+      - one elementwise launch un-normalises the people columns of the task operand as the module does (x * sqrt(var) + mean, no
+        epsilon, the clamp stays) into a zero-padded (5 E, 36) operand -- the module's literal view (B, 5, 33);
+      - the three point-net GEMMs with the bias / ReLU epilogue;
+      - one maximum over the five rows of an env, straight into columns [368 + 256, 368 + 256 + 64) of the actor operand."""
+
+    def __init__(self, network, mean_std, num_envs, device, clip_actions=1.0):
+        self.extra_actor_in = int(network.point_net_embedding_size)
+        super().__init__(network, mean_std, num_envs, device, clip_actions)          # (pads _task_mlp.0.weight over the people columns)
+        detail = network.task_obs_size_detail
+        self.topk, self.people = int(network.topk), int(detail["people"])
+        self.people_col = int(detail["traj"]) + int(detail["heightmap"])
+        assert self.people_col + self.people == self.task_size and self.people % self.topk == 0
+        f = dict(dtype=torch.float32, device=self.device)
+        sd = {k: v.detach().to(self.device, torch.float32).clone().contiguous() for k, v in network.state_dict().items() if k.startswith("_point_net.")}
+        idx = sorted({int(k.split(".")[1]) for k in sd if k.endswith(".weight")})
+        self.point_layers = [(sd[f"_point_net.{i}.weight"], sd[f"_point_net.{i}.bias"]) for i in idx]
+        w0, b0 = self.point_layers[0]
+        self.point_w = self.people // self.topk
+        self.point_k = (self.point_w + _PAD - 1) // _PAD * _PAD
+        w0p = torch.zeros((w0.shape[0], self.point_k), **f)
+        w0p[:, :self.point_w] = w0
+        self.point_layers[0] = (w0p, b0)
+        lo = self.self_size + self.people_col
+        self.people_mean = self.mean32[lo:lo + self.people].clone()
+        self.people_std = torch.sqrt(self.var32[lo:lo + self.people])
+        self.embed = self.point_layers[-1][0].shape[0]
+        self.mlp_out = self.task_layers[-1][0].shape[0]
+        assert self.embed == self.extra_actor_in and self.actor_in_size == self.self_size + self.mlp_out + self.embed
+        E = num_envs
+        self.point_in = torch.zeros((E * self.topk, self.point_k), **f)            # pad columns stay zero
+        self.point_rows = self.point_in.view(E, self.topk, self.point_k)[:, :, :self.point_w]
+        self.point_h = [torch.empty((E * self.topk, w.shape[0]), **f) for w, _ in self.point_layers]
+        self.point_feat = self.actor_in[:, self.self_size + self.mlp_out:]
+        self.flops_per_env += 2 * self.topk * sum(w.shape[0] * w.shape[1] for w, _ in self.point_layers)
+
+    def act_mean(self, obs):
+        """obs (E, self + path + map + people) fp32 on the device -> mu (E, actions); the returned tensor is reused by the next call."""
+        assert obs.shape == (self.E, self.self_size + self.task_size)
+        obs_normalize(obs, self.mean32, self.var32, self.eps, 5.0, split=self.self_size, out0=self.actor_in, out1=self.task_in)
+        x, k = self.task_in, self.task_k
+        for i, (w, b) in enumerate(self.task_layers):
+            if i == len(self.task_layers) - 1:
+                self._linear(x, k, w, b, self.actor_in, ldc=self.actor_in_size, c_off=self.self_size)
+            else:
+                self._linear(x, k, w, b, self.task_h[i])
+                x, k = self.task_h[i], w.shape[0]
+        people = self.task_in[:, self.people_col:self.people_col + self.people]
+        torch.addcmul(self.people_mean.view(self.topk, self.point_w), people.view(self.E, self.topk, self.point_w),
+                      self.people_std.view(self.topk, self.point_w), out=self.point_rows)
+        x, k = self.point_in, self.point_k
+        for i, (w, b) in enumerate(self.point_layers):
+            self._linear(x, k, w, b, self.point_h[i], relu=i < len(self.point_layers) - 1)
+            x, k = self.point_h[i], w.shape[0]
+        torch.amax(x.view(self.E, self.topk, self.embed), dim=1, out=self.point_feat)
+        x, k = self.actor_in, self.actor_in_size
         for i, (w, b) in enumerate(self.actor_layers):
             self._linear(x, k, w, b, self.actor_h[i])
             x, k = self.actor_h[i], w.shape[0]

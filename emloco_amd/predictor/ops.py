@@ -3,6 +3,7 @@
 PyTorch carries the autograd graph, device memory and the current stream; every contraction, softmax and
 layer norm below runs in libemloco_hip.so.  There is no fallback: without the library / a GPU these raise.
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -66,8 +67,29 @@ def backward_pieces():
     return dict(_BWD_PIECES)
 
 
-def _bwd_flags(kind):
-    return GEMM_SPLIT2 if _BWD_PIECES[kind] == 2 else 0
+_PIECES_FOR = [None]       # pieces of the gradient GEMMs of the `linear` calls made inside `backward_pieces_for` (None: _BWD_PIECES)
+
+
+@contextlib.contextmanager
+def backward_pieces_for(pieces):
+    """Every `linear` evaluated inside takes `pieces` (2 | 3) per operand in ITS gradient GEMMs, whenever its backward runs, instead of
+    the process-wide `_BWD_PIECES`.  The sept network's people branch evaluates actor and critic under 3: its point-net reads
+    un-normalised coordinates, and its gradients are held to the fp32 class (tests/test_gpu_crowd_people.py)."""
+    if pieces not in (2, 3):
+        raise ValueError(f"backward_pieces_for({pieces}): the pieces per operand of the backward products are 2 or 3")
+    before, _PIECES_FOR[0] = _PIECES_FOR[0], pieces
+    try:
+        yield
+    finally:
+        _PIECES_FOR[0] = before
+
+
+def _bwd_pieces(kind, pieces=None):
+    return pieces if pieces is not None else _BWD_PIECES[kind]
+
+
+def _bwd_flags(kind, pieces=None):
+    return GEMM_SPLIT2 if _bwd_pieces(kind, pieces) == 2 else 0
 # Frozen weights (the rollout's policy and discriminator) are cut into their bf16 pieces ONCE, when first used (learning/policy_runner.py:
 # +1.4 % on the policy forward, +1.8 % on the configs[2] loop, profiles/r05_ab_weight_image.txt); EMLOCO_GEMM_WEIGHT_IMAGE=0: never.
 # A trained weight would have to be cut once per launch (one small extra launch): measured on the predictor's tall GEMMs that buys
@@ -195,6 +217,7 @@ class LinearFn(torch.autograd.Function):
         ctx.save_for_backward(x2, Wc, y if relu else None)
         ctx.relu, ctx.has_bias, ctx.xs, ctx.drop = relu, b is not None, xs, (float(drop_p), int(drop_seed))
         ctx.w_param = W if getattr(W, "_emloco_direct_grad", False) else None     # (see `mark_direct_grad`)
+        ctx.pieces = _PIECES_FOR[0]                                                # (see `backward_pieces_for`)
         return y.view(*xs[:-1], N)
 
     @staticmethod
@@ -219,18 +242,18 @@ class LinearFn(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             dx = torch.empty((M, K), dtype=torch.float32, device=dy.device)
             gemm(1, M, K, N, dy2, N, 0, 0, W, K, 0, 1, dx, K, 0, ksplit=1 if dy2.dtype == torch.bfloat16 else _ksplit_for(N, M * K),
-                 b_image=_weight_image(W, M, K, N, K, 1) if (dy2.dtype == torch.float32 and _BWD_PIECES["dx"] == 3) else None,
-                 flags=_bwd_flags("dx"))                                                                                                # dx = dy W
+                 b_image=_weight_image(W, M, K, N, K, 1) if (dy2.dtype == torch.float32 and _bwd_pieces("dx", ctx.pieces) == 3) else None,
+                 flags=_bwd_flags("dx", ctx.pieces))                                                                                                # dx = dy W
             dx = dx.view(ctx.xs)
         if ctx.needs_input_grad[1]:
             g = ctx.w_param.grad if ctx.w_param is not None else None
             if g is not None and g.dtype == torch.float32 and g.shape == (N, K) and g.is_contiguous() and g.data_ptr() % 16 == 0 and dy2.dtype == torch.float32:
                 # the weight gradient goes straight INTO the parameter's .grad (a view of the learner's flat bucket): C += dy^T x in the
                 # GEMM's epilogue instead of a fresh N x K tensor and autograd's accumulation launch behind it
-                gemm(1, N, K, M, dy2, N, 0, 1, x2, K, 0, 1, g, K, 0, ksplit=_ksplit_for(M, N * K), flags=GEMM_ACC | _bwd_flags("dw"))
+                gemm(1, N, K, M, dy2, N, 0, 1, x2, K, 0, 1, g, K, 0, ksplit=_ksplit_for(M, N * K), flags=GEMM_ACC | _bwd_flags("dw", ctx.pieces))
             else:
                 dW = torch.empty((N, K), dtype=torch.float32, device=dy.device)
-                gemm(1, N, K, M, dy2, N, 0, 1, x2, K, 0, 1, dW, K, 0, ksplit=_ksplit_for(M, N * K), flags=_bwd_flags("dw"))   # dW = dy^T x
+                gemm(1, N, K, M, dy2, N, 0, 1, x2, K, 0, 1, dW, K, 0, ksplit=_ksplit_for(M, N * K), flags=_bwd_flags("dw", ctx.pieces))   # dW = dy^T x
         if need_db and db is None:
             db = colsum(dy2)
         return dx, dW, db, None, None, None, None

@@ -461,6 +461,19 @@ def crowd_policy_refusal(env_cfg, network, use_policy, train_policy, test, cnn_b
     if network not in NETWORKS:
         return f"run.py --cfg_train: network '{network}' is not built (params.network.name: one of {', '.join(NETWORKS)})"
     crowd = is_crowd_config(env_cfg)
+    from .crowd_people import config_block
+    if config_block(env_cfg):
+        # group_obs: the map carries no stamps and the rows end in the `people` block, which the sept network's point-net branch reads
+        # (amp_network_sept_builder.py); frozen, --test and --train_policy alike -- its layers are GEMMs with a backward
+        if network == "amp_sept_cnn":
+            return ("run.py: the configuration has group_obs: True, and the policy network 'amp_sept_cnn' does not read the 'people' block "
+                    "it appends to the observation (its map slice assumes the map ends the row).  The people block is read by the sept "
+                    "network's point-net branch: pass --cfg_train emloco_amd/data/cfg/train/rlg/amp_humanoid_smpl_sept_task.yaml, or none")
+        if env_cfg.get("velocity_map", False):
+            return ("run.py: the configuration has group_obs: True with velocity_map: True, and the sept network's task MLP reads a "
+                    "one-channel 'heightmap' block (amp_network_sept_builder.py:113-116): set velocity_map: False, as "
+                    "emloco_amd/data/cfg/pacer_group_obs.yaml does")
+        return None
     if train_policy and (crowd or network == "amp_sept_cnn") and not (cnn_backward and network == "amp_sept_cnn"):
         return ("run.py --train_policy: the CNN policy of the crowd sensor (amp_network_sept_cnn_builder.py, network amp_sept_cnn) runs as "
                 "inference only by default -- the CNN trunk's backward is not built into the default run, so it cannot be trained without "

@@ -688,6 +688,50 @@ int emloco_crowd_contacts_reduce(int n_env, int games_per_env, const EmlocoCrowd
  * minimum over the envs with a neighbour step), then totals is cleared.  A NULL pointer, n_env < 1: -1. */
 int emloco_crowd_contacts_epoch_reduce(int n_env, double *totals, double *epoch, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * The group observation (cfg["env"]["group_obs"]; humanoid_pedestrain_terrain.py:312-335,444-450,481-484 and
+ * compute_group_observation :1613-1666): the EMLOCO_PEOPLE_JOINTS selected joints and the root velocity of the EMLOCO_PEOPLE_TOPK
+ * nearest members of the env's group, in the env's heading frame.  Env e belongs to group e / group_size, as in the crowd sensor.
+ * All arithmetic is fp32 in the stated order, no contraction:
+ *   distance from e to member m:  d = p_root(m) - p_root(e), dist = sqrtf((d.x d.x + d.y d.y) + d.z d.z), z included; a non-finite
+ *       distance counts as +inf
+ *   selection:  the five members other than e itself with the lowest (dist, member index), ascending.  DEPARTURE: the reference takes
+ *       topk(6) and drops the first hit, which is the env itself only while no other member is at distance 0, and torch.topk leaves
+ *       the order among equal distances unspecified (with all roots equal the reference's function drops member 4 for every env; the
+ *       shipped crowd configuration resets every env to one spot, so ties are the common case at the first step).  The rule here
+ *       equals the reference's whenever the distances are distinct.
+ *   row, neighbour-major (the reference's bytes, whatever its view(B, -1, top_k, 3) suggests):
+ *       [0, 150)    [k][j][xyz]  position of body EMLOCO_PEOPLE_BODIES[j] of neighbour k minus the env's ROOT position
+ *       [150, 165)  [k][xyz]     the neighbour's root linear velocity (absolute, not relative)
+ *       each triple rotated by the inverse heading quaternion of the env's root rotation (calc_heading_quat_inv, my_quat_rotate: the
+ *       functions of the location observation); a neighbour with dist > EMLOCO_PEOPLE_FAR has its 30 + 3 values written as zeros
+ *   mirrored row (:481-484): the same 55 triples with y negated.  DEPARTURE: the reference finds the block at
+ *       traj + num_height_points, which with velocity_map lies inside the height map; here the mirrored block is the block's own
+ *       columns, whatever the map's width.
+ * The rows go to columns [col, col + EMLOCO_PEOPLE_WIDTH) of obs and flip_obs (row stride obs_stride floats); no other byte of
+ * either is touched.  The selection is a minimum over the integer key (distance bits, member index): the same bytes from run to
+ * run. */
+#define EMLOCO_PEOPLE_TOPK 5
+#define EMLOCO_PEOPLE_JOINTS 10
+#define EMLOCO_PEOPLE_WIDTH 165
+#define EMLOCO_PEOPLE_FAR 10.0f
+#define EMLOCO_PEOPLE_BODIES {0, 1, 5, 9, 3, 7, 16, 21, 18, 23}
+typedef struct EmlocoCrowdPeople {
+    int32_t n_env, group_size;      /* group_size >= EMLOCO_PEOPLE_TOPK + 1 divides n_env */
+    int32_t obs_stride, col;        /* floats per row of obs / flip_obs; 0 <= col, col + EMLOCO_PEOPLE_WIDTH <= obs_stride */
+    const float *rb_state;          /* [E][24][13] */
+    float *roots_ws;                /* [E][4] workspace: the root positions, packed */
+    float *obs;                     /* [E][obs_stride] */
+    float *flip_obs;                /* [E][obs_stride] */
+    int32_t *neighbours;            /* [E][EMLOCO_PEOPLE_TOPK] the chosen members' env ids, nearest first, or NULL */
+} EmlocoCrowdPeople;
+
+/* Two launches on the one stream: the packed roots of ALL n_env members, then the rows (and neighbours) of every env
+ * (dev_env_ids == NULL) or of the n listed envs (entries of -1 are skipped).  A NULL structure or buffer, group_size < 6 (five
+ * others must exist; the reference's topk(6) fails there too), n_env not a positive multiple of group_size, col < 0 or
+ * col + 165 > obs_stride, n < 0: -1 with the argument named in emloco_last_error(), nothing is launched. */
+int emloco_task_crowd_people(const EmlocoCrowdPeople *p, const int32_t *dev_env_ids, int n, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
