@@ -511,8 +511,15 @@ class AMPAgent:
         # Round 6 -- order of issue.  The two normalisers are independent objects: the AMP one sees its three batches in the reference's
         # order on the DISCRIMINATOR's arm (the only reader of its results), the observation one sees obs, flipped, next in the
         # reference's order on the caller's stream.  Each arm forks as soon as its inputs exist: the discriminator before anything
-        # else, the critic behind the normalised observations and ahead of the flipped / next ones (before: all six normaliser chains --
-        # 36 launches -- on the stream every arm forks from, ahead of every fork).
+        # else, the critic -- for a network that does not read the moments -- behind the normalised observations and ahead of the flipped /
+        # next ones (before: all six normaliser chains -- 36 launches -- on the stream every arm forks from, ahead of every fork).
+        # The people network is the exception: its forward READS the observation normaliser's moments (`eval_task` un-normalises the
+        # people columns through live aliases of `running_mean` / `running_var`), so the updates have a reader as well.  The reference
+        # normalises obs, flipped and next before it calls the model (amp_continuous.py:345-377): every evaluation of one step
+        # un-normalises with the moments after the step's third update.  With a `people` block all three observation updates are
+        # therefore issued on the caller's stream AHEAD of the critic's fork: the critic no longer reads the moments after the first
+        # update only, and no arm reads them while the caller's stream still writes them (an arm waits for the caller's stream at its
+        # fork and for nothing later).  Networks without the block issue what they issued before, in the same order.
         n_amp = self._amp_minibatch_size
         stack_actor = self.motion_sym_loss and self._stack_actor and d["obs"].is_cuda
         if branch_streams is not None and dropout_masks is not None:      # (allocated on the caller's stream, read on an arm's)
@@ -545,7 +552,13 @@ class AMPAgent:
                 disc_agent_replay_logit = net.eval_disc(torch.cat([mul(amp_obs, m(0)), mul(amp_replay, m(1))], dim=0))
                 disc_demo_logit, grad_pen = disc_forward_with_grad_penalty(net, amp_demo, m(2))
             disc_info = self._disc_loss(disc_agent_replay_logit, disc_demo_logit, grad_pen)
+        def flipped_and_next():
+            return (self._preproc_obs(d["flip_obs"]), self._preproc_obs(d["next_obses"])) if self.motion_sym_loss else (None, None)
+
+        early = bool(getattr(net, "has_people", False))      # the network reads the moments: every update ahead of the critic's fork
         obs = self._preproc_obs(d["obs"])
+        if early:
+            flip_n, next_n = flipped_and_next()
         if branch_streams is not None:
             obs.record_stream(s_c)
         heads = self._fused_heads and obs.is_cuda
@@ -556,9 +569,8 @@ class AMPAgent:
             else:
                 c_info = self._critic_loss(d["old_values"], values, self.e_clip, d["returns"], self.clip_value)
                 c_loss = torch.mean(c_info["critic_loss"])
-        flip_n = next_n = None
-        if self.motion_sym_loss:
-            flip_n, next_n = self._preproc_obs(d["flip_obs"]), self._preproc_obs(d["next_obses"])
+        if not early:
+            flip_n, next_n = flipped_and_next()
         s_loss = None
         if self.motion_sym_loss and not stack_actor:         # (two more actor evaluations, on an arm of their own)
             if branch_streams is not None:
