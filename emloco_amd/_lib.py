@@ -216,6 +216,24 @@ class CrowdPeople(C.Structure):
                 ("neighbours", C.c_void_p)]
 
 
+SPAWN_CROWDED, SPAWN_NO_GROUND, SPAWN_MAX_TRIES, SPAWN_MAX_GROUP = 1, 2, 8, 2048          # EMLOCO_SPAWN_*
+
+
+class CrowdSpawnInfo(C.Structure):
+    """EmlocoCrowdSpawnInfo (include/emloco_task.h): what the crowd spawn decided for one env."""
+    _fields_ = [("clearance2", C.c_float), ("tried", C.c_int32), ("flags", C.c_int32), ("order", C.c_int32)]
+
+
+class CrowdSpawn(C.Structure):
+    """EmlocoCrowdSpawn (include/emloco_task.h): the crowd spawn's inputs, workspace and outputs."""
+    _fields_ = [("n_env", C.c_int32), ("group_size", C.c_int32), ("tries", C.c_int32), ("root_stride", C.c_int32),
+                ("rows", C.c_int32), ("cols", C.c_int32), ("hscale", C.c_float),
+                ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float),
+                ("extent", C.c_float), ("min_dist", C.c_float), ("_pad", C.c_int32),
+                ("roots", C.c_void_p), ("walkable", C.c_void_p), ("centres", C.c_void_p), ("mark_ws", C.c_void_p),
+                ("place_xy", C.c_void_p), ("info", C.c_void_p)]
+
+
 class LocoValStep(C.Structure):
     """EmlocoLocoValStep (include/emloco_predictor.h)."""
     _fields_ = [("n_env", C.c_int32), ("step_to_pred", C.c_int32), ("gamma", C.c_float), ("inversion_penalty", C.c_float),

@@ -1,9 +1,10 @@
 // crowd_capi.hip -- C ABI (include/emloco_task.h) over the crowd-aware terrain sensor's kernels, the crowd contact audit's and the
-// group observation's.
+// group observation's and the crowd spawn's.
 #include <hip/hip_runtime.h>
 #include "crowd_kernels.hip"
 #include "crowd_contact_kernels.hip"
 #include "crowd_people_kernels.hip"
+#include "crowd_spawn_kernels.hip"
 #include "capi_error.h"
 
 using emloco::capi_fail;
@@ -80,6 +81,20 @@ int emloco_task_crowd_people(const EmlocoCrowdPeople *p, const int32_t *dev_env_
     EMLOCO_HIPCHK(hipGetLastError());
     const unsigned grid = crowd_grid((rows + emloco::kPeopleWaves - 1) / emloco::kPeopleWaves);
     hipLaunchKernelGGL(emloco::crowd_people_kernel, dim3(grid), dim3(emloco::kPeopleThreads), 0, st, *p, dev_env_ids, rows);
+    EMLOCO_HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int emloco_task_crowd_spawn(const EmlocoCrowdSpawn *s, const int32_t *dev_env_ids, int n, const float *u, void *stream) {
+    const char *who = "emloco_task_crowd_spawn";
+    if (const char *why = emloco::crowd_spawn_refusal(s, dev_env_ids, n, u)) return capi_fail(EMLOCO_E_ARG, who, why);
+    hipStream_t st = (hipStream_t)stream;
+    const int rows = dev_env_ids ? n : s->n_env;
+    if (rows == 0) return 0;
+    hipLaunchKernelGGL(emloco::crowd_spawn_mark_kernel, dim3((unsigned)((rows + emloco::kSpawnMarkThreads - 1) / emloco::kSpawnMarkThreads)),
+                       dim3(emloco::kSpawnMarkThreads), 0, st, *s, dev_env_ids, rows);
+    EMLOCO_HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(emloco::crowd_spawn_place_kernel, dim3((unsigned)(s->n_env / s->group_size)), dim3((unsigned)(s->tries * 64)), 0, st, *s, u, rows);
     EMLOCO_HIPCHK(hipGetLastError());
     return 0;
 }

@@ -86,6 +86,14 @@ class HumanoidPedestrianTerrain(humanoid_traj.HumanoidTraj):
         if self._crowd_mode and self._divide_group:
             group_layout(self.num_envs, self._group_num_people)               # refuses numEnvs that is no multiple, by name
         self._crowd = None
+        # group_spawn (this project's key, emloco_amd/crowd_spawn.py): a reset places the members of a group apart, on the device.  Needs
+        # divide_group, which makes the configuration a crowd one: the subclass below builds the spawn at its first reset
+        from ...crowd_spawn import config_block as spawn_block, spawn_refusal
+        why = spawn_refusal(cfg["env"], self._group_num_people)
+        if why:
+            raise NotImplementedError(why)
+        self._group_spawn = spawn_block(cfg["env"])["on"]
+        self._spawn = None
         self.num_height_points = self.sensor_res * self.sensor_res
         self.num_center_height_points = 9
         self.center_height_points = self.init_center_height_points()
@@ -503,6 +511,8 @@ class HumanoidPedestrianTerrain(humanoid_traj.HumanoidTraj):
         new_root_xy = self.terrain.sample_valid_locations(self.num_envs, env_ids)
         if flags.fixed:
             new_root_xy[:, 0], new_root_xy[:, 1] = 50, 55          # :588
+        if getattr(self, "_group_spawn", False):                   # the members of a group apart, decided on the device
+            new_root_xy = self._spawn_root_xy(env_ids)
         root_pos[:, 0:2] = new_root_xy
         root_states = torch.cat([root_pos, root_rot], dim=1)
         center_height = self.get_center_heights(root_states, env_ids=env_ids).mean(dim=-1)
@@ -546,6 +556,25 @@ class HumanoidPedestrianTerrainCrowd(HumanoidPedestrianTerrain):
             self._people = CrowdPeople(rb_state=self._rigid_body_state, n_env=self.num_envs, group_size=self._group_num_people,
                                        obs=self.obs_buf, flip_obs=self._flip_obs_buf, col=self.obs_buf.shape[1] - L.PEOPLE_WIDTH)
         return self._make_post_bufs_on(self._crowd_src_obs, self._crowd_src_flip)
+
+    def _make_spawn(self):
+        """The crowd spawn on this task's root states and terrain (emloco_amd/crowd_spawn.py).  The field is the whole height field, border
+        included; a square that leaves it less the margin, or a centre on ground nobody can stand on, is refused by key."""
+        from ...crowd_spawn import CrowdSpawn, config_block, resolve, spawn_refusal
+        hs = float(self.terrain.horizontal_scale)
+        field = (self.terrain.tot_rows * hs, self.terrain.tot_cols * hs)
+        walkable = self.terrain.walkable_field
+        why = spawn_refusal(self.cfg["env"], self._group_num_people, field, walkable.cpu().numpy(), hs)
+        if why:
+            raise NotImplementedError(why)
+        b = resolve(config_block(self.cfg["env"]), self._group_num_people, *field)
+        return CrowdSpawn(roots=self._humanoid_root_states, n_env=self.num_envs, group_size=self._group_num_people, walkable=walkable,
+                          hscale=hs, min_dist=b["min_dist"], tries=b["tries"], extent=b["extent"], centre=b["centre"], margin=b["margin"])
+
+    def _spawn_root_xy(self, env_ids):
+        if self._spawn is None:
+            self._spawn = self._make_spawn()
+        return self._spawn.place(env_ids)
 
     def _launch_post(self, mode, env_ids=None):
         super()._launch_post(mode, env_ids)

@@ -171,6 +171,55 @@ def pop_test_options(argv):
     return opt
 
 
+# ---------------------------------------------------------------------------------------------------------------- the crowd spawn
+def pop_spawn_options(argv):
+    """Remove --group_spawn and its sub-flags from argv (get_args does not know them): None without --group_spawn, else the keys they
+    set in cfg["env"] (emloco_amd/crowd_spawn.py).  A sub-flag without --group_spawn, a value that does not parse and
+    EMLOCO_OVERLAP_RESET=1 stop the run by name."""
+    on = "--group_spawn" in argv
+    if on:
+        argv.remove("--group_spawn")
+    raw = {k: _pop_opt(argv, "--group_spawn_" + k) for k in ("min_dist", "extent", "tries")}
+    if not on:
+        given = [k for k, v in raw.items() if v is not None]
+        if given:
+            raise SystemExit(f"run.py: --group_spawn_{given[0]} sets up the crowd spawn: turn it on with --group_spawn")
+        return None
+    if os.environ.get("EMLOCO_OVERLAP_RESET", "0") == "1":
+        raise SystemExit("run.py: --group_spawn places members in the host reset path of the sequential launch arrangement; "
+                         "EMLOCO_OVERLAP_RESET=1 switches on a reset chain that never asks it")
+    keys = dict(group_spawn=True)
+    try:
+        if raw["min_dist"] is not None:
+            keys["group_spawn_min_dist"] = float(raw["min_dist"])
+        if raw["extent"] is not None:
+            keys["group_spawn_extent"] = "auto" if raw["extent"] == "auto" else float(raw["extent"])
+        if raw["tries"] is not None:
+            keys["group_spawn_tries"] = int(raw["tries"])
+    except ValueError as e:
+        bad = [k for k in ("min_dist", "extent", "tries") if raw[k] is not None and "group_spawn_" + k not in keys][0]
+        raise SystemExit(f"run.py: --group_spawn_{bad}: {e}")
+    return keys
+
+
+def apply_spawn_options(keys, env_cfg):
+    """Set the keys of --group_spawn on cfg["env"]; a configuration the crowd spawn cannot run on stops here, before the simulator is built"""
+    if keys is None:
+        return
+    from .crowd_spawn import spawn_refusal
+    if not env_cfg.get("divide_group", False):
+        raise SystemExit("run.py --group_spawn: the configuration has no groups (divide_group); the crowd spawn places the members of a "
+                         "group apart (emloco_amd/data/cfg/pacer_group.yaml is one that has them)")
+    why = spawn_refusal(dict(env_cfg, **keys))
+    if why:
+        raise SystemExit(f"run.py --group_spawn: {why}")
+    env_cfg.update(keys)
+
+
+def _spawn_of(task):
+    return getattr(task, "_spawn", None)
+
+
 # ---------------------------------------------------------------------------------------------------------------- the flight recorder
 def capture_options(argv):
     """Remove the flight recorder's options from argv (get_args does not know them): None without --capture, else the arguments of
@@ -379,6 +428,11 @@ class LocoValTrainee:
             from .crowd_contacts import epoch_tail
             info["crowd"] = self.crowd.end_epoch()
             info["tail"] = info.get("tail", "") + epoch_tail(info["crowd"])
+        spawn = _spawn_of(getattr(a, "task", None))
+        if spawn is not None and self.stats is not None:  # the epoch's placements (this rank's envs): one read of four totals
+            from .crowd_spawn import epoch_tail as spawn_tail
+            info["spawn"] = spawn.totals(clear=True)
+            info["tail"] = info.get("tail", "") + spawn_tail(info["spawn"])
         return info
 
     def save(self, mof, epoch=None):
@@ -494,6 +548,7 @@ def main(argv=None):
     train_opt = train_options(argv)                      # (--steps leaves argv; a bad combination stops the run before any device call)
     # --test (the reference's player, amp_value_players.py): its own options, checked before anything touches a device
     opt = pop_test_options(argv)
+    spawn_opt = pop_spawn_options(argv)
     cap_opt = capture_options(argv)
     if cap_opt is not None and "--test" not in argv:
         train_opt["driver"] = True                       # the recorder is drained once per epoch: the run goes through the driver
@@ -549,6 +604,7 @@ def main(argv=None):
         args.num_envs = shard_range(int(args.num_envs), rank, world)[1]
     cfg, cfg_train, _ = load_cfg(args)
     fill_flags(args)
+    apply_spawn_options(spawn_opt, cfg["env"])
     policy_cfg = load_policy_cfg(args) if (use_policy or train_policy or args.test) else None
     network = policy_cfg["params"]["network"].get("name", "amp_sept") if policy_cfg else None
     refusal = crowd_policy_refusal(cfg["env"], network, use_policy, train_policy, args.test, cnn_backward=cnn_backward)
@@ -708,6 +764,11 @@ def _run_test(args, env, policy_ckpt, games_num, max_steps, eval_out, eval_recor
     torch.cuda.synchronize()
     rep["seconds"] = time.time() - t0
     say(f"{rep['steps']} steps of {ev.envs_total} envs in {rep['seconds']:.2f} s")
+    if _spawn_of(task) is not None:          # --group_spawn: inside `crowd` with --eval_crowd, beside it otherwise (this rank's envs)
+        from .crowd_spawn import report_line
+        block = _spawn_of(task).totals()
+        (rep["crowd"] if eval_crowd is not None else rep)["spawn"] = block
+        say(report_line(block))
     if capture is not None:                  # --test: one drain at the end of the run
         rep.update(capture.end_epoch())
         say(f"flight recorder: {rep['captures']} captures in {capture.path}")
@@ -776,6 +837,11 @@ def _run_compare(args, env, bundle, valuenet, compare, games_num, max_steps, gam
     torch.cuda.synchronize()
     seconds = time.time() - t0
     say(f"{ev.steps_run} steps of {ev.envs_total} envs in {seconds:.2f} s, {len(nets)} networks on the same games")
+    if _spawn_of(task) is not None:          # --group_spawn: inside `crowd` with --eval_crowd, beside it otherwise (this rank's envs)
+        from .crowd_spawn import report_line
+        block = _spawn_of(task).totals()
+        (rep["crowd"] if eval_crowd is not None else rep)["spawn"] = block
+        say(report_line(block))
     if capture is not None:                  # one drain at the end of the run
         say(f"flight recorder: {capture.end_epoch()['captures']} captures in {capture.path}")
     if eval_records:
@@ -805,6 +871,8 @@ def _run_compare(args, env, bundle, valuenet, compare, games_num, max_steps, gam
                 out["tracking"] = rep["tracking"]
             if eval_crowd is not None:
                 out["crowd"] = rep["crowd"]
+            elif "spawn" in rep:
+                out["spawn"] = rep["spawn"]
             json.dump(out, f, indent=1, default=float)
     if world > 1:
         torch.distributed.destroy_process_group()

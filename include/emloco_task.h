@@ -732,6 +732,71 @@ typedef struct EmlocoCrowdPeople {
  * col + 165 > obs_stride, n < 0: -1 with the argument named in emloco_last_error(), nothing is launched. */
 int emloco_task_crowd_people(const EmlocoCrowdPeople *p, const int32_t *dev_env_ids, int n, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * The crowd spawn (cfg["env"]["group_spawn"], this project's key): at a reset every listed member of a group is put on a random
+ * admissible spot of its group's square, at least min_dist from every member of the group that is standing at that moment.  The
+ * reference's placement for groups (Terrain.sample_valid_locations(..., sample_groups=True), humanoid_pedestrain_terrain.py:1196-1204,
+ * never called there) draws a group centre plus a U(-8, 8) m offset per member and checks neither clearance nor walkability.
+ *
+ * Env e belongs to group e / group_size, as in the sensor.  A call gets three things:
+ *   an id list dev_env_ids[n].  Entries of -1 are skipped (and so is any entry outside [0, n_env)).  NULL means every env, and row
+ *       i is env i.
+ *   u[n][tries][2], uniforms in [0, 1) chosen by the caller.  Row i belongs to list position i.  If an env is listed twice, its
+ *       lowest list position counts.
+ *   the roots of all envs, read as roots[e * root_stride + 0/1].  Horizontal distance only.
+ * All arithmetic is fp32 in the stated order, with no contraction.
+ *   candidate k of env e:  t = 2.0f * u - 1.0f;  c = centre[g] + extent * t, one multiply then one add, per axis.
+ *   admissible:  min_x <= c.x <= max_x and min_y <= c.y <= max_y, and walkable[ix * cols + iy] == 0, with ix = (int)(c.x / hscale)
+ *       and iy = (int)(c.y / hscale): IEEE division truncated, the reference's world_points_to_map.  Both indices must lie in
+ *       [0, rows) x [0, cols).  Otherwise the candidate is inadmissible.
+ *   standing members of e's group:  every member j != e whose root x and y are finite, and that is either not listed in this call,
+ *       or is listed and already placed by this call (then at its new spot).
+ *   clearance2(c):  the minimum over standing members of (dx * dx) + (dy * dy).  It is +inf when no member is standing.
+ *   order:  the listed members of a group are placed in ascending env index, one after another.  Each sees the ones placed before
+ *       it at their new spots.
+ *   choice:  take the lowest admissible k with clearance2 >= min_dist * min_dist.  If there is none, take the admissible k with the
+ *       largest clearance2, lowest k on ties, and set flag EMLOCO_SPAWN_CROWDED.  If no candidate is admissible, the spot is
+ *       centre[g], tried = -1, and flag EMLOCO_SPAWN_NO_GROUND is set (and EMLOCO_SPAWN_CROWDED beside it when
+ *       clearance2(centre[g]) < min_dist * min_dist).
+ * Outputs, written for listed envs only; no other byte is touched:
+ *   place_xy[e][2]
+ *   info[e] = {clearance2 of the spot taken, tried = the k taken, flags, order = the env's rank among its group's placements in
+ *       this call}
+ *   mark_ws[E] is a workspace.  It holds -1 everywhere on entry and again on exit.
+ * Nothing in the rule depends on scheduling.  Minima are exact, there are no float atomics, and equal inputs give equal bytes. */
+#define EMLOCO_SPAWN_CROWDED 1
+#define EMLOCO_SPAWN_NO_GROUND 2
+#define EMLOCO_SPAWN_MAX_TRIES 8
+#define EMLOCO_SPAWN_MAX_GROUP 2048
+typedef struct EmlocoCrowdSpawnInfo {
+    float clearance2;
+    int32_t tried, flags, order;
+} EmlocoCrowdSpawnInfo;
+
+typedef struct EmlocoCrowdSpawn {
+    int32_t n_env, group_size;      /* 1 <= group_size <= EMLOCO_SPAWN_MAX_GROUP divides n_env (the group's roots are staged on chip) */
+    int32_t tries, root_stride;     /* 1 <= tries <= EMLOCO_SPAWN_MAX_TRIES; floats between two envs' roots, >= 2 */
+    int32_t rows, cols;             /* of walkable */
+    float hscale;
+    float min_x, max_x, min_y, max_y;   /* the box a spot must lie in, bounds included */
+    float extent, min_dist;         /* half the side of a group's square; both in metres */
+    int32_t _pad;
+    const float *roots;             /* [E] roots, root_stride floats apart: x, y first */
+    const int16_t *walkable;        /* [rows][cols], 0: walkable */
+    const float *centres;           /* [E / group_size][2] */
+    int32_t *mark_ws;               /* [E] workspace, -1 everywhere between calls */
+    float *place_xy;                /* [E][2] */
+    EmlocoCrowdSpawnInfo *info;     /* [E] */
+} EmlocoCrowdSpawn;
+
+/* Two launches on the one stream: the lowest list position of every listed env into mark_ws, then one workgroup per group places
+ * its listed members and clears their marks.  u is on the device.  A NULL structure or buffer, group_size < 1 or above
+ * EMLOCO_SPAWN_MAX_GROUP, n_env not a positive multiple of group_size, tries outside 1..8, root_stride < 2, rows, cols or hscale not
+ * positive, extent not finite and positive, min_dist negative or non-finite, an empty box (min > max, or a NaN bound), n < 0, u NULL
+ * with work to do: -1 with the argument named in emloco_last_error(), nothing is launched.  n == 0 with a list: 0, nothing is
+ * launched. */
+int emloco_task_crowd_spawn(const EmlocoCrowdSpawn *s, const int32_t *dev_env_ids, int n, const float *u, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
