@@ -60,6 +60,7 @@ class _ActorHead(torch.autograd.Function):
         return o
 
     @staticmethod
+    @ops.once_differentiable_node
     def backward(ctx, ga, ge, gb, _gc, _gk):
         mu_, ls_, ac_, on_, ad_ = ctx.saved_tensors
         B, A = mu_.shape
@@ -92,6 +93,7 @@ class _CriticHead(torch.autograd.Function):
         return out[0]
 
     @staticmethod
+    @ops.once_differentiable_node
     def backward(ctx, g):
         v_, vo_, r_ = ctx.saved_tensors
         e_clip, clip_value, shape = ctx.cfg
@@ -120,6 +122,7 @@ class _DiscHead(torch.autograd.Function):
         return o
 
     @staticmethod
+    @ops.once_differentiable_node
     def backward(ctx, ga, _a, gd, _d):
         a_, d_ = ctx.saved_tensors
         z = torch.zeros((), dtype=torch.float32, device=a_.device)

@@ -5,9 +5,11 @@ layer norm below runs in libemloco_hip.so.  There is no fallback: without the li
 """
 import contextlib
 import ctypes as C
+import functools
 import os
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from .. import _lib as L
 from .._lib import EVAL_MAX_NETS, TRACK_MOMENTS, TRACK_SAMPLES, LocoValEval, LocoValNet, LocoValNets, LocoValStep, LocoValTrack  # noqa: F401  (re-exported: callers say ops.LocoValStep)
@@ -19,6 +21,24 @@ EVAL_MOMENTS = 20          # EMLOCO_EVAL_MOMENTS
 
 def _lib():
     return L.require_device()
+
+
+def once_differentiable_node(backward):
+    """torch's `once_differentiable` for the backward of a node built from raw launches, also when the incoming gradient is a constant.
+    torch's decorator arms its "differentiate twice" error only if an incoming gradient requires grad; a `create_graph=True` pass that
+    starts from ones (the discriminator's gradient penalty) would otherwise get a gradient WITHOUT a graph back and train on a penalty
+    whose own gradient is silently zero.  While a graph is being recorded the first incoming gradient is therefore handed on as one that
+    requires grad; the arithmetic is untouched (torch runs the backward itself under no_grad)."""
+    inner = once_differentiable(backward)
+
+    @functools.wraps(backward)
+    def wrapper(ctx, *grads):
+        if torch.is_grad_enabled() and not any(isinstance(g, torch.Tensor) and g.requires_grad for g in grads):
+            first = next((i for i, g in enumerate(grads) if isinstance(g, torch.Tensor) and g.is_floating_point()), None)
+            if first is not None:
+                grads = grads[:first] + (grads[first].detach().requires_grad_(),) + grads[first + 1:]
+        return inner(ctx, *grads)
+    return wrapper
 
 
 def _p(t, offset=0):
@@ -221,6 +241,7 @@ class LinearFn(torch.autograd.Function):
         return y.view(*xs[:-1], N)
 
     @staticmethod
+    @once_differentiable_node
     def backward(ctx, dy):
         x2, W, y = ctx.saved_tensors
         M, K = x2.shape
@@ -273,6 +294,7 @@ class ReluMaskFn(torch.autograd.Function):
         return out
 
     @staticmethod
+    @once_differentiable_node
     def backward(ctx, dy):
         (h2,) = ctx.saved_tensors
         d2 = dy.contiguous()
@@ -292,7 +314,11 @@ def mark_direct_grad(params, on=True):
     """Weights whose gradient `LinearFn.backward` may accumulate directly into `.grad` (GEMM epilogue, C += ...) instead of returning it
     to autograd.  The caller vouches that (1) `.grad` exists and is zeroed before every backward (FlatGradBucket) and (2) every use of
     the weight in one backward pass runs on ONE stream (the accumulations are then stream-ordered; autograd's own accumulation node
-    is what orders gradients that arrive from several streams)."""
+    is what orders gradients that arrive from several streams).
+    The direct path is taken only while `.grad` is a contiguous, 16-byte-aligned fp32 tensor of the weight's shape and the weight itself is
+    what `linear` hands to the GEMM (a K that `linear` pads makes the operand a copy: autograd's path).  Such a backward returns no
+    gradient for the weight to autograd, so `torch.autograd.grad(y, [W])` on a marked weight raises torch's "appears to not have been
+    used in the graph" error (and has by then added dy^T x to `W.grad`): ask for such a gradient with the mark taken back (on=False)."""
     for p_ in params:
         p_._emloco_direct_grad = bool(on)
 
@@ -365,7 +391,8 @@ class FeedForwardFn(torch.autograd.Function):
             return f.view(*xs[:-1], N)
         # the hidden layer is the largest tensor of the step (M x 1024): bf16 in HBM in the reduced-precision mode
         # (the bf16-in-memory GEMM variants serve the 128-wide tiles and 8-byte-aligned rows only: small models keep fp32)
-        h16 = _matmul_precision[0] == "bf16" and N > 32 and F > 32 and K > 32 and F % 4 == 0 and K % 4 == 0 and N % 4 == 0
+        # (nor does an x that does not start on a 16-byte boundary: the launcher refuses a bf16 output behind an unaligned operand)
+        h16 = _matmul_precision[0] == "bf16" and N > 32 and F > 32 and K > 32 and F % 4 == 0 and K % 4 == 0 and N % 4 == 0 and x2.data_ptr() % 16 == 0
         h = torch.empty((M, F), dtype=torch.bfloat16 if h16 else torch.float32, device=x.device)
         f32 = x2.dtype == torch.float32 and not h16
         gemm(1, M, F, K, x2, K, 0, 0, W1c, K, 0, 0, h, F, 0, bias=b1.contiguous(), flags=GEMM_BIAS | GEMM_RELU, drop_p=drop_p, drop_seed=seed1,
@@ -378,6 +405,7 @@ class FeedForwardFn(torch.autograd.Function):
         return f.view(*xs[:-1], N)
 
     @staticmethod
+    @once_differentiable_node
     def backward(ctx, df):
         dx, dW1, db1, dW2, db2 = _ffn_backward(ctx.saved_tensors[:5] if ctx.chain else tuple(ctx.saved_tensors[:4]) + (None,), ctx.chain, ctx.drop, ctx.xs,
                                                ctx.needs_input_grad[0], df)
@@ -472,6 +500,7 @@ class FeedForwardNormFn(torch.autograd.Function):
         return y.view(xs)
 
     @staticmethod
+    @once_differentiable_node
     def backward(ctx, dy, dy_b=None):
         x2, W1b, W2b, h, mbits, xr, gamma, mean, rstd = ctx.saved_tensors
         rows, d = xr.shape
@@ -544,6 +573,7 @@ class FusedAttentionFn(torch.autograd.Function):
         return out
 
     @staticmethod
+    @once_differentiable_node
     def backward(ctx, dout):
         qkv, key_pad, out, lse = ctx.saved_tensors
         nhead, scale, Sq = ctx.nhead, ctx.scale, ctx.Sq
@@ -609,6 +639,7 @@ class AttentionFn(torch.autograd.Function):
         return out
 
     @staticmethod
+    @once_differentiable_node
     def backward(ctx, dout):
         qkv, P, M = ctx.saved_tensors
         nhead, scale = ctx.nhead, ctx.scale
@@ -660,6 +691,7 @@ class LayerNormFn(torch.autograd.Function):
         return y.view(shp)
 
     @staticmethod
+    @once_differentiable_node
     def backward(ctx, dy, dy_b=None):
         xr, gamma, mean, rstd = ctx.saved_tensors
         rows, d = xr.shape
@@ -678,7 +710,10 @@ class LayerNormFn(torch.autograd.Function):
 
 
 def layer_norm(x, res, gamma, beta, eps=1e-5, fork=False):
-    """fork=True returns (y, y'): hand y to the next sublayer and y' to its residual branch (see LayerNormFn.forward)."""
+    """fork=True returns (y, y'): hand y to the next sublayer and y' to its residual branch (see LayerNormFn.forward).
+    res has x's shape (nothing is broadcast: the kernel reads one residual row per row of x); another shape is refused."""
+    if res is not None and res.shape != x.shape:
+        raise ValueError(f"layer_norm: res {tuple(res.shape)} must have the shape of x {tuple(x.shape)}")
     if fork and not (torch.is_grad_enabled() and (x.requires_grad or (res is not None and res.requires_grad))):
         y = LayerNormFn.apply(x, res, gamma, beta, eps)
         return y, y
@@ -704,6 +739,7 @@ class LocoValFn(torch.autograd.Function):
         return value.view(B, 1), x100
 
     @staticmethod
+    @once_differentiable_node
     def backward(ctx, dvalue, _dx100):
         traj, pose, vel, w1, w2, w3, value, x100, h1, h2, ang = ctx.saved_tensors
         B, ts = traj.shape[0], traj.shape[-1]
@@ -764,6 +800,7 @@ class LocoValVariantFn(torch.autograd.Function):
         return value.view(B, 1), x, pose_rot
 
     @staticmethod
+    @once_differentiable_node
     def backward(ctx, dvalue, _dx, _dpose_rot):
         traj, w1, w2, w3, value, x, h1, h2, ang, *rest = ctx.saved_tensors
         pose = rest.pop(0) if ctx.has_pose else None
